@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the LaMa FFC hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Metric (BASELINE.json): inpainted images/s at 512x512, big-lama, fp32.  One *step* = one pass of the
 hot path over one batch of synthetic input per rank: mask compose -> FFCResNetGenerator (big-lama,
@@ -667,6 +667,29 @@ def timed_region(loop, steps, warmup):
     return dt, range_ok
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loop):
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST timed step, as DIR/<name>.npy in float32 -- the u8 HWC
+    inpainted batch (the batch gathered to rank 0 with a process group).  Above DUMP_LIMIT_BYTES the file holds a fixed strided sample
+    of the flattened array (every n-th element from element 0), the same from run to run.  Rank 0 only."""
+    import numpy as np
+    if loop.dist is not None:
+        k = (loop.step_no - 1) & 1                  # the pair of buffers the last step wrote (StepLoop.step alternates them)
+        out = loop.gathered[k]
+    else:
+        out = loop.u8_ring[0]
+    a = out.cpu().numpy().astype(np.float32)
+    stride = -(-a.nbytes // DUMP_LIMIT_BYTES)
+    if stride > 1:
+        a = np.ascontiguousarray(a.reshape(-1)[::stride])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'inpainted_u8.npy'), a)
+    print(f'bench.py: wrote {os.path.join(out_dir, "inpainted_u8.npy")} {a.shape} (u8 HWC images as float32'
+          f'{f", every {stride}-th element" if stride > 1 else ""})', file=sys.stderr, flush=True)
+
+
 def spawn_command(gpus, argv, port):
     """The torch.distributed.run command line of `python bench.py --gpus N` (one rank per GPU of ONE node, rendezvous on 127.0.0.1) and
     the environment it needs (dmabuf IPC for RCCL)."""
@@ -703,6 +726,8 @@ def main():
     ap.add_argument('--no-photo-leg', action='store_true', help='skip the photo-sized-input leg')
     ap.add_argument('--lib', default=None, help='A/B runs: another build of liblama_hip.so (e.g. lama_amd/lib/liblama_hip_prof.so, whose kernel '
                                                 'switches read LAMA_* variables); the default is the in-tree product library')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write what the last one computed (the u8 inpainted '
+                                                                        'batch, as float32) to DIR/inpainted_u8.npy: outputs of two builds compare file for file')
     ap.add_argument('--cpu-one-thread-leg', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--eager-leg', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -761,6 +786,8 @@ def main():
     if args.split_batch:                      # --split-batch 1|2|4: override the generator's rule and its timing check
         model.generator.split_batch = args.split_batch
     dt, range_ok = timed_region(loop, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop)
     nsplit = model.generator._split_parts((BATCH, 4, RES, RES), device)          # (after the generator's own verification of the split plan)
     split_check = {f'{k[0][0]}x{k[0][2]}x{k[0][3]}': v for k, v in getattr(model.generator, 'split_decisions', {}).items()} or None   # every shape tune_split decided in this process
     if not range_ok:
