@@ -1258,7 +1258,7 @@ static inline int wg_ksplit(int batch, int bands, int MG) {
 // geometry pays for lanes outside the plane and -- like every one-workgroup-per-CU launch -- for whole rounds: a little more than a round of units
 // is two rounds (1 x 135 x 240: 272 units: 113 us against ~95 for 255 direct tiles; 1 x 168 x 168: 252 units: 65 against 92).  Cost model in us,
 // constants from profiles/r06_winograd_any_size.txt: a round of workgroups 8 + 45 / KS, the output transform 14 (+ 5 per extra slice) per 32768
-// pixels, a round of the direct kernel 92.
+// pixels, a round of the direct kernel 92 (fitted at 128 output rows, MG = 1; wider launches have constants of their own, below).
 bool CB_NAME(lama_cb_wino_preferred)(int batch, int cout, int cin, int H, int W) {
     WgGeo g;
     if (!wg_shape(cout, cin, H, W, &g)) return false;
@@ -1271,6 +1271,13 @@ bool CB_NAME(lama_cb_wino_preferred)(int batch, int cout, int cin, int H, int W)
     for (int tl = 5; tl >= 3; --tl) {
         const long long nt = (long long)batch * lama_ceil_div(W, 1 << tl) * lama_ceil_div(H, 128 >> tl);
         if (!tiles || (nt + 255) / 256 < (tiles + 255) / 256) tiles = nt;
+    }
+    if (MG > 1) {
+        // more than one 128-row group (the 512 -> 512 convs of the pix2pixhd_global blocks), refitted on 12 plane shapes timed both ways
+        // (profiles/regular_conv512.txt): a round of Winograd workgroups costs 58-65 us at KS = 1 (8 + 52 / KS), a round of the direct kernel
+        // 82-94 (88); with both constants fitted at this width the rule needs no safety margin
+        const double wino_m = (double)((units * KS + 255) / 256) * (8.0 + 52.0 / KS) + px * (14.0 + 5.0 * (KS - 1));
+        return wino_m < (double)((tiles * MG + 255) / 256) * 88.0;
     }
     const double direct = (double)((tiles * MG + 255) / 256) * 92.0;
     return wino < 0.92 * direct;

@@ -2,12 +2,15 @@
 import logging
 
 from .ffc import FFCResNetGenerator
+from .pix2pixhd import GlobalGenerator
 
 
 def make_generator(config, kind, **kwargs):
     logging.info(f'Make generator {kind}')
     if kind == 'ffc_resnet':
         return FFCResNetGenerator(**kwargs)
-    if kind in ('pix2pixhd_multidilated', 'pix2pixhd_global'):
+    if kind == 'pix2pixhd_global':
+        return GlobalGenerator(**kwargs)
+    if kind == 'pix2pixhd_multidilated':
         raise NotImplementedError(f'generator kind {kind} is outside the FFC hot path this package accelerates')
     raise ValueError(f'Unknown generator kind {kind}')

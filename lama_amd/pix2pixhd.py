@@ -1,0 +1,428 @@
+"""Host-side mirror of ``GlobalGenerator`` / ``ResnetBlock`` of ``saicinpainting/training/modules/pix2pixhd.py`` (the
+``pix2pixhd_global`` generator kind of the big-lama-regular and lama-regular checkpoints) whose forward runs on the gfx950 kernels
+of liblama_hip.so.
+
+Same class names, constructor signatures, sub-module names and therefore ``state_dict`` keys as the reference
+(``generator.model.13.conv_block.1.weight`` ...).  As in ``lama_amd.ffc``, the ``nn.Conv2d`` / ``nn.BatchNorm2d`` /
+``nn.ConvTranspose2d`` objects are parameter containers only: every conv carries its bias (``nn.Conv2d``'s default), which folds
+with the eval-mode BatchNorm behind it into one epilogue shift ``shift + scale * b``.  There is no eager / CPU fallback.
+
+Inference only.  Options no shipped config uses (dilated blocks, FFC positions, depthwise blocks, other conv kinds / norms /
+paddings, ``affine``, dilation) raise ``NotImplementedError`` at construction.
+"""
+from __future__ import annotations
+
+import collections
+import warnings
+from typing import List, Optional
+
+import torch
+import torch.nn as nn
+
+from . import _lib as L
+from ._lib import LamaError, LamaRangeError
+from .ffc import (_ACT, _DEFAULT_EXEC, _RANGE_MSG, Activation, BatchNorm2dEval, Conv2dOut, ConvTranspose2dUp, LayerSequence,
+                  ReflectionPad2d, _bn_fold, _Exec, _HipModule)
+
+
+def _is_bn(norm_layer) -> bool:
+    return norm_layer == 'bn' or norm_layer is nn.BatchNorm2d
+
+
+def _is_relu(act) -> bool:
+    return isinstance(act, nn.ReLU) or act is nn.ReLU
+
+
+class Conv2dBN(nn.Conv2d, _HipModule):
+    """``nn.Conv2d`` parameter container (bias included) whose forward is ``lama_conv2d_fwd``.  ``run`` folds the eval-mode
+    BatchNorm that follows it in ``generator.model`` into the packed weights and the epilogue shift, and takes the activation and
+    the residual add into the same launch.  A 3x3 stride-1 conv runs as Winograd F(2x2, 3x3) (``lama_winograd_conv3x3_fwd``)
+    when the caller hands it a workspace."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0):
+        nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding)
+        self._packed = None
+        self._exec = _DEFAULT_EXEC
+
+    def pack(self, bn: Optional[nn.BatchNorm2d], wino: bool = False) -> dict:
+        key = (id(bn), self.precision)
+        if self._packed is None or self._packed['key'] != key:
+            lib, w = self._exec.lib, self.weight.detach()
+            b = self.bias.detach().float()
+            if bn is not None:
+                scale, shift = _bn_fold(bn)
+                bias = shift + scale * b
+            else:
+                scale, bias = None, b
+            self._packed = dict(key=key, scale=scale, b=bias.contiguous(),
+                                w=lib.pack_conv_weight(w, scale, stride=self.stride[0], precision=self.precision))
+        pk = self._packed
+        if wino and 'wino' not in pk:
+            # a transformed weight beyond the fp16 split's range keeps the direct kernel (as FFC.pack does)
+            try:
+                pk['wino'] = self._exec.lib.pack_winograd_weight(self.weight.detach(), pk['scale'], self.precision)
+            except LamaRangeError:
+                pk['wino'] = None
+        return pk
+
+    def wino_ok(self, bn) -> bool:
+        """The Winograd form exists for this conv at the current precision (3x3, stride 1, cout % 128, cin % 32, weight in range)."""
+        if (self.kernel_size != (3, 3) or self.stride != (1, 1) or self.precision not in (L.PREC_F16X3, L.PREC_BF16X3)
+                or self.out_channels % 128 or self.in_channels % 32):
+            return False
+        return self.pack(bn, True)['wino'] is not None
+
+    def run(self, src: torch.Tensor, dst: torch.Tensor, bn: Optional[nn.BatchNorm2d] = None, act: int = L.ACT_NONE, pad: int = 0,
+            pad_mode: int = L.PAD_ZERO, resid: Optional[torch.Tensor] = None, wino_ws: Optional[torch.Tensor] = None) -> bool:
+        """src -> dst = act(bn(conv(pad(src)))) [+ resid]; ``resid`` may be ``dst`` itself (every element is read before it is written, by
+        the thread that writes it).  Returns True when the Winograd launch ran."""
+        ex = self._exec
+        pk = self.pack(bn, wino_ws is not None)
+        st = ex.stream(src)
+        rv = None if resid is None else L.view(resid)
+        if wino_ws is not None and pk.get('wino') is not None and pad == 1:
+            try:
+                ex.winograd_conv3x3(L.view(src), pk['wino'], L.view(dst), src.shape[0], wino_ws, pk['b'], act, rv, precision=self.precision,
+                                    stream=st, pad_mode=pad_mode)
+                return True
+            except LamaError as e:      # a view the Winograd entry does not take (alignment): the direct kernel
+                if e.code != L.ERR_UNSUPPORTED:
+                    raise
+        ex.conv2d(L.view(src), pk['w'], L.view(dst), src.shape[0], self.kernel_size[0], self.stride[0], pad, pad_mode, False, pk['b'], act, rv,
+                  precision=self.precision, stream=st)
+        return False
+
+    def out_shape(self, shape, pad: int):
+        B, _, H, W = shape
+        k, s = self.kernel_size[0], self.stride[0]
+        return (B, self.out_channels, (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1)
+
+    def forward(self, x):
+        self._exec.check(x)
+        x = x.contiguous()
+        y = torch.empty(self.out_shape(x.shape, self.padding[0]), device=x.device, dtype=torch.float32)
+        with self._exec.range_scope(x, self.precision):
+            self.run(x, y, None, L.ACT_NONE, self.padding[0], L.PAD_ZERO)
+        return y
+
+
+class ResnetBlock(_HipModule):
+    """pix2pixhd.py:30-90 with reflect padding: x + BN(conv3x3(pad(ReLU(BN(conv3x3(pad(x))))))), two launches (the second one's epilogue
+    adds the residual)."""
+
+    def __init__(self, dim, padding_type, norm_layer, activation=nn.ReLU(True), use_dropout=False, conv_kind='default', dilation=1,
+                 in_dim=None, groups=1, second_dilation=None):
+        super().__init__()
+        if padding_type != 'reflect':
+            raise NotImplementedError(f'ResnetBlock: padding {padding_type!r} (only reflect, the shipped configs\' padding, is implemented)')
+        if not _is_bn(norm_layer):
+            raise NotImplementedError('ResnetBlock: only BatchNorm2d (eval) is folded into the kernels')
+        if conv_kind not in ('default', nn.Conv2d):
+            raise NotImplementedError(f'ResnetBlock: conv_kind {conv_kind!r} (only default)')
+        if dilation != 1 or second_dilation not in (None, 1):
+            raise NotImplementedError('ResnetBlock: dilation != 1 is not used by the shipped configs')
+        if use_dropout or in_dim is not None or groups != 1:
+            raise NotImplementedError('ResnetBlock: dropout / in_dim / groups are not used by the shipped configs')
+        if not _is_relu(activation):
+            raise NotImplementedError('ResnetBlock: the activation must be ReLU')
+        self.in_dim = in_dim
+        self.dim = dim
+        self.conv_block = LayerSequence(ReflectionPad2d(1), Conv2dBN(dim, dim, 3), BatchNorm2dEval(dim), Activation('relu'),
+                                        ReflectionPad2d(1), Conv2dBN(dim, dim, 3), BatchNorm2dEval(dim))
+        self.out_channnels = dim           # (sic: the reference's attribute name)
+
+    def convs(self):
+        cb = self.conv_block
+        return (cb[1], cb[2]), (cb[5], cb[6])
+
+    def run(self, src: torch.Tensor, t: torch.Tensor, dst: torch.Tensor, wino_ws: Optional[torch.Tensor] = None) -> tuple:
+        """conv A (bias + BN + ReLU) into the scratch ``t``, conv B (bias + BN + residual ``src``) into ``dst`` -- which may be ``src``: the
+        state then walks in one buffer.  Returns which launches took the Winograd form."""
+        (ca, bna), (cb, bnb) = self.convs()
+        wa = ca.run(src, t, bna, L.ACT_RELU, 1, L.PAD_REFLECT, wino_ws=wino_ws)
+        wb = cb.run(t, dst, bnb, L.ACT_NONE, 1, L.PAD_REFLECT, resid=src, wino_ws=wino_ws)
+        return wa, wb
+
+    def forward(self, x):
+        self._exec.check(x)
+        x = x.contiguous()
+        t, dst = torch.empty_like(x, dtype=torch.float32), torch.empty_like(x, dtype=torch.float32)
+        with self._exec.range_scope(x, self.precision):
+            self.run(x, t, dst)
+        return dst
+
+
+class GlobalGenerator(_HipModule):
+    """pix2pixhd.py:341-436.  ``forward(x[B,input_nc,H,W]) -> [B,output_nc,H,W]``; ``.model`` has the reference's layout
+    (stem 0-3, downsampling 4-12, ``n_blocks`` ResnetBlocks, 3 x (ConvTranspose2d, BN, ReLU), pad + 7x7 conv, output activation).
+
+    The fused forward is a plan of HIP launches per input shape: stem (reflect pad + 7x7 conv + BN + ReLU), three stride-2 convs + BN +
+    ReLU, the blocks on ONE state buffer (conv A into a scratch, conv B in place over the block input), three ConvTranspose2d + BN + ReLU
+    and the 7x7 head with its activation.  The 512 -> 512 convs of the blocks run as Winograd F(2x2, 3x3) where
+    ``lama_winograd_preferred`` says so (split precisions), otherwise as the direct kernel; ``use_graph=True`` replays the plan from a
+    captured hipGraph.  ``split_batch`` is fixed at one part (``tune_split`` decides nothing for this generator)."""
+
+    def __init__(self, input_nc, output_nc, ngf=64, n_downsampling=3, n_blocks=9, norm_layer=nn.BatchNorm2d, padding_type='reflect',
+                 conv_kind='default', activation=nn.ReLU(True), up_norm_layer=nn.BatchNorm2d, affine=None, up_activation=nn.ReLU(True),
+                 dilated_blocks_n=0, dilated_blocks_n_start=0, dilated_blocks_n_middle=0, add_out_act=True, max_features=1024,
+                 is_resblock_depthwise=False, ffc_positions=None, ffc_kwargs={}, dilation=1, second_dilation=None,
+                 dilation_block_kind='simple', multidilation_kwargs={}):
+        assert (n_blocks >= 0)
+        super().__init__()
+        if dilated_blocks_n or dilated_blocks_n_start or dilated_blocks_n_middle:
+            raise NotImplementedError('GlobalGenerator: dilated blocks are not used by the published pix2pixhd_global checkpoints')
+        if ffc_positions is not None:
+            raise NotImplementedError('GlobalGenerator: ffc_positions is not implemented')
+        if is_resblock_depthwise:
+            raise NotImplementedError('GlobalGenerator: depthwise resnet blocks are not implemented')
+        if conv_kind not in ('default', nn.Conv2d):
+            raise NotImplementedError(f'GlobalGenerator: conv_kind {conv_kind!r} (only default)')
+        if affine is not None:
+            raise NotImplementedError('GlobalGenerator: affine is not used by the shipped configs')
+        if padding_type != 'reflect':
+            raise NotImplementedError(f'GlobalGenerator: padding {padding_type!r} (only reflect)')
+        if not _is_bn(norm_layer) or not _is_bn(up_norm_layer):
+            raise NotImplementedError('GlobalGenerator: only BatchNorm2d (eval) is folded into the kernels')
+        if dilation != 1 or second_dilation not in (None, 1):
+            raise NotImplementedError('GlobalGenerator: dilation != 1 is not used by the shipped configs')
+        if not _is_relu(activation) or not _is_relu(up_activation):
+            raise NotImplementedError('GlobalGenerator: activation / up_activation must be ReLU')
+
+        model: List[nn.Module] = [ReflectionPad2d(3), Conv2dBN(input_nc, ngf, kernel_size=7, padding=0), BatchNorm2dEval(ngf),
+                                  Activation('relu')]
+        for i in range(n_downsampling):
+            mult = 2 ** i
+            cin, cout = min(max_features, ngf * mult), min(max_features, ngf * mult * 2)
+            model += [Conv2dBN(cin, cout, kernel_size=3, stride=2, padding=1), BatchNorm2dEval(cout), Activation('relu')]
+        mult = 2 ** n_downsampling
+        feats_num_bottleneck = min(max_features, ngf * mult)
+        for i in range(n_blocks):
+            model += [ResnetBlock(feats_num_bottleneck, padding_type=padding_type, activation=activation, norm_layer=norm_layer)]
+        for i in range(n_downsampling):
+            mult = 2 ** (n_downsampling - i)
+            cin, cout = min(max_features, ngf * mult), min(max_features, int(ngf * mult / 2))
+            model += [ConvTranspose2dUp(cin, cout), BatchNorm2dEval(cout), Activation('relu')]
+        model += [ReflectionPad2d(3), Conv2dOut(ngf, output_nc, kernel_size=7, padding=0)]
+        if add_out_act:                                                       # base.get_activation
+            kind = 'tanh' if add_out_act is True else add_out_act
+            if kind not in ('tanh', 'sigmoid'):
+                raise ValueError(f'Unknown activation kind {kind}')
+            model.append(Activation(kind))
+        self.model = LayerSequence(*model)
+        self.n_downsampling = n_downsampling
+        self.use_graph = False
+        # the fp16-split range watch (as FFCResNetGenerator): a forward that split an activation beyond 65504 (or a NaN) is repeated with
+        # the 3-term bf16 split and the generator stays on it; auto_fallback = False raises LamaRangeError instead
+        self.auto_fallback = True
+        self.defer_range_check = False    # True: no flag read-back per forward; the caller asks check_range() at its own synchronisation point
+        self.clone_output = True          # False: forward returns the plan's own output buffer (overwritten by the next forward of the shape)
+        self.max_plans = 4                # activation buffers (+ captured graphs) of the most recently used input shapes
+        self.split_batch = 1              # one part: no split-batch plans for this generator
+        self._assume_graph = False
+        self.split_decisions = {}
+        self._plans = collections.OrderedDict()
+        super().train(False)
+
+    # ------------------------------------------------------------------------------------------------
+    def set_precision(self, precision: int):
+        if precision == L.PREC_F16:
+            raise NotImplementedError('GlobalGenerator: fp16 activations (LAMA_PREC_F16) are not implemented; use f16x3, bf16x3 or f32')
+        return super().set_precision(precision)
+
+    def _invalidate(self):
+        super()._invalidate()
+        self._plans = collections.OrderedDict()
+
+    def tune_split(self, shape, device) -> int:
+        """Split-batch plans are not built for this generator: always one part."""
+        return 1
+
+    def _build_plan(self, shape, device) -> dict:
+        """Pre-allocate every activation buffer of an input shape and record the launch list."""
+        layers = list(self.model)
+        steps, bufs = [], {}
+        cur, cur_shape, pad_pending = 'in', tuple(int(v) for v in shape), 0
+        i, n, k = 0, len(layers), 0
+
+        def new(shp):
+            nonlocal k
+            name = f'a{k}'
+            k += 1
+            bufs[name] = torch.empty(shp, device=device, dtype=torch.float32)
+            return name
+
+        def bn_act(j):
+            bn = layers[j] if j < n and isinstance(layers[j], BatchNorm2dEval) else None
+            act = layers[j + 1] if bn is not None and j + 1 < n and isinstance(layers[j + 1], Activation) else None
+            return bn, act
+
+        while i < n:
+            lay = layers[i]
+            if isinstance(lay, ReflectionPad2d):
+                pad_pending = lay.padding
+                i += 1
+            elif isinstance(lay, Conv2dBN):
+                bn, act = bn_act(i + 1)
+                pad, mode = (pad_pending, L.PAD_REFLECT) if pad_pending else (lay.padding[0], L.PAD_ZERO)
+                shp = lay.out_shape(cur_shape, pad)
+                dst = new(shp)
+                steps.append(('conv', lay, cur, dst, bn, _ACT[act.kind] if act else L.ACT_NONE, pad, mode))
+                cur, cur_shape, pad_pending = dst, shp, 0
+                i += 1 + (bn is not None) + (act is not None)
+            elif isinstance(lay, ResnetBlock):
+                if 'st' not in bufs:
+                    if cur == 'in':                   # (a generator without a stem / downsampling: the input is not overwritten)
+                        bufs['st'] = torch.empty(cur_shape, device=device, dtype=torch.float32)
+                        steps.append(('copy', cur, 'st'))
+                    else:
+                        bufs['st'] = bufs.pop(cur)
+                        for j, s in enumerate(steps):
+                            if s[3] == cur:
+                                steps[j] = s[:3] + ('st',) + s[4:]
+                    bufs['t'] = torch.empty(cur_shape, device=device, dtype=torch.float32)
+                    cur = 'st'
+                steps.append(('res', lay))
+                i += 1
+            elif isinstance(lay, ConvTranspose2dUp):
+                bn, act = bn_act(i + 1)
+                B, _, H, W = cur_shape
+                shp = (B, lay.out_channels, 2 * H, 2 * W)
+                dst = new(shp)
+                steps.append(('up', lay, cur, dst, bn, _ACT[act.kind] if act else L.ACT_NONE))
+                cur, cur_shape = dst, shp
+                i += 1 + (bn is not None) + (act is not None)
+            elif isinstance(lay, Conv2dOut):
+                act = layers[i + 1] if i + 1 < n and isinstance(layers[i + 1], Activation) else None
+                B, _, H, W = cur_shape
+                kk, p = lay.kernel_size[0], lay.padding[0] + pad_pending
+                shp = (B, lay.out_channels, H + 2 * p - kk + 1, W + 2 * p - kk + 1)
+                dst = new(shp)
+                steps.append(('out', lay, cur, dst, pad_pending, _ACT[act.kind] if act else L.ACT_NONE))
+                cur, cur_shape, pad_pending = dst, shp, 0
+                i += 2 if act else 1
+            else:
+                raise LamaError(f'no fused plan for layer {type(lay).__name__}; run generator.model layer by layer')
+        # the 512 -> 512 convs of the blocks: Winograd where the library expects it to beat the direct kernel at this shape and every block
+        # conv has its transformed weights (one workspace serves every launch: they run one after the other on one stream)
+        ws = None
+        blocks = [s[1] for s in steps if s[0] == 'res']
+        if blocks and self._exec.winograd and self.precision in (L.PREC_F16X3, L.PREC_BF16X3):
+            B, C, H, W = bufs['st'].shape
+            lib = self._exec.lib
+            if lib.winograd_preferred(B, C, C, H, W, self.precision) and all(c.wino_ok(bn) for b in blocks for c, bn in b.convs()):
+                ws = torch.empty(lib.winograd_workspace_bytes(B, C, H, W) // 4, device=device, dtype=torch.float32)
+        return dict(steps=steps, bufs=bufs, out=cur, wino_ws=ws, graph=None, static_in=None, paths=None)
+
+    def _run_plan(self, plan, x):
+        bufs = plan['bufs']
+
+        def B(name):
+            return x if name == 'in' else bufs[name]
+
+        paths = []
+        for st in plan['steps']:
+            kind = st[0]
+            if kind == 'conv':
+                _, lay, s, d, bn, act, pad, mode = st
+                lay.run(B(s), B(d), bn, act, pad, mode)
+            elif kind == 'res':
+                paths.extend(st[1].run(bufs['st'], bufs['t'], bufs['st'], plan['wino_ws']))
+            elif kind == 'up':
+                _, lay, s, d, bn, act = st
+                lay.run(B(s), B(d), bn, act)
+            elif kind == 'out':
+                _, lay, s, d, pad, act = st
+                lay.run(B(s), B(d), pad, act)
+            else:
+                B(st[2]).copy_(B(st[1]))
+        plan['paths'] = ['winograd' if w else 'direct' for w in paths]   # per bottleneck launch, in launch order
+        return bufs[plan['out']]
+
+    @staticmethod
+    def _plan_key(shape, device):
+        return (tuple(int(v) for v in shape), _Exec._dev_key(device))
+
+    def _plan_for(self, shape, device) -> dict:
+        key = self._plan_key(shape, device)
+        plan = self._plans.get(key)
+        if plan is None:
+            while len(self._plans) >= max(1, self.max_plans):
+                self._plans.popitem(last=False)
+            plan = self._plans[key] = self._build_plan(shape, device)
+        else:
+            self._plans.move_to_end(key)
+        return plan
+
+    def drop_plan(self, shape, device) -> None:
+        """Free the activation buffers / captured graph of one input shape."""
+        self._plans.pop(self._plan_key(shape, device), None)
+
+    def conv_paths(self, shape, device) -> Optional[List[str]]:
+        """'winograd' / 'direct' for each bottleneck launch of this shape's plan, in launch order (None before its first forward)."""
+        plan = self._plans.get(self._plan_key(shape, device))
+        return None if plan is None else plan['paths']
+
+    def input_buffer(self, shape, device) -> torch.Tensor:
+        """The tensor this shape's plan reads its input from (see FFCResNetGenerator.input_buffer)."""
+        device = torch.device(device)
+        plan = self._plan_for(shape, device)
+        if plan['static_in'] is None:
+            plan['static_in'] = torch.empty(tuple(shape), device=device, dtype=torch.float32)
+        return plan['static_in']
+
+    def _capture(self, plan, device):
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):           # warm-up outside capture (packs the weights)
+            self._run_plan(plan, plan['static_in'])
+        torch.cuda.current_stream(device).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            plan['static_out'] = self._run_plan(plan, plan['static_in'])
+        plan['graph'] = g
+
+    def _forward(self, x: torch.Tensor) -> torch.Tensor:
+        plan = self._plan_for(x.shape, x.device)
+        fin = (lambda t: t.clone()) if self.clone_output else (lambda t: t)
+        if not (self.use_graph and x.is_cuda):
+            return fin(self._run_plan(plan, x))
+        own = plan['static_in'] is not None and x.data_ptr() == plan['static_in'].data_ptr()
+        if plan['graph'] is None:
+            if not own:
+                plan['static_in'] = torch.empty_like(x)
+                plan['static_in'].copy_(x)
+            self._capture(plan, x.device)
+        if not own:
+            plan['static_in'].copy_(x)
+        plan['graph'].replay()
+        return fin(plan['static_out'])
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        self._exec.check(input)
+        x = input.contiguous()
+        if x.dtype != torch.float32:
+            raise LamaError(f'GlobalGenerator: fp32 input expected, got {x.dtype}')
+        try:
+            with self._exec.range_scope(x, self.precision, deferred=self.defer_range_check):
+                return self._forward(x)
+        except LamaRangeError as e:
+            if not self.auto_fallback or self.precision != L.PREC_F16X3:
+                raise
+            warnings.warn(f'lama_amd: {e}; switching this generator to the 3-term bf16 split (PREC_BF16X3)')
+            self.set_precision(L.PREC_BF16X3)
+            return self.forward(input)
+
+    def check_range(self, device=None, reduce=None) -> bool:
+        """The other half of ``defer_range_check`` (see FFCResNetGenerator.check_range): True when every forward since the last check stayed
+        inside the fp16 split's range; otherwise the generator switches to the 3-term bf16 split (``auto_fallback``) and False is returned --
+        the caller re-runs those inputs -- or LamaRangeError is raised."""
+        bad = self._exec.range_flag_raised(device)
+        if reduce is not None:
+            bad = bool(reduce(bad))
+        if not bad:
+            return True
+        if not self.auto_fallback or self.precision != L.PREC_F16X3:
+            raise LamaRangeError(_RANGE_MSG)
+        warnings.warn(f'lama_amd: {_RANGE_MSG}; switching this generator to the 3-term bf16 split (PREC_BF16X3): re-run the inputs since the last check')
+        self.set_precision(L.PREC_BF16X3)
+        return False

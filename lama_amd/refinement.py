@@ -258,6 +258,10 @@ def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: i
     if len(ids) > 1:
         warnings.warn(f'lama_amd.refinement: gpu_ids={gpu_ids!r}: the whole model stays on the first GPU (288 GB of HBM); the others are not used')
     gen = inpainter.generator
+    if not isinstance(gen, ffc.FFCResNetGenerator):
+        # refinement.py:128 unpacks ``z1, z2 = forward_front(...)``: only an FFC front returns the (x_l, x_g) pair, so the reference cannot
+        # refine a pix2pixhd_global generator either
+        raise NotImplementedError(f'refine=True needs an ffc_resnet generator; {type(gen).__name__} has no (local, global) feature pair to refine')
     model = gen.model
     first_resblock_ind, found = 0, False
     n_resnet_blocks = 0
