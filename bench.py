@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the LaMa FFC hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): inpainted images/s at 512x512, big-lama, fp32.  One *step* = one pass of the
 hot path over one batch of synthetic input per rank: mask compose -> FFCResNetGenerator (big-lama,
@@ -11,7 +11,9 @@ N ranks = configs[3] per rank).  N > 1: one process per GPU (torch.distributed o
 sharded data-parallel (weak scaling, 8 per rank) and the only data-path collective is the gather
 (to the writer rank 0) of the u8 output images, inside the timed region.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON line with the headline (`value`,
+`ms_per_step`, `dtype`, `config`); the fields below are null in it.  `--full` runs, after the timed steps, everything that takes runs
+of its own and fills them in (the --no-* options skip single parts of it):
   roofline      -- the dominant kernel of the step (by total time): algorithmic FLOPs per launch /
                    its average launch duration, measured here with HIP events on the launch stream
                    in instrumented eager steps after the timed region (graph replay cannot be
@@ -716,6 +718,10 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--precision', default=os.environ.get('LAMA_PRECISION', 'f16x3'), choices=['f32', 'bf16x3', 'f16x3'])
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also run the measurements the headline does not need: the '
+                                                        'per-kernel / roofline steps, the host-fed, exact-fp32, fp16, batch-16, refinement, photo-size '
+                                                        'and CLI legs, the CPU baseline and the PyTorch-ROCm eager comparator (the --no-* options skip '
+                                                        'single ones)')
     ap.add_argument('--no-f32-leg', action='store_true', help='skip the extra exact-fp32 timing leg')
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--split-batch', type=int, default=0, choices=[0, 1, 2, 4], help='parts of the batch as parallel branches of the hipGraph: 0 = the generator\'s rule, verified by timing once per shape (config.split_check); 1 / 2 / 4 force it')
@@ -760,7 +766,7 @@ def main():
     precision = L.PREC_NAMES[args.precision]
 
     lib = L.use_library(os.path.abspath(args.lib)) if args.lib else L.get_lib()      # raises if the HIP library is missing: no fallback
-    timer = KernelTimer(lib)
+    timer = KernelTimer(lib)        # installed in plain runs too: the timed steps go through the same launch wrappers with or without --full
     model = build_model(device, precision)
     model.generator.use_graph = not args.no_graph
     model.generator.overlap_streams = bool(int(os.environ.get('LAMA_OVERLAP_STREAMS', '1')))   # the generator's default; 0 = serial launch order (A/B runs)
@@ -796,7 +802,7 @@ def main():
     # the same K steps fed from / drained to pinned HOST buffers (SURVEY.md 8(d) "includes H2D/D2H"): u8 image + mask in, u8 out,
     # copies on the compute stream (serial, not overlapped).  Reported beside `value`, never as `value`.
     dt_pcie = dt_piped = dt_piped_graph = dt_replay = dt_host = hf_mode = None
-    if world == 1 and not args.no_host_fed_leg:
+    if args.full and world == 1 and not args.no_host_fed_leg:
         h_img, h_mask = loop.img_u8.cpu().pin_memory(), loop.mask_u8.cpu().pin_memory()      # (round 6) what is on disk: u8 HWC image + u8 mask, 8.4 MB per step
         h_u8 = torch.empty(BATCH, RES, RES, 3, dtype=torch.uint8).pin_memory()
         d_img, d_mask = torch.empty_like(loop.img_u8), torch.empty_like(loop.mask_u8)
@@ -856,7 +862,7 @@ def main():
     # instrumented eager steps: per-kernel durations with HIP events on the launch stream
     roof = roof_ffc = None
     kern, kern_seq = {}, {}
-    if rank == 0:
+    if args.full and rank == 0:
         model.generator.use_graph = False
         model.generator.overlap_streams = False     # per-kernel events need every launch on the current stream
         from lama_amd import ffc as _ffc2
@@ -1006,7 +1012,7 @@ def main():
 
     # extra leg (rank 0, N = 1): the same step on the exact-fp32 MFMA path, for reference beside the default bf16x3 split
     f32_leg = None
-    if rank == 0 and world == 1 and precision != L.PREC_F32 and not args.no_f32_leg:
+    if args.full and rank == 0 and world == 1 and precision != L.PREC_F32 and not args.no_f32_leg:
         model.generator.set_precision(L.PREC_F32)
         model.generator.use_graph = not args.no_graph
         for _ in range(2):
@@ -1025,7 +1031,7 @@ def main():
     # extra leg (rank 0, N = 1): BASELINE configs[2] -- big-lama 1024x1024 batch=4 "fp16" (PREC_F16: fp16 activations in HBM, fp16
     # weights, one MFMA product per MAC), beside the same shape on the fp32-accurate default.  A separate config, never the headline.
     c3_leg = None
-    if rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
+    if args.full and rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
         try:
             c3_leg = configs2_leg(model, device, lib, args)
         except Exception as e:      # noqa: BLE001
@@ -1035,7 +1041,7 @@ def main():
     # extra leg (rank 0, N = 1): the same network with SIXTEEN images per step (two batches of 8 in flight: four parts of four images as parallel
     # branches of the graph).  Not BASELINE's batch (8 per GPU) and never `value`: it shows what the chip does once the parts oversubscribe it
     b16_leg = None
-    if rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
+    if args.full and rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
         try:
             img16, mask16 = torch.cat([img, img.flip(0)], 0), torch.cat([mask, mask.flip(0)], 0)
             loop16 = StepLoop(model, lib, device, img16, mask16)
@@ -1052,7 +1058,7 @@ def main():
 
     # extra leg (rank 0, N = 1): BASELINE configs[4] -- refinement of one 2048x2048 image (px_budget 4194304, 15 iterations, 3 scales)
     c5_leg = None
-    if rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
+    if args.full and rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
         try:
             c5_leg = configs4_refine_leg(model, device)
         except Exception as e:      # noqa: BLE001
@@ -1062,7 +1068,7 @@ def main():
 
     # extra legs (rank 0, N = 1), round 6: the default refinement budget, photo-sized inputs, the CLI end to end.  Never `value`.
     c5d_leg = ph_leg = cli_leg = None
-    if rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
+    if args.full and rank == 0 and world == 1 and not args.no_f32_leg and BATCH == 8 and RES == 512:
         for name, fn in (('c5d', lambda: configs4_refine_leg(model, device, px_budget=1800000)), ('photo', lambda: photo_leg(model, device, lib)),
                          ('cli', lambda: predict_cli_leg(model))):
             if (name == 'cli' and args.no_cli_leg) or (name == 'photo' and args.no_photo_leg):
@@ -1082,11 +1088,11 @@ def main():
             model.generator._plans.clear()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(model)
 
     eager = None
-    if rank == 0 and world == 1 and not args.no_eager_leg and BATCH == 8 and RES == 512:
+    if args.full and rank == 0 and world == 1 and not args.no_eager_leg and BATCH == 8 and RES == 512:
         import subprocess
         try:
             torch.cuda.empty_cache()
@@ -1110,7 +1116,7 @@ def main():
                        'global_batch': world * BATCH, 'resolution': RES, 'parallelism': f'dp{world}',
                        'hip_graph': not args.no_graph, 'precision': args.precision,
                        'split_batch': f'{nsplit} parts of {BATCH // nsplit} images as parallel branches of the one hipGraph (generator.split_batch)' if nsplit > 1 else 1,
-                       'split_check': split_check},
+                       'split_check': split_check, 'full': args.full},
             'roofline': roof, 'roofline_ffc': roof_ffc, 'cpu_baseline': cpu, 'exact_f32_leg': f32_leg,
             'pytorch_rocm_eager': eager, 'configs2_fp16_leg': c3_leg, 'configs4_refine_leg': c5_leg, 'configs4_refine_default_leg': c5d_leg, 'photo_leg': ph_leg, 'predict_cli_leg': cli_leg, 'batch16_leg': b16_leg,
             'value_host_fed': None if dt_replay is None else dict(
@@ -1136,7 +1142,7 @@ def main():
                     value=round(BATCH * args.steps / dt_piped_graph, 3), ms_per_step=round(dt_piped_graph / args.steps * 1e3, 3),
                     note='HostFedStep(mode=graph): the two copies and the compute as parallel branches of ONE captured hipGraph per step (round 5) -- '
                          'in line with the kernels (= serial) when the compute is one kernel chain, overlapped when the batch runs in parallel parts')),
-            'kernels_us': {k: round(v['avg_us'], 1) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]['total_us'])},
+            'kernels_us': {k: round(v['avg_us'], 1) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]['total_us'])} if kern else None,
             'kernels_us_in_sequence': {k: round(v['avg_us'], 1) for k, v in sorted(kern_seq.items(), key=lambda kv: -kv[1]['total_us'])} if rank == 0 and kern_seq else None,
         }
         print(json.dumps(line), flush=True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """profiles/<tag>_pmc.json (what bench.py's `traffic` fields replay) from the IN-PIPELINE counter passes of tools/session.sh pmcbench:
-rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (one counter per run, --kernel-trace only) over `python bench.py --steps 4 --warmup 1`, averaged per
+rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (one counter per run, --kernel-trace only) over `python bench.py --full --steps 4 --warmup 1`, averaged per
 (kernel, grid) by tools/pmc_summary.py.  traffic = (2 x FETCH_SIZE + WRITE_SIZE) KiB: on gfx950 FETCH_SIZE tallies 128-byte requests at 64 bytes
 (MI355X_MICROARCH.md, HBM section).  The launch of every key is the launch bench.py times under that key (the global-branch launch WITH the fused
 conv1 of the next layer is its own key).

@@ -7,7 +7,7 @@
 #   tests[:<pytest -k expr>]   pytest -m gpu (optionally -k expr)                          -> pytest_gpu.log
 #   testsall                   pytest -m gpu without -x (every failure listed)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:<extra flags>]      python bench.py <flags>                                     -> bench.json (+ one-line digest)
+#   bench[:<extra flags>]      python bench.py --full <flags>                              -> bench.json (+ one-line digest)
 #   quick                      bench without the cpu / f32 / eager / configs legs          -> bench_quick.json
 #   stats                      rocprofv3 --kernel-trace --stats of the quick bench         -> kernel_stats.csv, timeline.txt
 #   overlap                    rocprofv3 kernel trace of tools/split_trace.py: which kernels ran side by side (one-part vs split plan) -> overlap_summary.txt
@@ -27,7 +27,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
-QUICK="--steps 20 --warmup 3 --no-cpu-baseline --no-f32-leg --no-eager-leg"
+QUICK="--full --steps 20 --warmup 3 --no-cpu-baseline --no-f32-leg --no-eager-leg"
 digest() { python - "$1" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -48,13 +48,13 @@ for STEP in "$@"; do
             tail -5 $O/pytest_gpu.log | tee -a $O/summary.txt ;;
     testsall) timeout 1800 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; grep -E "^(FAILED|ERROR)" $O/pytest_gpu.log | head -40 | tee -a $O/summary.txt; tail -3 $O/pytest_gpu.log | tee -a $O/summary.txt ;;
     smoke)  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $O/summary.txt ;;
-    bench)  timeout 1200 python bench.py $ARG > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; digest $O/bench.json | tee -a $O/summary.txt ;;
+    bench)  timeout 1200 python bench.py --full $ARG > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err; digest $O/bench.json | tee -a $O/summary.txt ;;
     quick)  timeout 400 python bench.py $QUICK > $O/bench_quick.json 2> $O/bench_quick.err; tail -c 300 $O/bench_quick.err; digest $O/bench_quick.json | tee -a $O/summary.txt ;;
     stats)  # (round 6: --split-batch 1 --no-host-fed-leg: every launch in the trace is a whole-batch launch of the ONE-part plan: 2 warm-up + 10 timed graph replays,
             #  then 2 x (1 warm-up + 3 instrumented) eager steps = 20 steps, i.e. 35 x 20 = 700 calls of the fused global launch)
             # rocprofv3's kernel trace SERIALISES the queues a split plan runs on (profiles/r05_overlap_under_rocprof.txt: 33 ms per replay instead of
             # 9.4): the generator's own check (verify_split) sees that and keeps the one-part plan -- the same kernels over the whole batch
-            (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof -o bench -- python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-f32-leg --no-eager-leg --no-host-fed-leg --split-batch 1 > $ROOT/$O/prof_bench.log 2>&1)
+            (cd "$TMPDIR" && timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof -o bench -- python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-f32-leg --no-eager-leg --no-host-fed-leg --split-batch 1 > $ROOT/$O/prof_bench.log 2>&1)
             grep -o '"value": [0-9.]*, "unit": "images/s", "n_gpus"' $O/prof_bench.log | head -1 | tee -a $O/summary.txt; grep -o '"ms_per_step": [0-9.]*' $O/prof_bench.log | head -1 | tee -a $O/summary.txt; grep -o '"split_batch": [^}]*}' $O/prof_bench.log | head -1 | tee -a $O/summary.txt
             for db in $(find $O/prof -name '*.db' | head -1); do python tools/rocpd_summary.py $db $O/kernel_stats.csv; python tools/timeline.py $db $O/timeline.txt 0; done
             rm -rf $O/prof; head -16 $O/kernel_stats.csv | cut -c1-170 | tee -a $O/summary.txt ;;
@@ -67,13 +67,13 @@ for STEP in "$@"; do
             rm -rf $O/prof_split; tail -2 $O/prof_split.log | tee -a $O/summary.txt ;;
     pmc)    bash tools/pmc_session.sh $TAG/pmc_$(echo $ARG | tr ' ' '_') "f16x3 $ARG" "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT" 2>&1 | tail -40 | tee -a $O/summary.txt ;;
     pmcbench) for CNT in FETCH_SIZE WRITE_SIZE; do
-              (cd /tmp && timeout 600 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $ROOT/$O/pmcb_$CNT -o pmc -- python $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-f32-leg --no-eager-leg --no-host-fed-leg --split-batch 1 > $ROOT/$O/pmcb_$CNT.log 2>&1)
+              (cd "$TMPDIR" && timeout 600 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $ROOT/$O/pmcb_$CNT -o pmc -- python $ROOT/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-f32-leg --no-eager-leg --no-host-fed-leg --split-batch 1 > $ROOT/$O/pmcb_$CNT.log 2>&1)
               f=$(find $O/pmcb_$CNT -name '*counter_collection.csv' | head -1); [ -n "$f" ] && python tools/pmc_summary.py $f > $O/pmc_bench_$CNT.txt && grep -E "conv_wr_kernel|wino_|gemm1x1_wk|fft2_ip64|convt2|head7|stem7" $O/pmc_bench_$CNT.txt | cut -c1-60,118-200 | tee -a $O/summary.txt; rm -rf $O/pmcb_$CNT; done
               python tools/pmc_bench_to_json.py $O/pmc.json $O/pmc_bench_FETCH_SIZE.txt $O/pmc_bench_WRITE_SIZE.txt | tee -a $O/summary.txt ;;
     mfmabench) # MFMA utilisation IN the pipeline: SQ_VALU_MFMA_BUSY_CYCLES (cycles, summed over the SIMDs: 32 per v_mfma_f32_32x32x16) and GRBM_GUI_ACTIVE
               # (clock cycles of the launch) in passes of their own over the one-part quick bench; tools/mfma_util.py turns them into busy fraction + effective clock
               for CNT in SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES; do
-              (cd /tmp && timeout 600 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $ROOT/$O/pmcb_$CNT -o pmc -- python $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-f32-leg --no-eager-leg --no-host-fed-leg --split-batch 1 > $ROOT/$O/pmcb_$CNT.log 2>&1)
+              (cd "$TMPDIR" && timeout 600 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $ROOT/$O/pmcb_$CNT -o pmc -- python $ROOT/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-f32-leg --no-eager-leg --no-host-fed-leg --split-batch 1 > $ROOT/$O/pmcb_$CNT.log 2>&1)
               f=$(find $O/pmcb_$CNT -name '*counter_collection.csv' | head -1); [ -n "$f" ] && python tools/pmc_summary.py $f > $O/pmc_bench_$CNT.txt; rm -rf $O/pmcb_$CNT; done
               python tools/mfma_util.py $O/pmc_bench_SQ_VALU_MFMA_BUSY_CYCLES.txt $O/pmc_bench_GRBM_GUI_ACTIVE.txt $O/kernel_stats.csv | tee $O/mfma_util.txt | tee -a $O/summary.txt ;;
     shapes) for cfg in "4 1024" "4 256" "1 512" "1 2048"; do set -- $cfg
