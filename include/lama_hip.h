@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LAMA_HIP_VERSION 110
+#define LAMA_HIP_VERSION 111
 
 #define LAMA_OK 0
 #define LAMA_ERR_BAD_ARG (-1)
@@ -302,6 +302,15 @@ int lama_l1_masked_fwd(void* stream, const lama_tensor* pred, const lama_tensor*
                        int32_t select_ge, double* accum, int32_t batch);
 int lama_l1_masked_bwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* mask, float thr,
                        int32_t select_ge, float scale, int32_t accumulate, const lama_tensor* g, int32_t batch);
+/* (v111) the same terms PER IMAGE (refining a batch of images as separate optimisations in one launch chain):
+ *   fwd: accum[2 b] += sum |pred - target|, accum[2 b + 1] += count over image b only   (accum: [batch][2] device doubles, zeroed by the caller)
+ *   bwd: g_b = (accumulate ? g_b : 0) + s_b * sign(pred - target) on the selected elements of image b, with s_b = (float)(1.0 / n_b) from the
+ *        count n_b = accum[2 b + 1] that the fwd left (0 for an empty selection): at batch 1 bit-identical to lama_l1_masked_bwd with
+ *        scale = (float)(1.0 / n).  batch <= 65535. */
+int lama_l1_masked_per_image_fwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* mask, float thr,
+                                 int32_t select_ge, double* accum, int32_t batch);
+int lama_l1_masked_per_image_bwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* mask, float thr,
+                                 int32_t select_ge, const double* accum, int32_t accumulate, const lama_tensor* g, int32_t batch);
 /* one torch.optim.Adam step (refinement.py:134,165: betas, eps as given, no weight decay / amsgrad) on a flat fp32 buffer;
  * step = 1, 2, ... */
 int lama_adam_step(void* stream, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,

@@ -19,7 +19,7 @@ CONV_COOPERATIVE = 1
 CONV_DEFER_OUT = 2          # lama_winograd_conv3x3_fwd: the GEMM launch only (include/lama_hip.h)
 CONV_SIBLINGS_SHIFT = 8     # (v109) bits 8..10: log2 of the number of sibling launches that share the chip with this one
 DT_F32, DT_F16 = 0, 1
-ABI_VERSION = 110      # LAMA_HIP_VERSION of include/lama_hip.h
+ABI_VERSION = 111      # LAMA_HIP_VERSION of include/lama_hip.h
 PREC_NAMES = {'f32': PREC_F32, 'bf16x3': PREC_BF16X3, 'f16x3': PREC_F16X3, 'f16': PREC_F16}
 
 _DEFAULT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'liblama_hip.so')
@@ -138,6 +138,8 @@ class LamaLib:
                            ('lama_erode_fwd', [vp, T, vp, i32, i32, f32, T, i32]),
                            ('lama_l1_masked_fwd', [vp, T, T, T, f32, i32, vp, i32]),
                            ('lama_l1_masked_bwd', [vp, T, T, T, f32, i32, f32, i32, T, i32]),
+                           ('lama_l1_masked_per_image_fwd', [vp, T, T, T, f32, i32, vp, i32]),
+                           ('lama_l1_masked_per_image_bwd', [vp, T, T, T, f32, i32, vp, i32, T, i32]),
                            ('lama_adam_step', [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, i32])):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = C.c_int, args
@@ -452,6 +454,20 @@ class LamaLib:
                       g: Tensor4, batch: int, stream: int = 0):
         self.check(self._l.lama_l1_masked_bwd(stream, C.byref(pred), C.byref(target), C.byref(mask), thr, int(select_ge), scale,
                                               int(accumulate), C.byref(g), batch), 'lama_l1_masked_bwd')
+
+    def l1_masked_per_image(self, pred: Tensor4, target: Tensor4, mask: Tensor4, thr: float, select_ge: bool, accum: torch.Tensor, batch: int,
+                            stream: int = 0):
+        """(v111) accum [batch, 2] float64 (zeroed by the caller) += per-image (sum |pred - target|, count)."""
+        assert accum.dtype == torch.float64 and accum.is_contiguous() and accum.numel() >= 2 * batch
+        self.check(self._l.lama_l1_masked_per_image_fwd(stream, C.byref(pred), C.byref(target), C.byref(mask), thr, int(select_ge),
+                                                        accum.data_ptr(), batch), 'lama_l1_masked_per_image_fwd')
+
+    def l1_masked_per_image_bwd(self, pred: Tensor4, target: Tensor4, mask: Tensor4, thr: float, select_ge: bool, accum: torch.Tensor,
+                                accumulate: bool, g: Tensor4, batch: int, stream: int = 0):
+        """(v111) g (+)= sign(pred - target) / n_b per image, n_b = accum[b, 1] as l1_masked_per_image left it."""
+        assert accum.dtype == torch.float64 and accum.is_contiguous() and accum.numel() >= 2 * batch
+        self.check(self._l.lama_l1_masked_per_image_bwd(stream, C.byref(pred), C.byref(target), C.byref(mask), thr, int(select_ge),
+                                                        accum.data_ptr(), int(accumulate), C.byref(g), batch), 'lama_l1_masked_per_image_bwd')
 
     def adam_step(self, param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, lr: float, step: int,
                   beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, stream: int = 0):

@@ -810,6 +810,90 @@ extern "C" int lama_l1_masked_bwd(void* stream, const lama_tensor* pred, const l
 }
 
 // ------------------------------------------------------------------------------------------------
+// (v111) the same terms per image, for refining several images in one batched optimisation: grid.y = image, so that every
+// workgroup reduces elements of ONE image and adds them to that image's pair accum[2 b], accum[2 b + 1] only.  The bwd takes
+// its per-image scale from the counts the fwd left: (float)(1.0 / n_b), the rounding the host applies for lama_l1_masked_bwd,
+// 0 for an empty selection -- no host read-back per iteration.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(LAMA_NTHREADS) void l1_masked_per_image_fwd_kernel(L1Params p) {
+    const long long per = (long long)p.C * p.hw;
+    const int b = blockIdx.y;
+    const float* pred = p.pred + b * p.pred_bs;
+    const float* tgt = p.tgt + b * p.tgt_bs;
+    const float* mask = p.mask + b * p.mask_bs;
+    double s = 0.0, n = 0.0;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < per; r += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(r / p.hw);
+        const long long px = r - (long long)c * p.hw;
+        const float m = mask[(p.mask_c == 1 ? 0 : c) * p.hw + px];
+        const bool sel = p.select_ge ? (m >= p.thr) : (m < p.thr);
+        if (sel) { s += (double)fabsf(pred[r] - tgt[r]); n += 1.0; }
+    }
+    double* red = reinterpret_cast<double*>(lama_smem);
+    red[threadIdx.x] = s;
+    red[LAMA_NTHREADS + threadIdx.x] = n;
+    __syncthreads();
+    for (int st = LAMA_NTHREADS / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) { red[threadIdx.x] += red[threadIdx.x + st]; red[LAMA_NTHREADS + threadIdx.x] += red[LAMA_NTHREADS + threadIdx.x + st]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { atomicAdd(&p.accum[2 * b], red[0]); atomicAdd(&p.accum[2 * b + 1], red[LAMA_NTHREADS]); }
+}
+
+__global__ __launch_bounds__(LAMA_NTHREADS) void l1_masked_per_image_bwd_kernel(L1Params p) {
+    const long long per = (long long)p.C * p.hw;
+    const int b = blockIdx.y;
+    const double n = p.accum[2 * b + 1];
+    const float scale = n != 0.0 ? (float)(1.0 / n) : 0.0f;
+    const float* pred = p.pred + b * p.pred_bs;
+    const float* tgt = p.tgt + b * p.tgt_bs;
+    const float* mask = p.mask + b * p.mask_bs;
+    float* gb = p.g + b * p.g_bs;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < per; r += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(r / p.hw);
+        const long long px = r - (long long)c * p.hw;
+        const float m = mask[(p.mask_c == 1 ? 0 : c) * p.hw + px];
+        const bool sel = p.select_ge ? (m >= p.thr) : (m < p.thr);
+        float g = 0.0f;
+        if (sel) {
+            const float d = pred[r] - tgt[r];
+            g = d > 0.0f ? scale : (d < 0.0f ? -scale : 0.0f);
+        }
+        gb[r] = p.accumulate ? gb[r] + g : g;
+    }
+}
+
+extern "C" int lama_l1_masked_per_image_fwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* mask, float thr,
+                                            int32_t select_ge, double* accum, int32_t batch) {
+    L1Params p;
+    int rc = rf_l1_fill(p, pred, target, mask, thr, select_ge, batch);
+    if (rc) return rc;
+    if (!accum || batch > 65535) return LAMA_ERR_BAD_ARG;
+    p.accum = accum;
+    int gx = rf_grid((long long)p.C * p.hw);
+    if (gx > 512) gx = 512;
+    hipLaunchKernelGGL(l1_masked_per_image_fwd_kernel, dim3(gx, batch), dim3(LAMA_NTHREADS), 2 * LAMA_NTHREADS * sizeof(double), (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+extern "C" int lama_l1_masked_per_image_bwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* mask, float thr,
+                                            int32_t select_ge, const double* accum, int32_t accumulate, const lama_tensor* g, int32_t batch) {
+    L1Params p;
+    int rc = rf_l1_fill(p, pred, target, mask, thr, select_ge, batch);
+    if (rc) return rc;
+    if (!accum || batch > 65535 || !rf_ok(g) || !rf_same(g, pred)) return LAMA_ERR_BAD_ARG;
+    p.accum = const_cast<double*>(accum);
+    p.g = (float*)g->ptr; p.g_bs = g->batch_stride;
+    p.accumulate = accumulate;
+    int gx = rf_grid((long long)p.C * p.hw);
+    if (gx > 4096 / batch) gx = 4096 / batch > 0 ? 4096 / batch : 1;
+    hipLaunchKernelGGL(l1_masked_per_image_bwd_kernel, dim3(gx, batch), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // torch.optim.Adam([z1, z2], lr) step t (betas 0.9 / 0.999, eps 1e-8, no weight decay, no amsgrad; refinement.py:134,165) on a flat buffer
 // ------------------------------------------------------------------------------------------------
 struct AdamParams {

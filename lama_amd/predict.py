@@ -45,9 +45,10 @@ DEFAULTS = {'model.checkpoint': 'best.ckpt', 'dataset.img_suffix': '.png', 'data
 # keys of configs/prediction/default.yaml this driver honours; anything else is rejected instead of silently ignored
 KNOWN_KEYS = set(DEFAULTS) | {'model.path', 'indir', 'outdir', 'device', 'dataset.kind', 'dataset.scale_factor', 'refine', 'profile',
                               'refiner.gpu_ids', 'refiner.modulo', 'refiner.n_iters', 'refiner.lr', 'refiner.min_side',
-                              'refiner.max_scales', 'refiner.px_budget'}
+                              'refiner.max_scales', 'refiner.px_budget', 'refiner.batch_size'}
 REFINER_DEFAULTS = {'refiner.gpu_ids': '0,', 'refiner.modulo': 8, 'refiner.n_iters': 15, 'refiner.lr': 0.002, 'refiner.min_side': 512,
-                    'refiner.max_scales': 3, 'refiner.px_budget': 1800000}     # configs/prediction/default.yaml:16-24
+                    'refiner.max_scales': 3, 'refiner.px_budget': 1800000,     # configs/prediction/default.yaml:16-24
+                    'refiner.batch_size': 1}     # extension: images of one size refined as one batched optimisation (refine_predict_batch)
 
 
 # option types: paths, suffixes and names stay strings whatever they look like (indir=2024, model.checkpoint=100 are a directory and
@@ -56,7 +57,7 @@ STRING_KEYS = {'model.path', 'model.checkpoint', 'indir', 'outdir', 'device', 'd
                'precision', 'refiner.gpu_ids'}
 BOOL_KEYS = {'refine', 'profile'}
 INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
-            'refiner.px_budget'}
+            'refiner.px_budget', 'refiner.batch_size'}
 FLOAT_KEYS = {'refiner.lr', 'dataset.scale_factor'}
 
 
@@ -101,6 +102,8 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
         raise SystemExit(f"out_key={cfg['out_key']!r}: the predict_only forward (trainers/default.py:56-71) produces 'inpainted' and 'predicted_image'")
     if cfg.get('dataset.scale_factor') is not None and not cfg['dataset.scale_factor'] > 0:
         raise SystemExit(f"dataset.scale_factor={cfg['dataset.scale_factor']!r}: a positive factor (evaluation/data.py:74-77)")
+    if cfg['refiner.batch_size'] < 1:
+        raise SystemExit(f"refiner.batch_size={cfg['refiner.batch_size']!r}: at least 1 image per refinement")
     return cfg
 
 
@@ -931,6 +934,8 @@ def predict_refine(model, items: List[Tuple[str, str]], indir: str, outdir: str,
     (no collective on this path)."""
     from .refinement import refine_predict
     pad_mod = int(cfg['dataset.pad_out_to_modulo'])
+    if int(cfg.get('refiner.batch_size', 1)) > 1:
+        return _predict_refine_batched(model, items, indir, outdir, cfg, device=device, rank=rank, world=world)
     pool = ThreadPoolExecutor(4)
     futures, written = [], 0
     for i in range(rank, len(items), world):
@@ -951,6 +956,66 @@ def predict_refine(model, items: List[Tuple[str, str]], indir: str, outdir: str,
     for f in futures:
         f.result()
     pool.shutdown()
+    return written
+
+
+def _predict_refine_batched(model, items: List[Tuple[str, str]], indir: str, outdir: str, cfg: dict, *, device='cuda', rank: int = 0,
+                            world: int = 1) -> int:
+    """``refine=True refiner.batch_size=N`` (N > 1; extension): the rank's share of the items (the same as predict_refine's) grouped by
+    their size after ``dataset.scale_factor``, each group refined in chunks of at most N images through refine_predict_batch -- one
+    batched optimisation per chunk, every image its own loss and Adam state.  The next chunk's PNGs load on the thread pool while the
+    current chunk refines; the files written are those of predict_refine."""
+    from PIL import Image
+    from .refinement import refine_predict_batch
+    pad_mod = int(cfg['dataset.pad_out_to_modulo'])
+    n_max = int(cfg['refiner.batch_size'])
+    scale_factor = cfg.get('dataset.scale_factor')
+    mine = [items[i] for i in range(rank, len(items), world)]
+    t0 = time.perf_counter()
+
+    def header_size(item):
+        with Image.open(item[1]) as im:
+            w, h = im.size
+        return (h, w) if scale_factor is None else scaled_size(h, w, scale_factor)
+
+    groups: Dict[Tuple[int, int], List[Tuple[str, str]]] = {}
+    for item in mine:
+        groups.setdefault(header_size(item), []).append(item)
+    chunks = [g[i:i + n_max] for g in groups.values() for i in range(0, len(g), n_max)]
+    pool = ThreadPoolExecutor(4)
+
+    def load(chunk):
+        return [load_item(m, im, pad_mod, scale_factor) for m, im in chunk]
+
+    futures, written = [], 0
+    try:
+        nxt = pool.submit(load, chunks[0]) if chunks else None
+        for ci, chunk in enumerate(chunks):
+            loaded = nxt.result()
+            nxt = pool.submit(load, chunks[ci + 1]) if ci + 1 < len(chunks) else None
+            hw = {tuple(hw_) for _, _, hw_ in loaded}
+            if len(hw) != 1:
+                raise L.LamaError(f'refiner.batch_size: the images of one chunk decode to different sizes {sorted(hw)}')
+            h, w = hw.pop()
+            B = len(chunk)
+            batch = dict(image=torch.from_numpy(np.stack([a for a, _, _ in loaded])).to(device),
+                         mask=torch.from_numpy(np.stack([m for _, m, _ in loaded])).to(device),
+                         unpad_to_size=[torch.tensor([h] * B), torch.tensor([w] * B)])
+            # the RAW grayscale masks, as in predict_refine (bin/predict.py:75-81)
+            cur_res = refine_predict_batch(batch, model, gpu_ids=str(cfg['refiner.gpu_ids']), modulo=int(cfg['refiner.modulo']),
+                                           n_iters=int(cfg['refiner.n_iters']), lr=float(cfg['refiner.lr']), min_side=int(cfg['refiner.min_side']),
+                                           max_scales=int(cfg['refiner.max_scales']), px_budget=int(cfg['refiner.px_budget']))
+            for b, (mask_path, _) in enumerate(chunk):
+                u8 = np.clip(cur_res[b].permute(1, 2, 0).numpy() * 255, 0, 255).astype('uint8')
+                rel = os.path.splitext(mask_path[len(indir):].lstrip(os.sep))[0] + cfg['out_ext']
+                futures.append(pool.submit(_write_png, os.path.join(outdir, rel), u8))
+                written += 1
+        for f in futures:
+            f.result()
+    finally:
+        pool.shutdown()
+    dt = time.perf_counter() - t0
+    print(f'rank {rank}: refined {written} images in {dt:.3f} s ({len(chunks)} batched optimisations of up to {n_max} images)')
     return written
 
 

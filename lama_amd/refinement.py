@@ -127,6 +127,17 @@ def _l1_loss(pred, pred_downscaled, ref, mask, mask_downscaled, image, on_pred: 
     return loss
 
 
+def _l1_loss_per_image(pred, pred_downscaled, ref, mask, mask_downscaled, image) -> List[float]:
+    """_l1_loss (on_pred=True) of every image of a batch on its own: [loss of image 0, loss of image 1, ...] (lama_l1_masked_per_image_fwd)."""
+    lib = _lib_of(pred)
+    B = pred.shape[0]
+    acc = torch.zeros(2, B, 2, dtype=torch.float64, device=pred.device)
+    lib.l1_masked_per_image(L.view(_c(pred)), L.view(_c(image)), L.view(_c(mask)), 1e-8, False, acc[0], B, _stream(pred))
+    lib.l1_masked_per_image(L.view(_c(pred_downscaled)), L.view(_c(ref)), L.view(_c(mask_downscaled)), 1e-8, True, acc[1], B, _stream(pred))
+    a = acc.tolist()
+    return [sum(s / n if n else 0.0 for s, n in (a[0][b], a[1][b])) for b in range(B)]
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # refinement.py:86-174
 # ----------------------------------------------------------------------------------------------------------------
@@ -138,10 +149,13 @@ def _state_buffer(z) -> torch.Tensor:
 
 
 def _infer(image: torch.Tensor, mask: torch.Tensor, forward_front, forward_rears, ref_lower_res: Optional[torch.Tensor],
-           orig_shape: tuple, devices: list, scale_ind: int, n_iters: int = 15, lr: float = 0.002, trace: Optional[dict] = None):
+           orig_shape: tuple, devices: list, scale_ind: int, n_iters: int = 15, lr: float = 0.002, trace: Optional[dict] = None,
+           per_image: bool = False):
     """refinement.py:86-174.  ``forward_front``: generator.model[0:first_resblock]; ``forward_rears``: a list whose entries are
     RearPass objects (lama_amd/backward.py) -- refine_predict builds ONE covering generator.model[first_resblock:].
-    ``trace`` (tests): receives per-iteration losses, the first prediction and the first gradient of z."""
+    ``trace`` (tests): receives per-iteration losses, the first prediction and the first gradient of z.
+    ``per_image`` (refine_predict_batch): every image of the batch is its own optimisation -- each L1 term is normalised by that
+    image's own count (lama_l1_masked_per_image_*), and the trace's loss entry of an iteration is the list of the B per-image losses."""
     if len(forward_rears) != 1 or not isinstance(forward_rears[0], RearPass):
         raise LamaError('_infer: forward_rears must be [RearPass] (single device; see the module docstring)')
     rear: RearPass = forward_rears[0]
@@ -165,8 +179,14 @@ def _infer(image: torch.Tensor, mask: torch.Tensor, forward_front, forward_rears
         mask_down = _erode_mask(mask_down, ekernel=ekernel)
         if tuple(mask_down.shape[2:]) != tuple(ref.shape[2:]):
             raise LamaError(f'_infer: reference scale {tuple(ref.shape[2:])} != half of {(oh, ow)}')
-        _, n1 = _masked_l1_terms(image, image, mask, False)
-        _, n2 = _masked_l1_terms(ref, ref, mask_down, True)
+        if per_image:
+            # per-image selection counts, constant over the iterations: the (sum, count) pairs of pred == target
+            cnt = torch.zeros(2, B, 2, dtype=torch.float64, device=image.device)
+            lib.l1_masked_per_image(L.view(image), L.view(image), L.view(mask), 1e-8, False, cnt[0], B, st)
+            lib.l1_masked_per_image(L.view(ref), L.view(ref), L.view(mask_down), 1e-8, True, cnt[1], B, st)
+        else:
+            _, n1 = _masked_l1_terms(image, image, mask, False)
+            _, n2 = _masked_l1_terms(ref, ref, mask_down, True)
         blur = torch.empty(B, 3, oh, ow, device=image.device)
         pdown = torch.empty_like(ref)
         g_pred = torch.empty(B, 3, H, W, device=image.device)
@@ -178,10 +198,15 @@ def _infer(image: torch.Tensor, mask: torch.Tensor, forward_front, forward_rears
         lib.gauss5(L.view(pred), L.view(blur), B, st)                                     # refinement.py:149: _pyrdown(pred[:,:,:oh,:ow])
         lib.bilinear(L.view(blur), L.view(pdown), B, st)
         if trace is not None:
-            trace.setdefault('loss', []).append(_l1_loss(pred, pdown, ref, mask, mask_down, image, on_pred=True))
+            trace.setdefault('loss', []).append(_l1_loss_per_image(pred, pdown, ref, mask, mask_down, image) if per_image
+                                                else _l1_loss(pred, pdown, ref, mask, mask_down, image, on_pred=True))
         if idi < n_iters - 1:
-            lib.l1_masked_bwd(L.view(pred), L.view(image), L.view(mask), 1e-8, False, (1.0 / n1) if n1 else 0.0, False, L.view(g_pred), B, st)
-            lib.l1_masked_bwd(L.view(pdown), L.view(ref), L.view(mask_down), 1e-8, True, (1.0 / n2) if n2 else 0.0, False, L.view(g_pdown), B, st)
+            if per_image:
+                lib.l1_masked_per_image_bwd(L.view(pred), L.view(image), L.view(mask), 1e-8, False, cnt[0], False, L.view(g_pred), B, st)
+                lib.l1_masked_per_image_bwd(L.view(pdown), L.view(ref), L.view(mask_down), 1e-8, True, cnt[1], False, L.view(g_pdown), B, st)
+            else:
+                lib.l1_masked_bwd(L.view(pred), L.view(image), L.view(mask), 1e-8, False, (1.0 / n1) if n1 else 0.0, False, L.view(g_pred), B, st)
+                lib.l1_masked_bwd(L.view(pdown), L.view(ref), L.view(mask_down), 1e-8, True, (1.0 / n2) if n2 else 0.0, False, L.view(g_pdown), B, st)
             lib.bilinear_bwd(L.view(g_pdown), L.view(g_blur), B, st)
             lib.gauss5_bwd(L.view(g_blur), L.view(g_wide), B, st)
             lib.add(L.view(g_pred), L.view(g_wide), L.view(g_pred), B, st)
@@ -214,6 +239,11 @@ def _get_image_mask_pyramid(batch: dict, min_side: int, max_scales: int, px_budg
     assert batch['image'].shape[0] == 1, "refiner works on only batches of size 1!"
     h, w = batch['unpad_to_size']
     h, w = int(h[0]) if hasattr(h, '__len__') else int(h), int(w[0]) if hasattr(w, '__len__') else int(w)
+    return _image_mask_pyramid(batch, h, w, min_side, max_scales, px_budget)
+
+
+def _image_mask_pyramid(batch: dict, h: int, w: int, min_side: int, max_scales: int, px_budget: int):
+    """The pyramid of _get_image_mask_pyramid for every image of the batch at once (all cropped to the same h x w)."""
     image = batch['image'][..., :h, :w]
     mask = batch['mask'][..., :h, :w].float()
     if h * w > px_budget:
@@ -246,6 +276,19 @@ def _pad_tensor_to_modulo(img: torch.Tensor, mod: int) -> torch.Tensor:
 # refinement.py:228-314
 # ----------------------------------------------------------------------------------------------------------------
 
+def _first_resblock(model) -> Tuple[int, int]:
+    """refinement.py:266-275: (index of the first FFCResnetBlock, number of FFCResnetBlocks) of generator.model."""
+    first_resblock_ind, found = 0, False
+    n_resnet_blocks = 0
+    for idl in range(len(model)):
+        if isinstance(model[idl], ffc.FFCResnetBlock):
+            n_resnet_blocks += 1
+            found = True
+        elif not found:
+            first_resblock_ind += 1
+    return first_resblock_ind, n_resnet_blocks
+
+
 def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: int, lr: float, min_side: int, max_scales: int,
                    px_budget: int, trace: Optional[list] = None, bwd_precision: Optional[int] = None):
     """refinement.py:228-314: coarse-to-fine refinement of the features after generator.model[:first_resblock].
@@ -263,14 +306,7 @@ def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: i
         # refine a pix2pixhd_global generator either
         raise NotImplementedError(f'refine=True needs an ffc_resnet generator; {type(gen).__name__} has no (local, global) feature pair to refine')
     model = gen.model
-    first_resblock_ind, found = 0, False
-    n_resnet_blocks = 0
-    for idl in range(len(model)):                                                         # refinement.py:266-275
-        if isinstance(model[idl], ffc.FFCResnetBlock):
-            n_resnet_blocks += 1
-            found = True
-        elif not found:
-            first_resblock_ind += 1
+    first_resblock_ind, n_resnet_blocks = _first_resblock(model)
     if not n_resnet_blocks:
         raise LamaError('refine_predict: the generator has no resnet blocks')
     device = batch['image'].device
@@ -278,7 +314,15 @@ def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: i
         raise LamaError('refine_predict: the batch must live on the GPU')
     forward_front = model[0:first_resblock_ind]                                           # refinement.py:281
     ls_images, ls_masks = _get_image_mask_pyramid(batch, min_side, max_scales, px_budget)
-    lib = _lib_of(batch['image'])
+    return _refine_pyramid(gen, first_resblock_ind, forward_front, ls_images, ls_masks, modulo, device, n_iters, lr, trace, bwd_precision)
+
+
+def _refine_pyramid(gen, first_resblock_ind: int, forward_front, ls_images, ls_masks, modulo: int, device, n_iters: int, lr: float,
+                    trace: Optional[list], bwd_precision: Optional[int], per_image: bool = False) -> torch.Tensor:
+    """refinement.py:292-314: the coarse-to-fine loop over the pyramid (one batch of images of one size), with the fp16 split's
+    range watch around it (a LamaRangeError repeats the whole loop on the 3-term bf16 split)."""
+    lib = _lib_of(ls_images[0])
+    B = ls_images[0].shape[0]
 
     def run(rear: RearPass):
         image_inpainted = None
@@ -287,9 +331,10 @@ def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: i
             image = _c(_pad_tensor_to_modulo(image, modulo))
             mask = _c(_pad_tensor_to_modulo(mask, modulo))
             mb = torch.empty_like(mask)
-            lib.threshold(L.view(mask), 1e-8, L.view(mb), 1, _stream(mask))               # mask[mask >= 1e-8] = 1; mask[mask < 1e-8] = 0
+            lib.threshold(L.view(mask), 1e-8, L.view(mb), B, _stream(mask))               # mask[mask >= 1e-8] = 1; mask[mask < 1e-8] = 0
             tr = {} if trace is not None else None
-            image_inpainted = _infer(image, mb, forward_front, [rear], image_inpainted, orig_shape, [device], ids_, n_iters, lr, trace=tr)
+            image_inpainted = _infer(image, mb, forward_front, [rear], image_inpainted, orig_shape, [device], ids_, n_iters, lr, trace=tr,
+                                     per_image=per_image)
             image_inpainted = image_inpainted[:, :, :orig_shape[0], :orig_shape[1]]
             if trace is not None:
                 tr['out'] = image_inpainted
@@ -306,3 +351,50 @@ def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: i
         if trace is not None:
             del trace[:]
         return run(RearPass(gen, first_resblock_ind))
+
+
+def _unpad_sizes(batch: dict, B: int) -> List[Tuple[int, int]]:
+    """batch['unpad_to_size'] ([h, w] with one entry -- or a scalar -- per image, as the data loader collates it) -> [(h, w)] * B."""
+    hs, ws = batch['unpad_to_size']
+    hs = [int(v) for v in (hs.reshape(-1).tolist() if torch.is_tensor(hs) else (hs if hasattr(hs, '__len__') else [hs]))]
+    ws = [int(v) for v in (ws.reshape(-1).tolist() if torch.is_tensor(ws) else (ws if hasattr(ws, '__len__') else [ws]))]
+    if len(hs) == 1 and len(ws) == 1:
+        hs, ws = hs * B, ws * B
+    if len(hs) != B or len(ws) != B:
+        raise LamaError(f'refine_predict_batch: unpad_to_size has {len(hs)} x {len(ws)} entries for {B} images')
+    return list(zip(hs, ws))
+
+
+def refine_predict_batch(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: int, lr: float, min_side: int, max_scales: int,
+                         px_budget: int, trace: Optional[list] = None, bwd_precision: Optional[int] = None) -> torch.Tensor:
+    """Extension (the reference refines one image per call): refine_predict for B images of ONE size (the same ``unpad_to_size``,
+    hence the same pyramid and padded shapes) as one batched optimisation.  Every image keeps its own features, Adam moments and
+    loss -- each L1 term is normalised by that image's own selection (lama_l1_masked_per_image_*) and Adam is elementwise -- so
+    image b follows the trajectory of its own batch-1 refinement; the batch fills the chip where one image's bottleneck planes do
+    not, and shares the launches.  Returns the inpainted images [B, 3, h, w] (CPU tensor).  ``trace``: one dict per scale as for
+    refine_predict; its ``'loss'`` holds one list of B per-image losses per iteration and ``'out'`` the batch."""
+    assert not inpainter.training
+    assert not getattr(inpainter, 'add_noise_kwargs', None)
+    assert inpainter.concat_mask
+    ids = [g for g in str(gpu_ids).replace(' ', '').split(',') if g.isdigit()]
+    if len(ids) > 1:
+        warnings.warn(f'lama_amd.refinement: gpu_ids={gpu_ids!r}: the whole model stays on the first GPU (288 GB of HBM); the others are not used')
+    gen = inpainter.generator
+    if not isinstance(gen, ffc.FFCResNetGenerator):
+        raise NotImplementedError(f'refine=True needs an ffc_resnet generator; {type(gen).__name__} has no (local, global) feature pair to refine')
+    first_resblock_ind, n_resnet_blocks = _first_resblock(gen.model)
+    if not n_resnet_blocks:
+        raise LamaError('refine_predict_batch: the generator has no resnet blocks')
+    B = batch['image'].shape[0]
+    if B < 1 or batch['mask'].shape[0] != B:
+        raise LamaError(f'refine_predict_batch: {B} images and {batch["mask"].shape[0]} masks')
+    sizes = _unpad_sizes(batch, B)
+    if len(set(sizes)) != 1:
+        raise LamaError(f'refine_predict_batch: every image of a call must have the same unpad_to_size; got {sorted(set(sizes))}')
+    device = batch['image'].device
+    if not device.type == 'cuda' and getattr(_lib_of, 'override', None) is None:
+        raise LamaError('refine_predict_batch: the batch must live on the GPU')
+    h, w = sizes[0]
+    ls_images, ls_masks = _image_mask_pyramid(batch, h, w, min_side, max_scales, px_budget)
+    return _refine_pyramid(gen, first_resblock_ind, gen.model[0:first_resblock_ind], ls_images, ls_masks, modulo, device, n_iters, lr, trace,
+                           bwd_precision, per_image=True)
