@@ -49,7 +49,7 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void act_bwd_kernel(ActBwdParams p) 
             float d = 1.0f;
             if (p.act == LAMA_ACT_RELU) d = y[e] > 0.0f ? 1.0f : 0.0f;
             else if (p.act == LAMA_ACT_SIGMOID) d = y[e] * (1.0f - y[e]);
-            else if (p.act == LAMA_ACT_TANH) d = 1.0f - y[e] * y[e];
+            else if (p.act == LAMA_ACT_TANH) d = fmaf(-y[e], y[e], 1.0f);      // one rounding: 1 - fl(y^2) loses everything near |y| = 1
             o[e] = g[e] * d;
         }
         *reinterpret_cast<fv_t*>(p.out + b * p.out_bs + r) = o;
@@ -174,7 +174,7 @@ struct FoldParams {
 __device__ __forceinline__ float rf_act_deriv(int act, float y) {
     if (act == LAMA_ACT_RELU) return y > 0.0f ? 1.0f : 0.0f;
     if (act == LAMA_ACT_SIGMOID) return y * (1.0f - y);
-    if (act == LAMA_ACT_TANH) return 1.0f - y * y;
+    if (act == LAMA_ACT_TANH) return fmaf(-y, y, 1.0f);
     return 1.0f;
 }
 
@@ -498,13 +498,10 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void gauss5_bwd_kernel(GaussParams p
 
 namespace {
 void rf_gauss_weights(float* k) {
-    double g[5], s = 0.0;
-    for (int i = 0; i < 5; ++i) { const double x = (double)(i - 2); g[i] = (double)expf((float)(-x * x / 2.0)); s += g[i]; }
     // kornia computes the window in fp32: exp(-x^2 / (2 sigma^2)) / sum
     float gf[5], sf = 0.0f;
     for (int i = 0; i < 5; ++i) { const float x = (float)(i - 2); gf[i] = expf(-x * x / 2.0f); sf += gf[i]; }
     for (int i = 0; i < 5; ++i) k[i] = gf[i] / sf;
-    (void)g; (void)s;
 }
 }  // namespace
 
@@ -711,7 +708,7 @@ extern "C" int lama_erode_fwd(void* stream, const lama_tensor* x, const float* s
 // ------------------------------------------------------------------------------------------------
 // masked L1 terms of refinement.py:75-84: over the elements selected by the mask (mask < thr, or mask >= thr; a 1-channel mask
 // is broadcast over the channels of pred like mask.repeat(1,3,1,1)):
-//   fwd: accum[0] += sum |pred - target|, accum[1] += count          (accum: two device floats... doubles, zeroed by the caller)
+//   fwd: accum[0] += sum |pred - target|, accum[1] += count          (accum: two device doubles, zeroed by the caller)
 //   bwd: g (+)= scale * sign(pred - target) on the selected elements, 0 elsewhere   (d mean|.| / d pred, scale = 1 / count)
 // ------------------------------------------------------------------------------------------------
 struct L1Params {

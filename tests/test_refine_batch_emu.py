@@ -35,10 +35,17 @@ def _np_terms(pred, target, mask, select_ge):
     return [(float(np.abs(d[b][sel[b]]).sum()), float(sel[b].sum())) for b in range(pred.shape[0])], sel
 
 
-@pytest.mark.parametrize('mask_c', [1, 3])
-@pytest.mark.parametrize('select_ge', [False, True])
-def test_l1_masked_per_image_kernels_against_numpy(mask_c, select_ge):
-    lib = emu_lib()
+PER_IMAGE_MASK_C = [1, 3]
+PER_IMAGE_SELECT_GE = [False, True]
+
+
+def _sync(dev):
+    if dev != 'cpu':
+        torch.cuda.synchronize()
+
+
+def check_l1_masked_per_image_kernels_against_numpy(lib, mask_c, select_ge, dev='cpu'):
+    """The body of the test below; tests/test_refine_kernels_gpu.py reruns it through the production library (``dev='cuda'``)."""
     g = torch.Generator().manual_seed(40 + mask_c + 2 * select_ge)
     B, H, W = 3, 11, 17
     pred, target = torch.rand(B, 3, H, W, generator=g), torch.rand(B, 3, H, W, generator=g)
@@ -52,35 +59,48 @@ def test_l1_masked_per_image_kernels_against_numpy(mask_c, select_ge):
         mask[2] = 1.0                                              # image 2: mask all 1 -> nothing < thr: empty selection
     terms, sel = _np_terms(pred.numpy(), target.numpy(), mask.numpy(), select_ge)
     assert terms[2][1] == 0 and terms[0][1] != terms[1][1]
-    acc = torch.zeros(B, 2, dtype=torch.float64)
-    lib.l1_masked_per_image(L.view(pred), L.view(target), L.view(mask), 1e-8, select_ge, acc, B)
+    predd, targetd, maskd = pred.to(dev), target.to(dev), mask.to(dev)
+    accd = torch.zeros(B, 2, dtype=torch.float64, device=dev)
+    lib.l1_masked_per_image(L.view(predd), L.view(targetd), L.view(maskd), 1e-8, select_ge, accd, B)
+    _sync(dev)
+    acc = accd.cpu()
     for b in range(B):
         assert acc[b, 1].item() == terms[b][1]
         assert abs(acc[b, 0].item() - terms[b][0]) <= 1e-9 * max(1.0, terms[b][0])
     sgn = np.sign(pred.numpy() - target.numpy()) * sel
     scale = np.array([np.float32(1.0 / n) if n else np.float32(0.0) for _, n in terms], dtype=np.float32)
     want = (sgn * scale[:, None, None, None]).astype(np.float32)
-    gbuf = torch.full((B, 3, H, W), 5.0)
-    lib.l1_masked_per_image_bwd(L.view(pred), L.view(target), L.view(mask), 1e-8, select_ge, acc, False, L.view(gbuf), B)
-    assert np.array_equal(gbuf.numpy(), want)
+    gbuf = torch.full((B, 3, H, W), 5.0, device=dev)
+    lib.l1_masked_per_image_bwd(L.view(predd), L.view(targetd), L.view(maskd), 1e-8, select_ge, accd, False, L.view(gbuf), B)
+    _sync(dev)
+    assert np.array_equal(gbuf.cpu().numpy(), want)
     assert float(gbuf[2].abs().max()) == 0.0                       # the empty selection contributes 0 (and overwrites)
     base = torch.randn(B, 3, H, W, generator=g)
-    gacc = base.clone()
-    lib.l1_masked_per_image_bwd(L.view(pred), L.view(target), L.view(mask), 1e-8, select_ge, acc, True, L.view(gacc), B)
-    assert np.array_equal(gacc.numpy(), (base.numpy() + want).astype(np.float32))
+    gacc = base.clone().to(dev)
+    lib.l1_masked_per_image_bwd(L.view(predd), L.view(targetd), L.view(maskd), 1e-8, select_ge, accd, True, L.view(gacc), B)
+    _sync(dev)
+    assert np.array_equal(gacc.cpu().numpy(), (base.numpy() + want).astype(np.float32))
     # batch 1: bit-identical to lama_l1_masked_bwd with the host's float(1 / n)
     for b in range(B):
-        one = torch.zeros(1, 2, dtype=torch.float64)
-        v = lambda t: L.view(t[b:b + 1].contiguous())             # noqa: E731
-        lib.l1_masked_per_image(v(pred), v(target), v(mask), 1e-8, select_ge, one, 1)
-        old = torch.zeros(2, dtype=torch.float64)
-        lib.l1_masked(v(pred), v(target), v(mask), 1e-8, select_ge, old, 1)
-        assert torch.equal(one[0], old)
+        one = torch.zeros(1, 2, dtype=torch.float64, device=dev)
+        pb, tb, mb = predd[b:b + 1].contiguous(), targetd[b:b + 1].contiguous(), maskd[b:b + 1].contiguous()
+        lib.l1_masked_per_image(L.view(pb), L.view(tb), L.view(mb), 1e-8, select_ge, one, 1)
+        old = torch.zeros(2, dtype=torch.float64, device=dev)
+        lib.l1_masked(L.view(pb), L.view(tb), L.view(mb), 1e-8, select_ge, old, 1)
+        _sync(dev)
+        assert torch.equal(one[0].cpu(), old.cpu())
         n = float(old[1])
-        g_old, g_new = torch.zeros(1, 3, H, W), torch.zeros(1, 3, H, W)
-        lib.l1_masked_bwd(v(pred), v(target), v(mask), 1e-8, select_ge, (1.0 / n) if n else 0.0, False, L.view(g_old), 1)
-        lib.l1_masked_per_image_bwd(v(pred), v(target), v(mask), 1e-8, select_ge, one, False, L.view(g_new), 1)
-        assert torch.equal(g_old, g_new)
+        g_old, g_new = torch.zeros(1, 3, H, W, device=dev), torch.zeros(1, 3, H, W, device=dev)
+        lib.l1_masked_bwd(L.view(pb), L.view(tb), L.view(mb), 1e-8, select_ge, (1.0 / n) if n else 0.0, False, L.view(g_old), 1)
+        lib.l1_masked_per_image_bwd(L.view(pb), L.view(tb), L.view(mb), 1e-8, select_ge, one, False, L.view(g_new), 1)
+        _sync(dev)
+        assert torch.equal(g_old.cpu(), g_new.cpu())
+
+
+@pytest.mark.parametrize('mask_c', PER_IMAGE_MASK_C)
+@pytest.mark.parametrize('select_ge', PER_IMAGE_SELECT_GE)
+def test_l1_masked_per_image_kernels_against_numpy(mask_c, select_ge):
+    check_l1_masked_per_image_kernels_against_numpy(emu_lib(), mask_c, select_ge)
 
 
 def _case(B, seed, Hp=96, Wp=104):
