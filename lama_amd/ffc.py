@@ -116,7 +116,7 @@ class _Exec:
     It also owns the RANGE WATCH of the fp16 split (lama_conv2d_args.range_flag): every public ``forward`` opens a
     ``range_scope``; the conv / FourierUnit launches inside it hand the per-device flag to the kernels, and the outermost
     scope reads it back when it closes (one 4-byte D2H per forward) and raises ``LamaRangeError`` if an activation beyond
-    65504 (or a NaN) was split -- FFCResNetGenerator.forward then falls back to PREC_BF16X3."""
+    65504 (or a NaN) was split -- _PlanGenerator.forward then falls back to PREC_BF16X3."""
 
     def __init__(self, lib: Optional[L.LamaLib] = None):
         self._lib = lib
@@ -298,6 +298,183 @@ class _HipModule(nn.Module):
         return super().train(False)
 
 
+class _PlanGenerator(_HipModule):
+    """Base of the generators (FFCResNetGenerator, pix2pixhd.GlobalGenerator): the serving machinery around a per-shape launch plan.
+    A subclass supplies ``_build_plan(shape, device) -> dict`` (every activation buffer pre-allocated, the launch list recorded; keys
+    ``bufs``, ``out``, ``graph=None``, ``static_in=None`` at least) and ``_run_plan(plan, x) -> output buffer``; this class keeps the plans
+    of the most recently used shapes, captures and replays them as hipGraphs and owns the fp16 split's range fallback."""
+
+    def __init__(self):
+        super().__init__()
+        self.use_graph = False
+        # fp16-split range watch (lama_conv2d_args.range_flag): one 4-byte read-back per forward; when an activation beyond 65504
+        # (or a NaN) was met the forward is repeated with the 3-term bf16 split (fp32 exponent range) and the generator stays
+        # on it.  auto_fallback = False raises LamaRangeError instead.
+        self.auto_fallback = True
+        # True: ``forward`` does NOT read the flag back (no host synchronisation per forward: step k + 1 queues behind step k, and a serving
+        # loop's launch thread never waits for the GPU); the flag stays raised on the device and the CALLER asks at its own synchronisation
+        # point -- ``check_range()`` -- before it trusts the results produced since the last check.  predict.py (per bucket) and bench.py
+        # (closing barrier of the timed region) run this way.  Default False: a plain ``generator(x)`` is self-checking like the reference.
+        self.defer_range_check = False
+        # False: ``forward`` returns the plan's own output buffer instead of a copy of it -- for callers that consume the result before this
+        # generator's next forward of the same shape (DefaultInpaintingTrainingModule with keep_predicted_image = False: blend reads it at once)
+        self.clone_output = True
+        # activation-buffer sets (+ captured hipGraphs) per input shape: 2.2 GB at 8 x 512^2, so only the most recently used
+        # ``max_plans`` shapes are kept (a directory of many image sizes would otherwise fill HBM)
+        self.max_plans = 4
+        self._assume_graph = False        # set by a caller that captures this generator's plain launches into a graph of its own (HostFedStep)
+        self.split_decisions = {}         # (shape, device) -> what tune_split measured and kept (bench.py prints it)
+        self._plans = collections.OrderedDict()
+
+    def _invalidate(self):
+        super()._invalidate()
+        self._plans = collections.OrderedDict()
+
+    @staticmethod
+    def _plan_key(shape, device):
+        """Key of the plan cache and of the split verdicts: 'cuda' and 'cuda:<current>' are ONE device (ADVICE r5: predict / HostFedStep pass
+        torch.device('cuda'), every forward sees x.device = 'cuda:0' -- two keys meant a verdict and a tuned plan no forward ever found)."""
+        return (tuple(int(v) for v in shape), _Exec._dev_key(device))
+
+    def _split_parts(self, shape, device) -> int:
+        """How many parallel parts the plan of this input shape has: one, unless the generator builds split plans."""
+        return 1
+
+    def _new_plan(self, shape, device, n: int) -> dict:
+        return self._build_plan(shape, device)
+
+    def _make_room(self):
+        """Release the least recently used plans until one more fits under ``max_plans``."""
+        while len(self._plans) >= max(1, self.max_plans):
+            self._plans.popitem(last=False)
+
+    def _plan_for(self, shape, device) -> dict:
+        key = self._plan_key(shape, device)
+        n = self._split_parts(shape, device)                 # on every call, cached plan or not: a bad ``split_batch`` raises here
+        plan = self._plans.get(key)
+        if plan is not None and plan.get('nsplit', 1) != n:
+            plan = None                                      # split_batch changed since this plan was built
+            del self._plans[key]
+        if plan is None:
+            self._make_room()                                # BEFORE the new plan allocates: its buffers take the evicted plan's blocks
+            plan = self._plans[key] = self._new_plan(shape, device, n)
+        else:
+            self._plans.move_to_end(key)
+        return plan
+
+    def drop_plan(self, shape, device) -> None:
+        """Free the activation buffers / captured graph of one input shape (predict.py drops a bucket's plan when it is done)."""
+        self._plans.pop(self._plan_key(shape, device), None)
+
+    def input_buffer(self, shape, device) -> torch.Tensor:
+        """The tensor this shape's plan READS its input from (the captured hipGraph's static input when ``use_graph``): a caller that produces
+        the generator's input itself (DefaultInpaintingTrainingModule: mask_compose) writes it here and passes it to ``forward``, which then
+        skips its staging copy (33.5 MB read + written per step at 8 x 512^2).  Valid until the plan is dropped."""
+        device = torch.device(device)
+        plan = self._plan_for(shape, device)
+        if plan['static_in'] is None:
+            plan['static_in'] = torch.empty(tuple(shape), device=device, dtype=torch.float32)
+        return plan['static_in']
+
+    def _capture(self, plan, device):
+        """Warm the plan up on a side stream (packs weights) and capture its launches into plan['graph']; plan['static_in'] holds the input."""
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):           # warm-up outside capture
+            self._run_plan(plan, plan['static_in'])
+        torch.cuda.current_stream(device).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            plan['static_out'] = self._run_plan(plan, plan['static_in'])
+        plan['graph'] = g
+
+    def _forward(self, x: torch.Tensor) -> torch.Tensor:
+        plan = self._plan_for(x.shape, x.device)
+        # ``clone_output`` False: the caller consumes the result before this generator's next forward (the plan's output buffer is returned)
+        fin = (lambda t: t.clone()) if self.clone_output else (lambda t: t)
+        if not (self.use_graph and x.is_cuda):
+            return fin(self._run_plan(plan, x))
+        own = plan['static_in'] is not None and x.data_ptr() == plan['static_in'].data_ptr()       # written in place by the caller (input_buffer)
+        if plan['graph'] is None:
+            if not own:
+                plan['static_in'] = torch.empty_like(x)
+                plan['static_in'].copy_(x)
+            self._capture(plan, x.device)
+        if not own:
+            plan['static_in'].copy_(x)
+        plan['graph'].replay()
+        return fin(plan['static_out'])
+
+    def _can_fall_back(self) -> bool:
+        return self.auto_fallback and self.precision in (L.PREC_F16X3, L.PREC_F16)
+
+    def _check_input(self, x: torch.Tensor):
+        self._exec.check(x)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        self._check_input(input)
+        x = input.contiguous()
+        try:
+            with self._exec.range_scope(x, self.precision, deferred=self.defer_range_check):
+                return self._forward(x)
+        except LamaRangeError as e:
+            if not self._can_fall_back():
+                raise
+            warnings.warn(f'lama_amd: {e}; switching this generator to the 3-term bf16 split (PREC_BF16X3)')
+            self.set_precision(L.PREC_BF16X3)
+            return self.forward(input)
+
+    def check_range(self, device=None, reduce=None) -> bool:
+        """The other half of ``defer_range_check``: one 4-byte read-back (a host synchronisation) of the range flag the forwards since the last
+        check have been OR-ing into.  Returns True when every one of them stayed inside the fp16 split's range.  Otherwise their results are NOT
+        valid: with ``auto_fallback`` the generator switches to the 3-term bf16 split and False is returned -- the caller re-runs those inputs --
+        without it LamaRangeError is raised.  ``reduce`` (multi-rank callers): bool -> bool, the OR over all ranks, called UNCONDITIONALLY (a
+        collective), so that every rank switches precision and re-runs alike."""
+        bad = self._exec.range_flag_raised(device)
+        if reduce is not None:
+            bad = bool(reduce(bad))
+        if not bad:
+            return True
+        if not self._can_fall_back():
+            raise LamaRangeError(_RANGE_MSG)
+        warnings.warn(f'lama_amd: {_RANGE_MSG}; switching this generator to the 3-term bf16 split (PREC_BF16X3): re-run the inputs since the last check')
+        self.set_precision(L.PREC_BF16X3)
+        return False
+
+
+def _plan_up(layers, i, src, dst, src_shape, bufs, steps, device):
+    """Plan ``layers[i]``, a ConvTranspose2dUp, with the BatchNorm2dEval (+ Activation) behind it folded into its launch: allocates
+    ``bufs[dst]`` and appends the 'up' step.  Returns (output shape, number of layers taken)."""
+    lay, n = layers[i], len(layers)
+    bn = layers[i + 1] if i + 1 < n and isinstance(layers[i + 1], BatchNorm2dEval) else None
+    act = layers[i + 2] if bn is not None and i + 2 < n and isinstance(layers[i + 2], Activation) else None
+    B, _, H, W = src_shape
+    shp = (B, lay.out_channels, 2 * H, 2 * W)
+    bufs[dst] = torch.empty(shp, device=device, dtype=_act_dtype(lay.precision))
+    steps.append(('up', lay, src, dst, bn, _ACT[act.kind] if act else L.ACT_NONE))
+    return shp, 1 + (bn is not None) + (act is not None)
+
+
+def _plan_out(layers, i, src, dst, src_shape, pad, bufs, steps, device):
+    """Plan ``layers[i]``, the Conv2dOut head, with the pending reflection pad ``pad`` and the output Activation behind it folded into its
+    launch: allocates ``bufs[dst]`` (fp32 at every precision) and appends the 'out' step.  Returns (output shape, number of layers taken)."""
+    lay = layers[i]
+    act = layers[i + 1] if i + 1 < len(layers) and isinstance(layers[i + 1], Activation) else None
+    B, _, H, W = src_shape
+    kk, p = lay.kernel_size[0], lay.padding[0] + pad
+    shp = (B, lay.out_channels, H + 2 * p - kk + 1, W + 2 * p - kk + 1)
+    bufs[dst] = torch.empty(shp, device=device, dtype=torch.float32)
+    steps.append(('out', lay, src, dst, pad, _ACT[act.kind] if act else L.ACT_NONE))
+    return shp, 2 if act else 1
+
+
+def _run_step(st, buf):
+    """Run a plan step of the form (kind, layer, source name, destination name, *what the layer's ``run`` takes behind the two tensors):
+    the 'up' and 'out' steps above, and the regular generator's 'conv'."""
+    lay, src, dst = st[1:4]
+    lay.run(buf(src), buf(dst), *st[4:])
+
+
 # ----------------------------------------------------------------------------------------------------
 # FourierUnit / SpectralTransform
 # ----------------------------------------------------------------------------------------------------
@@ -462,10 +639,8 @@ class FFC(_HipModule):
         outputs (None = the bare FFC of ffc.py:205-225: no BatchNorm, no bias)."""
         f, lib, prec = self, self._exec.lib, self.precision
         pk = {}
-        dev = f.convl2l.weight.device if isinstance(f.convl2l, nn.Conv2d) else f.convl2g.weight.device
 
         def cat_opt(ts, n):
-            ts = [t if t is not None else None for t in ts]
             return None if any(t is None for t in ts) else torch.cat(ts, 0).contiguous()
 
         if f.in_cg == 0:
@@ -497,7 +672,6 @@ class FFC(_HipModule):
             st._pack(sg)
             st._packed['fused_scale'] = id(sg) if sg is not None else 'none'
             st.fu._pack()
-        del dev
         return pk
 
     # -- launch --------------------------------------------------------------------------------------
@@ -888,7 +1062,7 @@ class LayerSequence(nn.Sequential):
 # the generator
 # ----------------------------------------------------------------------------------------------------
 
-class FFCResNetGenerator(_HipModule):
+class FFCResNetGenerator(_PlanGenerator):
     """ffc.py:305-367.  ``forward(x[B,input_nc,H,W]) -> [B,output_nc,H,W]``; ``.model`` has the reference's
     36-entry layout (big-lama) and state_dict keys.
 
@@ -940,7 +1114,6 @@ class FFCResNetGenerator(_HipModule):
                 raise ValueError(f'Unknown activation kind {kind}')
             model.append(Activation(kind))
         self.model = LayerSequence(*model)
-        self.use_graph = False
         # spectral branch (conv1 -> rfft2 -> spectral 1x1 -> irfft2) on a second stream next to the MFMA-bound local 3x3 conv,
         # joined before the global conv (fused forward only; fork / join are captured into the hipGraph).  +3-4 % images/s.
         # Round 1 had to switch it off: FFT planes came out wrong when FFT and conv workgroups shared a CU.  Root cause (round 2,
@@ -960,15 +1133,6 @@ class FFCResNetGenerator(_HipModule):
         # layer.  Off: inside a hipGraph ROCm 7.2 spreads that topology over three queues and every edge becomes a ~10 us cross-queue
         # signal (727 -> 695 images/s, profiles/r02_ab_pipeline_local.txt); bit-identical results either way.
         self.pipeline_local = False
-        # fp16-split range watch (lama_conv2d_args.range_flag): one 4-byte read-back per forward; when an activation beyond 65504
-        # (or a NaN) was met the forward is repeated with the 3-term bf16 split (fp32 exponent range) and the generator stays
-        # on it.  auto_fallback = False raises LamaRangeError instead.
-        self.auto_fallback = True
-        # True: ``forward`` does NOT read the flag back (no host synchronisation per forward: step k + 1 queues behind step k, and a serving
-        # loop's launch thread never waits for the GPU); the flag stays raised on the device and the CALLER asks at its own synchronisation
-        # point -- ``check_range()`` -- before it trusts the results produced since the last check.  predict.py (per bucket) and bench.py
-        # (closing barrier of the timed region) run this way.  Default False: a plain ``generator(x)`` is self-checking like the reference.
-        self.defer_range_check = False
         # LAMA_PREC_F16 (fp16 activations in HBM, BASELINE configs[2]): the layers BEHIND the resnet blocks -- the three ConvTranspose2d + BN + ReLU and
         # the 7x7 head -- keep fp32 tensors and the 3-term split.  Measured on the oracle with a rounding to fp16 wherever the path has one
         # (tools/fp16_by_tensor.py, 1 x 1024^2): every ONE of the three upsampled tensors in fp16 costs 5-9e-3 max-abs on its own (the features
@@ -982,9 +1146,6 @@ class FFCResNetGenerator(_HipModule):
         self.alias_wino = True
         # the Winograd output transform of a residual layer inside the rfft2 launch of the next one (one-stream plans)
         self.defer_wino_out = True
-        # activation-buffer sets (+ captured hipGraphs) per input shape: 2.2 GB at 8 x 512^2, so only the most recently used
-        # ``max_plans`` shapes are kept (a directory of many image sizes would otherwise fill HBM)
-        self.max_plans = 4
         # Parts of a batch as PARALLEL BRANCHES of the plan (round 5).  Every launch of the one-stream forward fills the chip with workgroups that run
         # the same phase at the same time, and between two launches the chip drains and refills (~190 boundaries per forward).  Two (four) parts of
         # the batch, each with its own buffers, issued on streams of their own inside the SAME captured hipGraph (kernel branches of a graph run
@@ -1002,15 +1163,9 @@ class FFCResNetGenerator(_HipModule):
         # quarter-size launches of a split plan would run one after the other on a quarter of the chip each; the check then keeps the one-part
         # plan.  ~100 ms once per shape.  False: trust the rule.
         self.verify_split = True
-        self._assume_graph = False        # set by a caller that captures this generator's plain launches into a graph of its own (HostFedStep)
         self._split_ok = {}               # (shape, device) -> False where the check rejected the split plan
-        self.split_decisions = {}         # (shape, device) -> what tune_split measured and kept (bench.py prints it)
         self.split_margin = 0.02          # the split plan must be this much faster (median) to be kept
         self.split_replays = 9            # timed replays of each graph in tune_split
-        # False: ``forward`` returns the plan's own output buffer instead of a copy of it -- for callers that consume the result before this
-        # generator's next forward of the same shape (DefaultInpaintingTrainingModule with keep_predicted_image = False: blend reads it at once)
-        self.clone_output = True
-        self._plans = collections.OrderedDict()
         super().train(False)
 
     # ------------------------------------------------------------------------------------------------
@@ -1025,7 +1180,6 @@ class FFCResNetGenerator(_HipModule):
 
     def _invalidate(self):
         super()._invalidate()
-        self._plans = collections.OrderedDict()
         self._split_ok = {}
 
     def _build_plan(self, shape, device, one_stream: bool = False):
@@ -1079,26 +1233,12 @@ class FFCResNetGenerator(_HipModule):
             elif isinstance(lay, ConcatTupleLayer):
                 pass
             elif isinstance(lay, ConvTranspose2dUp):
-                bn = layers[i + 1] if i + 1 < n and isinstance(layers[i + 1], BatchNorm2dEval) else None
-                act = layers[i + 2] if bn is not None and i + 2 < n and isinstance(layers[i + 2], Activation) else None
-                B, _, H, W = cur_shape
-                shp = (B, lay.out_channels, 2 * H, 2 * W)
-                dst = new(f'a{k}', shp, _act_dtype(lay.precision)); k += 1
-                if bn is not None and act is not None:
-                    steps.append(('up', lay, cur, dst, bn, _ACT[act.kind])); i += 2
-                else:
-                    steps.append(('up', lay, cur, dst, None, L.ACT_NONE))
-                cur, cur_shape = dst, shp
+                dst = f'a{k}'; k += 1
+                cur_shape, took = _plan_up(layers, i, cur, dst, cur_shape, bufs, steps, device)
+                cur = dst; i += took - 1
             elif isinstance(lay, Conv2dOut):
-                act = layers[i + 1] if i + 1 < n and isinstance(layers[i + 1], Activation) else None
-                B, _, H, W = cur_shape
-                kk, p = lay.kernel_size[0], lay.padding[0] + pad_pending
-                shp = (B, lay.out_channels, H + 2 * p - kk + 1, W + 2 * p - kk + 1)
-                dst = new('out', shp, torch.float32)
-                steps.append(('out', lay, cur, dst, pad_pending, _ACT[act.kind] if act else L.ACT_NONE))
-                cur, cur_shape, pad_pending = dst, shp, 0
-                if act:
-                    i += 1
+                cur_shape, took = _plan_out(layers, i, cur, 'out', cur_shape, pad_pending, bufs, steps, device)
+                cur, pad_pending = 'out', 0; i += took - 1
             else:
                 raise LamaError(f'no fused plan for layer {type(lay).__name__}; run generator.model layer by layer')
             i += 1
@@ -1178,53 +1318,9 @@ class FFCResNetGenerator(_HipModule):
                         self._exec.lib.winograd_out(pend[0], pend[1], self._exec.stream(x))
                     if pipe is not None:
                         pipe.join()                 # the last local conv: everything downstream reads its x_l
-            elif kind == 'up':
-                _, lay, s, d, bn, act = st
-                lay.run(B(s), B(d), bn, act)
-            else:
-                _, lay, s, d, pad, act = st
-                lay.run(B(s), B(d), pad, act)
+            else:                                   # 'up', 'out'
+                _run_step(st, B)
         return bufs[plan['out']]
-
-    def drop_plan(self, shape, device) -> None:
-        """Free the activation buffers / captured graph of one input shape (predict.py drops a bucket's plan when it is done)."""
-        self._plans.pop(self._plan_key(shape, device), None)
-
-    @staticmethod
-    def _plan_key(shape, device):
-        """Key of the plan cache and of the split verdicts: 'cuda' and 'cuda:<current>' are ONE device (ADVICE r5: predict / HostFedStep pass
-        torch.device('cuda'), every forward sees x.device = 'cuda:0' -- two keys meant a verdict and a tuned plan no forward ever found)."""
-        return (tuple(int(v) for v in shape), _Exec._dev_key(device))
-
-    def forward(self, input: torch.Tensor) -> torch.Tensor:
-        self._exec.check(input)
-        x = input.contiguous()
-        try:
-            with self._exec.range_scope(x, self.precision, deferred=self.defer_range_check):
-                return self._forward(x)
-        except LamaRangeError as e:
-            if not self.auto_fallback or self.precision not in (L.PREC_F16X3, L.PREC_F16):
-                raise
-            warnings.warn(f'lama_amd: {e}; switching this generator to the 3-term bf16 split (PREC_BF16X3)')
-            self.set_precision(L.PREC_BF16X3)
-            return self.forward(input)
-
-    def check_range(self, device=None, reduce=None) -> bool:
-        """The other half of ``defer_range_check``: one 4-byte read-back (a host synchronisation) of the range flag the forwards since the last
-        check have been OR-ing into.  Returns True when every one of them stayed inside the fp16 split's range.  Otherwise their results are NOT
-        valid: with ``auto_fallback`` the generator switches to the 3-term bf16 split and False is returned -- the caller re-runs those inputs --
-        without it LamaRangeError is raised.  ``reduce`` (multi-rank callers): bool -> bool, the OR over all ranks, called UNCONDITIONALLY (a
-        collective), so that every rank switches precision and re-runs alike."""
-        bad = self._exec.range_flag_raised(device)
-        if reduce is not None:
-            bad = bool(reduce(bad))
-        if not bad:
-            return True
-        if not self.auto_fallback or self.precision not in (L.PREC_F16X3, L.PREC_F16):
-            raise LamaRangeError(_RANGE_MSG)
-        warnings.warn(f'lama_amd: {_RANGE_MSG}; switching this generator to the 3-term bf16 split (PREC_BF16X3): re-run the inputs since the last check')
-        self.set_precision(L.PREC_BF16X3)
-        return False
 
     def _split_parts(self, shape, device) -> int:
         """How many parallel parts the plan of this input shape has (``split_batch``)."""
@@ -1282,42 +1378,8 @@ class FFCResNetGenerator(_HipModule):
             ex.siblings_log2 = keep
         return plan['out_full']
 
-    def _plan_for(self, shape, device) -> dict:
-        key = self._plan_key(shape, device)
-        n = self._split_parts(shape, device)
-        plan = self._plans.get(key)
-        if plan is not None and plan.get('nsplit', 1) != n:
-            plan = None                                      # split_batch changed since this plan was built
-            del self._plans[key]
-        if plan is None:
-            while len(self._plans) >= max(1, self.max_plans):
-                self._plans.popitem(last=False)
-            plan = self._plans[key] = self._build_split_plan(shape, device, n) if n > 1 else self._build_plan(shape, device)
-        else:
-            self._plans.move_to_end(key)
-        return plan
-
-    def input_buffer(self, shape, device) -> torch.Tensor:
-        """The tensor this shape's plan READS its input from (the captured hipGraph's static input when ``use_graph``): a caller that produces
-        the generator's input itself (DefaultInpaintingTrainingModule: mask_compose) writes it here and passes it to ``forward``, which then
-        skips its staging copy (33.5 MB read + written per step at 8 x 512^2).  Valid until the plan is dropped."""
-        device = torch.device(device)
-        plan = self._plan_for(shape, device)
-        if plan['static_in'] is None:
-            plan['static_in'] = torch.empty(tuple(shape), device=device, dtype=torch.float32)
-        return plan['static_in']
-
-    def _capture(self, plan, device):
-        """Warm the plan up on a side stream (packs weights) and capture its launches into plan['graph']; plan['static_in'] holds the input."""
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):           # warm-up outside capture
-            self._run_plan(plan, plan['static_in'])
-        torch.cuda.current_stream(device).wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            plan['static_out'] = self._run_plan(plan, plan['static_in'])
-        plan['graph'] = g
+    def _new_plan(self, shape, device, n: int) -> dict:
+        return self._build_split_plan(shape, device, n) if n > 1 else self._build_plan(shape, device)
 
     def tune_split(self, shape, device) -> int:
         """``verify_split``: decide ONCE per input shape whether the split plan the rule proposes really runs its parts side by side (see
@@ -1336,7 +1398,7 @@ class FFCResNetGenerator(_HipModule):
         cand, times = {}, {n: [], 1: []}
         with self._exec.scratch_range_scope(x, self.precision):
             for parts in (n, 1):
-                plan = self._build_split_plan(shape, device, parts) if parts > 1 else self._build_plan(shape, device)
+                plan = self._new_plan(shape, device, parts)
                 plan['static_in'] = x
                 self._capture(plan, device)
                 cand[parts] = plan
@@ -1362,8 +1424,7 @@ class FFCResNetGenerator(_HipModule):
         plan = cand.pop(n if ok else 1)           # (its captured graph and its input buffer -- the random tensor -- stay: forward stages into it,
         cand.clear()                              #  input_buffer hands it to a caller that writes its input in place); the loser is released now
         del x
-        while len(self._plans) >= max(1, self.max_plans):
-            self._plans.popitem(last=False)
+        self._make_room()
         self._plans[key] = plan
         torch.cuda.empty_cache()
         return n if ok else 1
@@ -1371,18 +1432,4 @@ class FFCResNetGenerator(_HipModule):
     def _forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.use_graph and x.is_cuda and self.verify_split and self.split_batch is None:
             self.tune_split(x.shape, x.device)
-        plan = self._plan_for(x.shape, x.device)
-        # ``clone_output`` False: the caller consumes the result before this generator's next forward (the plan's output buffer is returned)
-        fin = (lambda t: t.clone()) if self.clone_output else (lambda t: t)
-        if not (self.use_graph and x.is_cuda):
-            return fin(self._run_plan(plan, x))
-        own = plan['static_in'] is not None and x.data_ptr() == plan['static_in'].data_ptr()       # written in place by the caller (input_buffer)
-        if plan['graph'] is None:
-            if not own:
-                plan['static_in'] = torch.empty_like(x)
-                plan['static_in'].copy_(x)
-            self._capture(plan, x.device)
-        if not own:
-            plan['static_in'].copy_(x)
-        plan['graph'].replay()
-        return fin(plan['static_out'])
+        return super()._forward(x)

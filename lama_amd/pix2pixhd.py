@@ -12,8 +12,6 @@ paddings, ``affine``, dilation) raise ``NotImplementedError`` at construction.
 """
 from __future__ import annotations
 
-import collections
-import warnings
 from typing import List, Optional
 
 import torch
@@ -21,8 +19,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import LamaError, LamaRangeError
-from .ffc import (_ACT, _DEFAULT_EXEC, _RANGE_MSG, Activation, BatchNorm2dEval, Conv2dOut, ConvTranspose2dUp, LayerSequence,
-                  ReflectionPad2d, _bn_fold, _Exec, _HipModule)
+from .ffc import (_ACT, _DEFAULT_EXEC, Activation, BatchNorm2dEval, Conv2dOut, ConvTranspose2dUp, LayerSequence, ReflectionPad2d,
+                  _bn_fold, _HipModule, _plan_out, _plan_up, _PlanGenerator, _run_step)
 
 
 def _is_bn(norm_layer) -> bool:
@@ -152,15 +150,16 @@ class ResnetBlock(_HipModule):
         return dst
 
 
-class GlobalGenerator(_HipModule):
+class GlobalGenerator(_PlanGenerator):
     """pix2pixhd.py:341-436.  ``forward(x[B,input_nc,H,W]) -> [B,output_nc,H,W]``; ``.model`` has the reference's layout
     (stem 0-3, downsampling 4-12, ``n_blocks`` ResnetBlocks, 3 x (ConvTranspose2d, BN, ReLU), pad + 7x7 conv, output activation).
 
     The fused forward is a plan of HIP launches per input shape: stem (reflect pad + 7x7 conv + BN + ReLU), three stride-2 convs + BN +
     ReLU, the blocks on ONE state buffer (conv A into a scratch, conv B in place over the block input), three ConvTranspose2d + BN + ReLU
     and the 7x7 head with its activation.  The 512 -> 512 convs of the blocks run as Winograd F(2x2, 3x3) where
-    ``lama_winograd_preferred`` says so (split precisions), otherwise as the direct kernel; ``use_graph=True`` replays the plan from a
-    captured hipGraph.  ``split_batch`` is fixed at one part (``tune_split`` decides nothing for this generator)."""
+    ``lama_winograd_preferred`` says so (split precisions), otherwise as the direct kernel.  The plan cache, ``use_graph`` (replay from a
+    captured hipGraph), ``input_buffer`` / ``clone_output`` and the fp16 split's range fallback (``auto_fallback``, ``defer_range_check`` /
+    ``check_range``) are ``ffc._PlanGenerator``'s.  ``split_batch`` is fixed at one part (``tune_split`` decides nothing for this generator)."""
 
     def __init__(self, input_nc, output_nc, ngf=64, n_downsampling=3, n_blocks=9, norm_layer=nn.BatchNorm2d, padding_type='reflect',
                  conv_kind='default', activation=nn.ReLU(True), up_norm_layer=nn.BatchNorm2d, affine=None, up_activation=nn.ReLU(True),
@@ -210,17 +209,7 @@ class GlobalGenerator(_HipModule):
             model.append(Activation(kind))
         self.model = LayerSequence(*model)
         self.n_downsampling = n_downsampling
-        self.use_graph = False
-        # the fp16-split range watch (as FFCResNetGenerator): a forward that split an activation beyond 65504 (or a NaN) is repeated with
-        # the 3-term bf16 split and the generator stays on it; auto_fallback = False raises LamaRangeError instead
-        self.auto_fallback = True
-        self.defer_range_check = False    # True: no flag read-back per forward; the caller asks check_range() at its own synchronisation point
-        self.clone_output = True          # False: forward returns the plan's own output buffer (overwritten by the next forward of the shape)
-        self.max_plans = 4                # activation buffers (+ captured graphs) of the most recently used input shapes
         self.split_batch = 1              # one part: no split-batch plans for this generator
-        self._assume_graph = False
-        self.split_decisions = {}
-        self._plans = collections.OrderedDict()
         super().train(False)
 
     # ------------------------------------------------------------------------------------------------
@@ -228,10 +217,6 @@ class GlobalGenerator(_HipModule):
         if precision == L.PREC_F16:
             raise NotImplementedError('GlobalGenerator: fp16 activations (LAMA_PREC_F16) are not implemented; use f16x3, bf16x3 or f32')
         return super().set_precision(precision)
-
-    def _invalidate(self):
-        super()._invalidate()
-        self._plans = collections.OrderedDict()
 
     def tune_split(self, shape, device) -> int:
         """Split-batch plans are not built for this generator: always one part."""
@@ -284,22 +269,13 @@ class GlobalGenerator(_HipModule):
                 steps.append(('res', lay))
                 i += 1
             elif isinstance(lay, ConvTranspose2dUp):
-                bn, act = bn_act(i + 1)
-                B, _, H, W = cur_shape
-                shp = (B, lay.out_channels, 2 * H, 2 * W)
-                dst = new(shp)
-                steps.append(('up', lay, cur, dst, bn, _ACT[act.kind] if act else L.ACT_NONE))
-                cur, cur_shape = dst, shp
-                i += 1 + (bn is not None) + (act is not None)
+                dst = f'a{k}'; k += 1
+                cur_shape, took = _plan_up(layers, i, cur, dst, cur_shape, bufs, steps, device)
+                cur, i = dst, i + took
             elif isinstance(lay, Conv2dOut):
-                act = layers[i + 1] if i + 1 < n and isinstance(layers[i + 1], Activation) else None
-                B, _, H, W = cur_shape
-                kk, p = lay.kernel_size[0], lay.padding[0] + pad_pending
-                shp = (B, lay.out_channels, H + 2 * p - kk + 1, W + 2 * p - kk + 1)
-                dst = new(shp)
-                steps.append(('out', lay, cur, dst, pad_pending, _ACT[act.kind] if act else L.ACT_NONE))
-                cur, cur_shape, pad_pending = dst, shp, 0
-                i += 2 if act else 1
+                dst = f'a{k}'; k += 1
+                cur_shape, took = _plan_out(layers, i, cur, dst, cur_shape, pad_pending, bufs, steps, device)
+                cur, pad_pending, i = dst, 0, i + took
             else:
                 raise LamaError(f'no fused plan for layer {type(lay).__name__}; run generator.model layer by layer')
         # the 512 -> 512 convs of the blocks: Winograd where the library expects it to beat the direct kernel at this shape and every block
@@ -322,107 +298,21 @@ class GlobalGenerator(_HipModule):
         paths = []
         for st in plan['steps']:
             kind = st[0]
-            if kind == 'conv':
-                _, lay, s, d, bn, act, pad, mode = st
-                lay.run(B(s), B(d), bn, act, pad, mode)
-            elif kind == 'res':
+            if kind == 'res':
                 paths.extend(st[1].run(bufs['st'], bufs['t'], bufs['st'], plan['wino_ws']))
-            elif kind == 'up':
-                _, lay, s, d, bn, act = st
-                lay.run(B(s), B(d), bn, act)
-            elif kind == 'out':
-                _, lay, s, d, pad, act = st
-                lay.run(B(s), B(d), pad, act)
-            else:
+            elif kind == 'copy':
                 B(st[2]).copy_(B(st[1]))
+            else:                                   # 'conv', 'up', 'out'
+                _run_step(st, B)
         plan['paths'] = ['winograd' if w else 'direct' for w in paths]   # per bottleneck launch, in launch order
         return bufs[plan['out']]
-
-    @staticmethod
-    def _plan_key(shape, device):
-        return (tuple(int(v) for v in shape), _Exec._dev_key(device))
-
-    def _plan_for(self, shape, device) -> dict:
-        key = self._plan_key(shape, device)
-        plan = self._plans.get(key)
-        if plan is None:
-            while len(self._plans) >= max(1, self.max_plans):
-                self._plans.popitem(last=False)
-            plan = self._plans[key] = self._build_plan(shape, device)
-        else:
-            self._plans.move_to_end(key)
-        return plan
-
-    def drop_plan(self, shape, device) -> None:
-        """Free the activation buffers / captured graph of one input shape."""
-        self._plans.pop(self._plan_key(shape, device), None)
 
     def conv_paths(self, shape, device) -> Optional[List[str]]:
         """'winograd' / 'direct' for each bottleneck launch of this shape's plan, in launch order (None before its first forward)."""
         plan = self._plans.get(self._plan_key(shape, device))
         return None if plan is None else plan['paths']
 
-    def input_buffer(self, shape, device) -> torch.Tensor:
-        """The tensor this shape's plan reads its input from (see FFCResNetGenerator.input_buffer)."""
-        device = torch.device(device)
-        plan = self._plan_for(shape, device)
-        if plan['static_in'] is None:
-            plan['static_in'] = torch.empty(tuple(shape), device=device, dtype=torch.float32)
-        return plan['static_in']
-
-    def _capture(self, plan, device):
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):           # warm-up outside capture (packs the weights)
-            self._run_plan(plan, plan['static_in'])
-        torch.cuda.current_stream(device).wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            plan['static_out'] = self._run_plan(plan, plan['static_in'])
-        plan['graph'] = g
-
-    def _forward(self, x: torch.Tensor) -> torch.Tensor:
-        plan = self._plan_for(x.shape, x.device)
-        fin = (lambda t: t.clone()) if self.clone_output else (lambda t: t)
-        if not (self.use_graph and x.is_cuda):
-            return fin(self._run_plan(plan, x))
-        own = plan['static_in'] is not None and x.data_ptr() == plan['static_in'].data_ptr()
-        if plan['graph'] is None:
-            if not own:
-                plan['static_in'] = torch.empty_like(x)
-                plan['static_in'].copy_(x)
-            self._capture(plan, x.device)
-        if not own:
-            plan['static_in'].copy_(x)
-        plan['graph'].replay()
-        return fin(plan['static_out'])
-
-    def forward(self, input: torch.Tensor) -> torch.Tensor:
-        self._exec.check(input)
-        x = input.contiguous()
+    def _check_input(self, x: torch.Tensor):
+        super()._check_input(x)
         if x.dtype != torch.float32:
             raise LamaError(f'GlobalGenerator: fp32 input expected, got {x.dtype}')
-        try:
-            with self._exec.range_scope(x, self.precision, deferred=self.defer_range_check):
-                return self._forward(x)
-        except LamaRangeError as e:
-            if not self.auto_fallback or self.precision != L.PREC_F16X3:
-                raise
-            warnings.warn(f'lama_amd: {e}; switching this generator to the 3-term bf16 split (PREC_BF16X3)')
-            self.set_precision(L.PREC_BF16X3)
-            return self.forward(input)
-
-    def check_range(self, device=None, reduce=None) -> bool:
-        """The other half of ``defer_range_check`` (see FFCResNetGenerator.check_range): True when every forward since the last check stayed
-        inside the fp16 split's range; otherwise the generator switches to the 3-term bf16 split (``auto_fallback``) and False is returned --
-        the caller re-runs those inputs -- or LamaRangeError is raised."""
-        bad = self._exec.range_flag_raised(device)
-        if reduce is not None:
-            bad = bool(reduce(bad))
-        if not bad:
-            return True
-        if not self.auto_fallback or self.precision != L.PREC_F16X3:
-            raise LamaRangeError(_RANGE_MSG)
-        warnings.warn(f'lama_amd: {_RANGE_MSG}; switching this generator to the 3-term bf16 split (PREC_BF16X3): re-run the inputs since the last check')
-        self.set_precision(L.PREC_BF16X3)
-        return False

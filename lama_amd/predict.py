@@ -19,6 +19,7 @@ writes the PNGs on a thread pool so file IO overlaps the next round's compute.
 """
 from __future__ import annotations
 
+import contextlib
 import glob
 import os
 import sys
@@ -402,6 +403,19 @@ def _write_png(path: str, rgb: np.ndarray):
 # one step fed from host memory
 # ----------------------------------------------------------------------------------------------------------------
 
+@contextlib.contextmanager
+def _settings(gen, **attrs):
+    """Set attributes of the generator for the duration of the block; they have their former values afterwards, a raise included."""
+    keep = {k: getattr(gen, k) for k in attrs}
+    for k, v in attrs.items():
+        setattr(gen, k, v)
+    try:
+        yield
+    finally:
+        for k, v in keep.items():
+            setattr(gen, k, v)
+
+
 class HostFedStep:
     """One predict step -- mask binarisation (bin/predict.py:84), mask-compose + generator + blend (trainers/default.py:56-71), u8 HWC
     quantisation (bin/predict.py:92) -- fed from / drained to pinned HOST buffers, double-buffered:
@@ -455,15 +469,10 @@ class HostFedStep:
             # captures and 18 replays (~0.35 s) buy at most 5 % of the bucket's time
             mode, self.one_part = ('host' if self.on_gpu else 'replay'), True
         if mode == 'auto':      # by measurement (table above): copy nodes overlap only in a graph that has parallel kernel branches already
-            gen = model.generator
-            split = 1
-            if hasattr(gen, '_split_parts'):
+            if self.on_gpu:
                 # (the generator verifies once per shape that this runtime runs the parts side by side: FFCResNetGenerator.verify_split)
-                keep_ag, gen._assume_graph = getattr(gen, '_assume_graph', False), True
-                try:
-                    split = gen.tune_split((self.n, 4, Hp, Wp), self.device) if self.on_gpu else 1
-                finally:
-                    gen._assume_graph = keep_ag
+                with _settings(model.generator, _assume_graph=True):
+                    model.generator.tune_split((self.n, 4, Hp, Wp), self.device)
             mode = 'host' if self.on_gpu else 'replay'       # round 6 (u8 copies): the host-synchronised copy streams beside whichever plan won, 0.999 of the resident rate (profiles/r06_host_fed.txt)
         self.mode = mode
         pin = dict(pin_memory=True) if self.on_gpu else {}
@@ -575,12 +584,16 @@ class HostFedStep:
         if self.drain:
             main.wait_stream(self.s_out)
 
+    def _generator(self, use_graph: bool):
+        """The generator's settings while a step is issued: no flag read-back per forward (``predict`` asks ``check_range`` per bucket), the
+        one-part plan where this step decided so."""
+        one_part = dict(split_batch=1) if self.one_part else {}
+        return _settings(self.model.generator, use_graph=use_graph, defer_range_check=True, **one_part)
+
     def _capture(self, p: int):
-        gen = self.model.generator
-        keep = (gen.use_graph, gen.defer_range_check, getattr(gen, '_assume_graph', False))
-        gen.use_graph, gen.defer_range_check = False, True       # the plan's launches go into THIS graph; no flag read-back (a host sync) inside it
-        gen._assume_graph = True                                 # ... so the plan may be the split one although generator.use_graph is off
-        try:
+        # the plan's launches go into THIS graph, with no flag read-back (a host sync) inside it; _assume_graph: so the plan may be the split
+        # one although generator.use_graph is off
+        with _settings(self.model.generator, use_graph=False, defer_range_check=True, _assume_graph=True):
             if self.graphs[1 - p] is None:                       # first capture: pack the weights / build the plan outside it
                 side = torch.cuda.Stream(device=self.device)
                 side.wait_stream(torch.cuda.current_stream(self.device))
@@ -592,8 +605,6 @@ class HostFedStep:
             with torch.cuda.graph(g, capture_error_mode='thread_local'):
                 self._body(p)
             self.graphs[p] = g
-        finally:
-            gen.use_graph, gen.defer_range_check, gen._assume_graph = keep
 
     # -- the caller's four verbs ----------------------------------------------------------------------------------
     def prime(self, p: int):
@@ -608,12 +619,8 @@ class HostFedStep:
 
     def launch(self, p: int):
         if not self.on_gpu:
-            gen = self.model.generator
-            keep, gen.defer_range_check = gen.defer_range_check, True
-            try:
+            with _settings(self.model.generator, defer_range_check=True):
                 self._body(p)
-            finally:
-                gen.defer_range_check = keep
             return
         if self.mode == 'host':
             # round 6: NO device-side fork / join between the queues.  The compute of this batch is queued first (behind nothing but the event of
@@ -623,12 +630,7 @@ class HostFedStep:
             # the cross-queue dependencies of the other forms cost more than that (profiles/r06_host_fed.txt).
             q = 1 - p
             main = torch.cuda.current_stream(self.device)
-            gen = self.model.generator
-            keep = (gen.use_graph, gen.defer_range_check, getattr(gen, 'split_batch', None))
-            gen.use_graph, gen.defer_range_check = True, True
-            if self.one_part:
-                gen.split_batch = 1
-            try:
+            with self._generator(use_graph=True):
                 if self._h2d_issued[p]:
                     main.wait_event(self.h2d[p])
                 if self.span_events is not None:       # profile=true: the step's span on the GPU clock
@@ -638,10 +640,6 @@ class HostFedStep:
                 if self.span_events is not None:
                     ev[1].record(main)
                     self.span_events.append(ev)
-            finally:
-                gen.use_graph, gen.defer_range_check = keep[:2]
-                if self.one_part:
-                    gen.split_batch = keep[2]
             self.done[p].record(main)
             if self._launched[q]:
                 self.done[q].synchronize()               # host: step k - 1 is complete (step k is queued behind it: the GPU does not idle)
@@ -663,17 +661,8 @@ class HostFedStep:
                 self._capture(p)
             self.graphs[p].replay()
         else:       # the two copies on streams of their own (fork / join by events) beside this batch's compute: the generator's own hipGraph
-            gen = self.model.generator          # replay ('replay') or its ~270 plain launches ('streams')
-            keep = (gen.use_graph, gen.defer_range_check, getattr(gen, 'split_batch', None))
-            gen.use_graph, gen.defer_range_check = self.mode == 'replay', True
-            if self.one_part:
-                gen.split_batch = 1
-            try:
+            with self._generator(use_graph=self.mode == 'replay'):          # replay ('replay') or its ~270 plain launches ('streams')
                 self._body(p)
-            finally:
-                gen.use_graph, gen.defer_range_check = keep[:2]
-                if self.one_part:
-                    gen.split_batch = keep[2]
         self.done[p].record(torch.cuda.current_stream(self.device))
         self._launched[p] = True
 
@@ -711,11 +700,8 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
     captured plan instead of building (and capturing) a second one, and a bucket's plan is dropped when the bucket is done."""
-    gen = model.generator
-    keep = gen.defer_range_check
     # no host synchronisation per forward: the fp16 split's range flag is read once per bucket, where every rank synchronises anyway
-    gen.defer_range_check = True
-    try:
+    with _settings(model.generator, defer_range_check=True):
         for _attempt in range(2):
             try:
                 return _predict_once(model, items, indir, outdir, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext, device=device,
@@ -723,8 +709,6 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
             except _RangeRestart:
                 continue                     # the generator switched to the 3-term bf16 split (every rank alike): all images again
         raise L.LamaError('range restart did not converge')
-    finally:
-        gen.defer_range_check = keep
 
 
 def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, device, rank, world, dist, io_threads, out_key='inpainted', scale_factor=None) -> int:

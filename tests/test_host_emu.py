@@ -70,6 +70,29 @@ def test_generator_fused_fft_path_and_layerwise(small):
     assert float((rear(front(x)) - ref).abs().max()) < 1e-4
 
 
+def test_plan_folds_batchnorm_without_activation_into_the_upsampling_launch():
+    """A ConvTranspose2dUp + BatchNorm2dEval with NO activation behind it (no shipped config; the plan builder shared with the regular
+    generator takes it): the plan folds the BatchNorm into the launch (bn, ACT_NONE) and computes what generator.model computes layer by
+    layer, where the ConvTranspose2d and the BatchNorm are two launches."""
+    cfg = O.small_config(ngf=8, n_blocks=1)
+    sd = O.make_synthetic_state_dict(cfg, seed=5, calib_hw=32)
+    gen = make_generator(None, kind='ffc_resnet', **cfg)
+    gen.load_state_dict(sd, strict=True)
+    layers = list(gen.model)
+    up = next(i for i, l in enumerate(layers) if isinstance(l, F.ConvTranspose2dUp))
+    assert isinstance(layers[up + 1], F.BatchNorm2dEval) and isinstance(layers[up + 2], F.Activation)
+    del layers[up + 2]
+    gen.model = F.LayerSequence(*layers)
+    gen.set_exec(F._Exec(emu_lib()))
+    batch = O.make_synthetic_batch(1, 32, 40, seed=4)
+    x = torch.cat([batch['image'] * (1 - batch['mask']), batch['mask']], 1)
+    y = gen(x)
+    step = next(s for s in next(iter(gen._plans.values()))['steps'] if s[0] == 'up')
+    assert step[4] is layers[up + 1] and step[5] == F.L.ACT_NONE
+    # (tolerance of test_regular_emu's plan-against-layerwise check: the fold rounds scale * w where the separate launch rounds w)
+    assert float((gen.model(x) - y).abs().max()) <= 1e-5
+
+
 def test_units_match_golden(golden_dir):
     g = np.load(os.path.join(golden_dir, 'ffc_units.npz'))
     ex = F._Exec(emu_lib())
