@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define LAMA_HIP_VERSION 111
+#define LAMA_HIP_VERSION 112
 
 #define LAMA_OK 0
 #define LAMA_ERR_BAD_ARG (-1)
@@ -179,6 +179,21 @@ int lama_fourier_unit_winograd_out_fwd(void* stream, const lama_tensor* x, const
                                        int32_t batch, int32_t add_input, int32_t precision, void* workspace, size_t workspace_bytes,
                                        uint32_t* range_flag, const lama_conv2d_args* wino_args, void* wino_workspace,
                                        size_t wino_workspace_bytes);
+
+/* (v112) Multi-dilated 3x3 reflect convolution in ONE launch:
+ *     y = act( sum_{j < groups} conv3x3(reflect_pad(x[:, j*Cin/groups : (j+1)*Cin/groups], d_j), w_j, dilation = d_j) + bias ) [+ resid],
+ *     d_j = min_dilation * 2^j.
+ * Replaces MultidilatedConv(comb_mode='cat_in', equal_dim=True), multidilated_conv.py:36-63,73-98 (the G dilated nn.Conv2d over the channel
+ * chunks of x and their sum), with the BatchNorm2d(eval) + ReLU behind it and the residual add of MultidilatedResnetBlock, pix2pixhd.py:155-175,
+ * in the epilogue -- four separate launches cannot do that: the ReLU would fall between partial sums.
+ *   args: read as for lama_conv2d_fwd with kh = kw = 3, stride = 1, pad_mode = LAMA_PAD_REFLECT (pad is implied: d_j per group), no x2, no
+ *     fuse1_*, fp32 tensors; anything else returns LAMA_ERR_UNSUPPORTED.  w_packed = lama_conv2d_pack_weight (stride 1) of the group weights
+ *     concatenated along Cin to [Cout, Cin, 3, 3]; bias = the sum of the group biases (folded with the BatchNorm).  resid may alias y.
+ *   groups in {1, 2, 4}, (Cin / groups) % 16 == 0, Cout % 32 == 0, min_dilation * 2^(groups-1) <= 8 on the split precisions.
+ *   Planes with H <= d_max or W <= d_max have no reflect padding (the reference raises there): LAMA_ERR_UNSUPPORTED.
+ *   precision: LAMA_PREC_F16X3 / BF16X3 (3-term split on v_mfma_f32_32x32x16_*; range_flag as lama_conv2d_fwd) or LAMA_PREC_F32 (an exact fmaf
+ *     chain per output, slow: the path errors are localised with). */
+int lama_multidilated_conv3x3_fwd(void* stream, const lama_conv2d_args* args, int32_t groups, int32_t min_dilation);
 
 /* torch.fft.rfftn(x, dim=(-2,-1), norm='ortho') followed by the Re/Im channel interleave
  * (ffc.py:86-89): x [B,C,h,w] -> spec [B,2C,h,w/2+1], channel 2c = Re, 2c+1 = Im. */

@@ -19,7 +19,7 @@ CONV_COOPERATIVE = 1
 CONV_DEFER_OUT = 2          # lama_winograd_conv3x3_fwd: the GEMM launch only (include/lama_hip.h)
 CONV_SIBLINGS_SHIFT = 8     # (v109) bits 8..10: log2 of the number of sibling launches that share the chip with this one
 DT_F32, DT_F16 = 0, 1
-ABI_VERSION = 111      # LAMA_HIP_VERSION of include/lama_hip.h
+ABI_VERSION = 112      # LAMA_HIP_VERSION of include/lama_hip.h
 PREC_NAMES = {'f32': PREC_F32, 'bf16x3': PREC_BF16X3, 'f16x3': PREC_F16X3, 'f16': PREC_F16}
 
 _DEFAULT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'lib', 'liblama_hip.so')
@@ -153,6 +153,7 @@ class LamaLib:
         L.lama_winograd_supported.restype, L.lama_winograd_supported.argtypes = i32, [i32, i32, i32, i32, i32]
         L.lama_winograd_preferred.restype, L.lama_winograd_preferred.argtypes = i32, [i32, i32, i32, i32, i32, i32]
         L.lama_winograd_conv3x3_fwd.restype, L.lama_winograd_conv3x3_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dArgs), vp, C.c_size_t]
+        L.lama_multidilated_conv3x3_fwd.restype, L.lama_multidilated_conv3x3_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dArgs), i32, i32]
         del dp
         if L.lama_version() != ABI_VERSION:
             raise LamaError(f'{path}: ABI version {L.lama_version()} != {ABI_VERSION}')
@@ -275,6 +276,23 @@ class LamaLib:
         a.flags = (CONV_DEFER_OUT if defer_out else 0) | (int(siblings_log2) << CONV_SIBLINGS_SHIFT)
         self.check(self._l.lama_winograd_conv3x3_fwd(stream, C.byref(a), ws.data_ptr(), ws.numel() * ws.element_size()), 'lama_winograd_conv3x3_fwd')
         return a if defer_out else None
+
+    def multidilated_conv3x3(self, x: Tensor4, w_packed: torch.Tensor, y: Tensor4, batch: int, groups: int, min_dilation: int = 1,
+                             bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, resid: Optional[Tensor4] = None,
+                             precision: int = PREC_F16X3, stream: int = 0, range_flag: Optional[torch.Tensor] = None):
+        """(v112) lama_multidilated_conv3x3_fwd: ``groups`` dilated 3x3 reflect convs (dilation min_dilation * 2^j) over the channel chunks of x,
+        summed, + bias, activation and residual in one launch.  ``w_packed``: ``pack_conv_weight`` of the group weights concatenated along Cin."""
+        a = Conv2dArgs()
+        a.x, a.w_packed = x, w_packed.data_ptr()
+        a.kh = a.kw = 3
+        a.stride, a.pad, a.pad_mode, a.transposed = 1, min_dilation, PAD_REFLECT, 0
+        a.bias = None if bias is None else bias.data_ptr()
+        a.act = act
+        if resid is not None:
+            a.resid = resid
+        a.y, a.batch, a.precision = y, batch, precision
+        a.range_flag = None if range_flag is None else range_flag.data_ptr()
+        self.check(self._l.lama_multidilated_conv3x3_fwd(stream, C.byref(a), groups, min_dilation), 'lama_multidilated_conv3x3_fwd')
 
     def winograd_out(self, args: 'Conv2dArgs', ws: torch.Tensor, stream: int = 0):
         """The output transform a ``winograd_conv3x3(..., defer_out=True)`` call left out (lama_winograd_out_fwd)."""

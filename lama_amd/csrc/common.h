@@ -175,4 +175,7 @@ LAMA_CB_DECL(_f16)
 LAMA_WG_DECL(_bf16x3)
 LAMA_WG_DECL(_f16x3)
 #undef LAMA_WG_DECL
+// multi-dilated 3x3 reflect convolution (mdconv_dev.inc), reached through lama_multidilated_conv3x3_fwd with LAMA_PREC_BF16X3 / F16X3
+int lama_cb_mdconv_fwd_bf16x3(hipStream_t stream, const lama_conv2d_args* a, int groups, int min_dilation);
+int lama_cb_mdconv_fwd_f16x3(hipStream_t stream, const lama_conv2d_args* a, int groups, int min_dilation);
 int lama_wino_out_params(const lama_conv2d_args* a, void* workspace, size_t workspace_bytes, void* out);   // conv_mfma.hip -> fft.hip

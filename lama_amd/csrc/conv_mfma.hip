@@ -543,6 +543,100 @@ extern "C" int lama_winograd_out_fwd(void* stream, const lama_conv2d_args* a, vo
     return lama_cb_wino_out_fwd_f16x3((hipStream_t)stream, a, workspace, workspace_bytes);
 }
 
+// ---- multi-dilated 3x3 reflect convolution (MultidilatedConv comb_mode='cat_in', multidilated_conv.py:36-63,73-98) ------------------------
+// LAMA_PREC_F32: the exact form, one fmaf chain per output (speed is not its purpose: it is the path errors are localised with).  One thread =
+// one pixel x 16 output channels; the weights are the lama_conv2d_pack_weight image [chunk of 8 channels][tap][8][Mpad] of the group weights
+// concatenated along Cin, read as wave-uniform rows.  The split precisions run mdconv_dev.inc.
+struct MdF32Params {
+    const float* x;
+    long long x_bstride;
+    int C, H, W;
+    const float* w;
+    int Mpad;
+    const float* bias;
+    const float* resid;
+    long long resid_bstride;
+    float* y;
+    long long y_bstride;
+    int M, gch, dmin, act;   // gch: channels per dilation group
+};
+
+__global__ __launch_bounds__(LAMA_NTHREADS) void mdconv_f32_kernel(MdF32Params p) {
+    const int HW = p.H * p.W;
+    const int pix = blockIdx.x * LAMA_NTHREADS + threadIdx.x;
+    const int m0 = blockIdx.y * 16, b = blockIdx.z;
+    if (pix >= HW) return;
+    const int gy = pix / p.W, gx = pix - gy * p.W;
+    const float* xb = p.x + (long long)b * p.x_bstride;
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
+    for (int c = 0; c < p.C; ++c) {
+        const int d = p.dmin << (c / p.gch);
+        const float* xc = xb + (long long)c * HW;
+        const float* wc = p.w + ((long long)(c >> 3) * 72 + (c & 7)) * p.Mpad + m0;
+        for (int ky = 0; ky < 3; ++ky) {
+            const int iy = conv_src_coord(gy + (ky - 1) * d, p.H, LAMA_PAD_REFLECT);
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ix = conv_src_coord(gx + (kx - 1) * d, p.W, LAMA_PAD_REFLECT);
+                const float v = xc[iy * p.W + ix];
+                const float* wt = wc + (long long)((ky * 3 + kx) * 8) * p.Mpad;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) acc[j] = fmaf(wt[j], v, acc[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int m = m0 + j;
+        float v = acc[j];
+        if (p.bias) v += p.bias[m];
+        if (p.act == LAMA_ACT_RELU) v = fmaxf(v, 0.0f);
+        else if (p.act == LAMA_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
+        else if (p.act == LAMA_ACT_TANH) v = tanhf(v);
+        const long long o = (long long)m * HW + pix;
+        if (p.resid) v += p.resid[(long long)b * p.resid_bstride + o];   // resid may be y: read before written, by the thread that writes it
+        p.y[(long long)b * p.y_bstride + o] = v;
+    }
+}
+
+extern "C" int lama_multidilated_conv3x3_fwd(void* stream, const lama_conv2d_args* a, int32_t groups, int32_t min_dilation) {
+    if (!a || !tensor_ok(a->x) || !tensor_ok(a->y) || !a->w_packed || a->batch <= 0) return LAMA_ERR_BAD_ARG;
+    if ((groups != 1 && groups != 2 && groups != 4) || min_dilation < 1 || min_dilation > 8) return LAMA_ERR_UNSUPPORTED;
+    if (a->kh != 3 || a->kw != 3 || a->stride != 1 || a->pad_mode != LAMA_PAD_REFLECT || a->transposed) return LAMA_ERR_UNSUPPORTED;
+    if (a->x2.ptr || a->fuse1_w) return LAMA_ERR_UNSUPPORTED;
+    if (a->x.dtype != LAMA_DT_F32 || a->y.dtype != LAMA_DT_F32 || (a->resid.ptr && a->resid.dtype != LAMA_DT_F32)) return LAMA_ERR_UNSUPPORTED;
+    if (a->x.H != a->y.H || a->x.W != a->y.W) return LAMA_ERR_BAD_ARG;
+    if (a->resid.ptr && (a->resid.C != a->y.C || a->resid.H != a->y.H || a->resid.W != a->y.W)) return LAMA_ERR_BAD_ARG;
+    const int cout = a->y.C, cin = a->x.C, H = a->x.H, W = a->x.W;
+    if (cin % (16 * groups) != 0 || cout % 32 != 0) return LAMA_ERR_UNSUPPORTED;
+    const int dmax = min_dilation << (groups - 1);
+    if (H <= dmax || W <= dmax) return LAMA_ERR_UNSUPPORTED;      // no reflect padding of dmax on such a plane (the reference raises too)
+    if (a->precision == LAMA_PREC_BF16X3) return lama_cb_mdconv_fwd_bf16x3((hipStream_t)stream, a, groups, min_dilation);
+    if (a->precision == LAMA_PREC_F16X3) return lama_cb_mdconv_fwd_f16x3((hipStream_t)stream, a, groups, min_dilation);
+    if (a->precision != LAMA_PREC_F32) return LAMA_ERR_UNSUPPORTED;
+    if ((long long)cin * H * W >= (1ll << 31) || cout / 16 > 65535 || a->batch > 65535) return LAMA_ERR_UNSUPPORTED;
+    MdF32Params p;
+    memset(&p, 0, sizeof(p));
+    p.x = (const float*)a->x.ptr;
+    p.x_bstride = a->x.batch_stride;
+    p.C = cin; p.H = H; p.W = W;
+    p.w = (const float*)a->w_packed;
+    p.Mpad = lama_round_up(cout, pick_bm(cout));
+    p.bias = a->bias;
+    p.resid = (const float*)a->resid.ptr;
+    p.resid_bstride = a->resid.batch_stride;
+    p.y = (float*)a->y.ptr;
+    p.y_bstride = a->y.batch_stride;
+    p.M = cout;
+    p.gch = cin / groups;
+    p.dmin = min_dilation;
+    p.act = a->act;
+    hipLaunchKernelGGL(mdconv_f32_kernel, dim3(lama_ceil_div(H * W, LAMA_NTHREADS), cout / 16, a->batch), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
 extern "C" void lama_fuse1_channel_order(int32_t* order) {
     for (int kq = 0; kq < 24; ++kq)
         for (int kh = 0; kh < 2; ++kh)

@@ -744,6 +744,7 @@ __global__ void CB_NAME(conv_pack_kernel)(CbPackParams p) {
 #if !CB_HALF
 #include "wino_dev.inc"
 #include "convt_dev.inc"
+#include "mdconv_dev.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1165,6 +1166,48 @@ int CB_NAME(lama_cb_conv2d_fwd)(hipStream_t stream, const lama_conv2d_args* a, i
     }
     return LAMA_OK;
 }
+
+#if !CB_HALF
+// Multi-dilated 3x3 reflect convolution (mdconv_dev.inc); arguments were validated by lama_multidilated_conv3x3_fwd (conv_mfma.hip):
+// w_packed is the lama_conv2d_pack_weight image of the group weights concatenated along Cin
+int CB_NAME(lama_cb_mdconv_fwd)(hipStream_t stream, const lama_conv2d_args* a, int groups, int min_dilation) {
+    const int cout = a->y.C, cin = a->x.C, H = a->x.H, W = a->x.W;
+    const int dmax = min_dilation << (groups - 1);
+    if (dmax > MD_MAX_DIL || cout % 32 != 0 || cin % (16 * groups) != 0) return LAMA_ERR_UNSUPPORTED;
+    if ((long long)cin * H * W >= (1ll << 31) || (long long)cout * H * W >= (1ll << 31)) return LAMA_ERR_UNSUPPORTED;   // 32-bit element offsets inside one image
+    MdParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = (const float*)a->x.ptr;
+    p.x_bstride = a->x.batch_stride;
+    p.C = cin; p.H = H; p.W = W;
+    p.w = (const char*)a->w_packed;
+    p.mft = cout / 32;
+    p.bias = a->bias;
+    p.resid = (const float*)a->resid.ptr;
+    p.resid_bstride = a->resid.batch_stride;
+    p.y = (float*)a->y.ptr;
+    p.y_bstride = a->y.batch_stride;
+    p.M = cout;
+    p.MT = lama_ceil_div(cout, 128);
+    p.B = a->batch;
+    p.TWlog = W <= 8 ? 3 : 4;      // the squarer tile: 8 rows x 16 columns (the halo of d = 8 costs 24 x 32 patch pixels; 4 x 32 would cost 20 x 48)
+    const int TW = 1 << p.TWlog, TH = 128 >> p.TWlog;
+    p.tiles_x = lama_ceil_div(W, TW);
+    p.tiles_y = lama_ceil_div(H, TH);
+    p.act = a->act;
+    p.gchunks = cin / groups / 16;
+    p.dmin = min_dilation;
+    p.pbytes = 2 * 2 * (TH + 2 * dmax) * (TW + 2 * dmax) * 16;
+    p.range_flag = a->range_flag;
+    const size_t shmem = 2 * (size_t)MD_WBYTES + 2 * (size_t)p.pbytes;
+    if (shmem > 160 * 1024) return LAMA_ERR_UNSUPPORTED;
+    const long long grid = (long long)p.B * p.tiles_x * p.tiles_y * p.MT;
+    if (grid <= 0 || grid >= (1ll << 31)) return grid <= 0 ? LAMA_OK : LAMA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(CB_NAME(mdconv_kernel), dim3((unsigned)grid), dim3(MD_THREADS), shmem, stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // Winograd F(2x2, 3x3) form of the stride-1 3x3 reflect convolution (wino_dev.inc): pack + two launches

@@ -234,6 +234,10 @@ class _Exec:
         flag = self._cur_flag if precision in (L.PREC_F16X3, L.PREC_F16) else None
         self.lib.fourier_unit(*a, precision=precision, stream=stream, range_flag=flag, wino_out=wino_out, siblings_log2=self.siblings_log2)
 
+    def multidilated_conv3x3(self, *a, precision: int = L.PREC_F16X3, **kw):
+        flag = self._cur_flag if precision == L.PREC_F16X3 else None
+        self.lib.multidilated_conv3x3(*a, precision=precision, range_flag=flag, **kw)
+
     def winograd_conv3x3(self, *a, precision: int = L.PREC_F16X3, **kw):
         flag = self._cur_flag if precision == L.PREC_F16X3 else None
         if self.siblings_log2:

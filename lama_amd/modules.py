@@ -2,7 +2,7 @@
 import logging
 
 from .ffc import FFCResNetGenerator
-from .pix2pixhd import GlobalGenerator
+from .pix2pixhd import GlobalGenerator, MultiDilatedGlobalGenerator
 
 
 def make_generator(config, kind, **kwargs):
@@ -12,5 +12,5 @@ def make_generator(config, kind, **kwargs):
     if kind == 'pix2pixhd_global':
         return GlobalGenerator(**kwargs)
     if kind == 'pix2pixhd_multidilated':
-        raise NotImplementedError(f'generator kind {kind} is outside the FFC hot path this package accelerates')
+        return MultiDilatedGlobalGenerator(**kwargs)
     raise ValueError(f'Unknown generator kind {kind}')

@@ -1,6 +1,7 @@
 """Host-side mirror of ``GlobalGenerator`` / ``ResnetBlock`` of ``saicinpainting/training/modules/pix2pixhd.py`` (the
-``pix2pixhd_global`` generator kind of the big-lama-regular and lama-regular checkpoints) whose forward runs on the gfx950 kernels
-of liblama_hip.so.
+``pix2pixhd_global`` generator kind of the big-lama-regular and lama-regular checkpoints) and of ``MultiDilatedGlobalGenerator`` /
+``MultidilatedResnetBlock`` / ``MultidilatedConv`` (the ``pix2pixhd_multidilated`` kind of the lama-dilated checkpoint) whose forward runs on
+the gfx950 kernels of liblama_hip.so.
 
 Same class names, constructor signatures, sub-module names and therefore ``state_dict`` keys as the reference
 (``generator.model.13.conv_block.1.weight`` ...).  As in ``lama_amd.ffc``, the ``nn.Conv2d`` / ``nn.BatchNorm2d`` /
@@ -12,6 +13,7 @@ paddings, ``affine``, dilation) raise ``NotImplementedError`` at construction.
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Optional
 
 import torch
@@ -150,6 +152,113 @@ class ResnetBlock(_HipModule):
         return dst
 
 
+class MultidilatedConv(_HipModule):
+    """multidilated_conv.py:7-98 with ``comb_mode='cat_in'``: the input channels are cut into ``dilation_num`` equal chunks, chunk j goes through
+    its own 3x3 conv to ALL output channels with dilation ``2^j`` and reflect padding ``2^j``, and the results are summed.  ``convs`` holds the
+    reference's ``nn.Conv2d`` objects as parameter containers (keys ``convs.{j}.weight|bias``); the forward is ONE launch of
+    ``lama_multidilated_conv3x3_fwd`` over the weights concatenated along Cin, with the BatchNorm behind it, the activation and the residual
+    in its epilogue.  Every other option of the reference raises ``NotImplementedError``."""
+
+    def __init__(self, in_dim, out_dim, kernel_size, dilation_num=3, comb_mode='sum', equal_dim=True, shared_weights=False, padding=1,
+                 min_dilation=1, shuffle_in_channels=False, use_depthwise=False, **kwargs):
+        super().__init__()
+        if comb_mode not in ('cat_out', 'sum', 'cat_in', 'cat_both'):
+            raise ValueError(f'MultidilatedConv: unknown comb_mode {comb_mode!r}')
+        if comb_mode != 'cat_in':
+            raise NotImplementedError(f'MultidilatedConv: comb_mode {comb_mode!r} (only cat_in, the published lama-dilated config, is implemented)')
+        if not equal_dim or shared_weights or shuffle_in_channels or use_depthwise:
+            raise NotImplementedError('MultidilatedConv: equal_dim=False / shared_weights / shuffle_in_channels / use_depthwise are not implemented')
+        if min_dilation != 1 or padding != 1:
+            raise NotImplementedError('MultidilatedConv: only min_dilation = 1 and padding = 1 (the defaults) are implemented')
+        if kernel_size not in (3, (3, 3)):
+            raise NotImplementedError('MultidilatedConv: only 3x3 kernels')
+        if kwargs.pop('padding_mode', 'reflect') != 'reflect':
+            raise NotImplementedError('MultidilatedConv: only reflect padding')
+        if kwargs:
+            raise NotImplementedError(f'MultidilatedConv: conv options {sorted(kwargs)} are not implemented')
+        if dilation_num not in (1, 2, 4) or in_dim % (16 * dilation_num) or out_dim % 32:
+            raise NotImplementedError('MultidilatedConv: dilation_num in {1, 2, 4}, (in_dim / dilation_num) % 16 == 0 and out_dim % 32 == 0 '
+                                      f'are what lama_multidilated_conv3x3_fwd takes (got {dilation_num}, {in_dim}, {out_dim})')
+        self.equal_dim, self.cat_in, self.cat_out = True, True, False
+        self.in_dims, self.out_dims = [in_dim // dilation_num] * dilation_num, [out_dim] * dilation_num
+        self.in_channels, self.out_channels, self.min_dilation = in_dim, out_dim, min_dilation
+        self.convs = nn.ModuleList([nn.Conv2d(in_dim // dilation_num, out_dim, 3, padding=min_dilation * 2 ** j, dilation=min_dilation * 2 ** j,
+                                              padding_mode='reflect') for j in range(dilation_num)])
+        self.shuffle_in_channels = False
+
+    @property
+    def max_dilation(self) -> int:
+        return self.min_dilation * 2 ** (len(self.convs) - 1)
+
+    def pack(self, bn: Optional[nn.BatchNorm2d]) -> dict:
+        key = (id(bn), self.precision)
+        if self._packed is None or self._packed['key'] != key:
+            w = torch.cat([c.weight.detach().float() for c in self.convs], dim=1)       # [Cout, Cin, 3, 3]: chunk j of Cin is group j
+            b = torch.stack([c.bias.detach().float() for c in self.convs]).sum(0)
+            if bn is not None:
+                scale, shift = _bn_fold(bn)
+                bias = shift + scale * b
+            else:
+                scale, bias = None, b
+            self._packed = dict(key=key, b=bias.contiguous(), w=self._exec.lib.pack_conv_weight(w, scale, stride=1, precision=self.precision))
+        return self._packed
+
+    def run(self, src: torch.Tensor, dst: torch.Tensor, bn: Optional[nn.BatchNorm2d] = None, act: int = L.ACT_NONE,
+            resid: Optional[torch.Tensor] = None):
+        """src -> dst = act(bn(sum_j conv_j(pad(src_j)))) [+ resid]; ``resid`` may be ``dst`` itself (as Conv2dBN.run)."""
+        if min(src.shape[2], src.shape[3]) <= self.max_dilation:
+            raise LamaError(f'MultidilatedConv: a {src.shape[2]} x {src.shape[3]} plane has no reflect padding of {self.max_dilation} '
+                            f'(each side must exceed the largest dilation)', code=L.ERR_UNSUPPORTED)
+        ex = self._exec
+        pk = self.pack(bn)
+        ex.multidilated_conv3x3(L.view(src), pk['w'], L.view(dst), src.shape[0], len(self.convs), self.min_dilation, bias=pk['b'], act=act,
+                                resid=None if resid is None else L.view(resid), precision=self.precision, stream=ex.stream(src))
+
+    def forward(self, x):
+        self._exec.check(x)
+        x = x.contiguous()
+        y = torch.empty((x.shape[0], self.out_channels) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+        with self._exec.range_scope(x, self.precision):
+            self.run(x, y)
+        return y
+
+
+class MultidilatedResnetBlock(_HipModule):
+    """pix2pixhd.py:155-175: x + BN(mdconv(ReLU(BN(mdconv(x))))) -- ``conv_block`` = [conv, BN, ReLU, conv, BN] (the padding lives in the convs),
+    two launches like ``ResnetBlock``; there is no Winograd form of a dilated conv, so both always take the multi-dilated kernel."""
+
+    def __init__(self, dim, padding_type, conv_layer, norm_layer, activation=nn.ReLU(True), use_dropout=False):
+        super().__init__()
+        if padding_type != 'reflect':
+            raise NotImplementedError(f'MultidilatedResnetBlock: padding {padding_type!r} (only reflect)')
+        if not _is_bn(norm_layer):
+            raise NotImplementedError('MultidilatedResnetBlock: only BatchNorm2d (eval) is folded into the kernels')
+        if use_dropout or not _is_relu(activation):
+            raise NotImplementedError('MultidilatedResnetBlock: dropout / activations other than ReLU are not implemented')
+        self.dim = dim
+        self.conv_block = LayerSequence(conv_layer(dim, dim, kernel_size=3, padding_mode=padding_type), BatchNorm2dEval(dim), Activation('relu'),
+                                        conv_layer(dim, dim, kernel_size=3, padding_mode=padding_type), BatchNorm2dEval(dim))
+
+    def convs(self):
+        cb = self.conv_block
+        return (cb[0], cb[1]), (cb[3], cb[4])
+
+    def run(self, src: torch.Tensor, t: torch.Tensor, dst: torch.Tensor, wino_ws: Optional[torch.Tensor] = None) -> tuple:
+        """As ``ResnetBlock.run`` (``dst`` may be ``src``); ``wino_ws`` is ignored.  Returns the path of the two launches."""
+        (ca, bna), (cb, bnb) = self.convs()
+        ca.run(src, t, bna, L.ACT_RELU)
+        cb.run(t, dst, bnb, L.ACT_NONE, resid=src)
+        return 'multidilated', 'multidilated'
+
+    def forward(self, x):
+        self._exec.check(x)
+        x = x.contiguous()
+        t, dst = torch.empty_like(x, dtype=torch.float32), torch.empty_like(x, dtype=torch.float32)
+        with self._exec.range_scope(x, self.precision):
+            self.run(x, t, dst)
+        return dst
+
+
 class GlobalGenerator(_PlanGenerator):
     """pix2pixhd.py:341-436.  ``forward(x[B,input_nc,H,W]) -> [B,output_nc,H,W]``; ``.model`` has the reference's layout
     (stem 0-3, downsampling 4-12, ``n_blocks`` ResnetBlocks, 3 x (ConvTranspose2d, BN, ReLU), pad + 7x7 conv, output activation).
@@ -254,7 +363,7 @@ class GlobalGenerator(_PlanGenerator):
                 steps.append(('conv', lay, cur, dst, bn, _ACT[act.kind] if act else L.ACT_NONE, pad, mode))
                 cur, cur_shape, pad_pending = dst, shp, 0
                 i += 1 + (bn is not None) + (act is not None)
-            elif isinstance(lay, ResnetBlock):
+            elif isinstance(lay, (ResnetBlock, MultidilatedResnetBlock)):
                 if 'st' not in bufs:
                     if cur == 'in':                   # (a generator without a stem / downsampling: the input is not overwritten)
                         bufs['st'] = torch.empty(cur_shape, device=device, dtype=torch.float32)
@@ -281,7 +390,7 @@ class GlobalGenerator(_PlanGenerator):
         # the 512 -> 512 convs of the blocks: Winograd where the library expects it to beat the direct kernel at this shape and every block
         # conv has its transformed weights (one workspace serves every launch: they run one after the other on one stream)
         ws = None
-        blocks = [s[1] for s in steps if s[0] == 'res']
+        blocks = [s[1] for s in steps if s[0] == 'res' and isinstance(s[1], ResnetBlock)]
         if blocks and self._exec.winograd and self.precision in (L.PREC_F16X3, L.PREC_BF16X3):
             B, C, H, W = bufs['st'].shape
             lib = self._exec.lib
@@ -304,11 +413,11 @@ class GlobalGenerator(_PlanGenerator):
                 B(st[2]).copy_(B(st[1]))
             else:                                   # 'conv', 'up', 'out'
                 _run_step(st, B)
-        plan['paths'] = ['winograd' if w else 'direct' for w in paths]   # per bottleneck launch, in launch order
+        plan['paths'] = [w if isinstance(w, str) else ('winograd' if w else 'direct') for w in paths]   # per bottleneck launch, in launch order
         return bufs[plan['out']]
 
     def conv_paths(self, shape, device) -> Optional[List[str]]:
-        """'winograd' / 'direct' for each bottleneck launch of this shape's plan, in launch order (None before its first forward)."""
+        """'winograd' / 'direct' ('multidilated' in MultiDilatedGlobalGenerator) for each bottleneck launch of this shape's plan, in launch order (None before its first forward)."""
         plan = self._plans.get(self._plan_key(shape, device))
         return None if plan is None else plan['paths']
 
@@ -316,3 +425,42 @@ class GlobalGenerator(_PlanGenerator):
         super()._check_input(x)
         if x.dtype != torch.float32:
             raise LamaError(f'GlobalGenerator: fp32 input expected, got {x.dtype}')
+
+
+class MultiDilatedGlobalGenerator(GlobalGenerator):
+    """pix2pixhd.py:178-237 (the ``pix2pixhd_multidilated`` generator kind of the lama-dilated checkpoint): ``GlobalGenerator``'s stem, downsampling,
+    ``ConvTranspose2d`` upsampling and head around ``n_blocks`` ``MultidilatedResnetBlock``s.  The plan builder and runner, the plan cache, graph
+    replay and the range fallback are ``GlobalGenerator``'s; every bottleneck launch reports the path 'multidilated'.  An input must be larger
+    than ``2^n_downsampling`` times the largest dilation on each side (72 pixels for the shipped config): the reference's reflect padding
+    raises below that, and so does this class (``LamaError``)."""
+
+    def __init__(self, input_nc, output_nc, ngf=64, n_downsampling=3, n_blocks=3, norm_layer=nn.BatchNorm2d, padding_type='reflect',
+                 conv_kind='default', deconv_kind='convtranspose', activation=nn.ReLU(True), up_norm_layer=nn.BatchNorm2d, affine=None,
+                 up_activation=nn.ReLU(True), add_out_act=True, max_features=1024, multidilation_kwargs={}, ffc_positions=None, ffc_kwargs={}):
+        if deconv_kind != 'convtranspose':
+            raise NotImplementedError(f'MultiDilatedGlobalGenerator: deconv_kind {deconv_kind!r} (only convtranspose)')
+        # everything but the blocks is GlobalGenerator's (which refuses ffc_positions, affine, other norms / paddings / activations)
+        super().__init__(input_nc, output_nc, ngf=ngf, n_downsampling=n_downsampling, n_blocks=0, norm_layer=norm_layer, padding_type=padding_type,
+                         conv_kind=conv_kind, activation=activation, up_norm_layer=up_norm_layer, affine=affine, up_activation=up_activation,
+                         add_out_act=add_out_act, max_features=max_features, ffc_positions=ffc_positions)
+        dim = min(max_features, ngf * 2 ** n_downsampling)
+        conv_layer = functools.partial(MultidilatedConv, **dict(multidilation_kwargs))
+        blocks = [MultidilatedResnetBlock(dim, padding_type=padding_type, conv_layer=conv_layer, activation=activation, norm_layer=norm_layer)
+                  for _ in range(n_blocks)]
+        layers = list(self.model)
+        at = 4 + 3 * n_downsampling
+        self.model = LayerSequence(*(layers[:at] + blocks + layers[at:]))
+        self.max_dilation = max([1] + [c.max_dilation for b in blocks for c, _ in b.convs()])
+        super().train(False)
+
+    @property
+    def min_input_side(self) -> int:
+        """The smallest input side whose bottleneck plane still has the reflect padding of the largest dilation."""
+        return (self.max_dilation + 1) << self.n_downsampling
+
+    def _check_input(self, x: torch.Tensor):
+        super()._check_input(x)
+        if min(x.shape[2], x.shape[3]) < self.min_input_side:
+            raise LamaError(f'MultiDilatedGlobalGenerator: input {x.shape[2]} x {x.shape[3]} is too small: the bottleneck plane must exceed the '
+                            f'largest dilation ({self.max_dilation}) for its reflect padding; the minimum input side is {self.min_input_side}',
+                            code=L.ERR_UNSUPPORTED)
