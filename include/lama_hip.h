@@ -257,6 +257,30 @@ int lama_mask_compose_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8
 int lama_blend_quantize_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* sizes, const lama_tensor* pred,
                                uint8_t* dst_hwc, int32_t batch, int32_t binarize);
 
+/* (added to v112 without a version bump: one new symbol, nothing else changes) dataset.scale_factor inside the u8 predict step: the loader's whole
+ * chain for a batch of DECODED images in one launch, so that a scaled run uploads 4 bytes per SOURCE pixel and the host only decodes.
+ *   image_hwc u8 [B][Hs][Ws][3] + mask u8 [B][Hs][Ws] (device pointers): source slots, each image's own h x w pixels in the top-left corner;
+ *   src_sizes int32 [B][2] = (h, w) on the device (h = 0: an empty slot of a partial batch -> zeros);
+ *   dst_sizes int32 [B][2] = the size cv::resize(dsize=None, fx, fy) gives that image, saturate_cast<int>(size * factor) (round half to even),
+ *     computed by the host;  factor = dataset.scale_factor.
+ * Per image the kernel does what InpaintingDataset.__getitem__ does on the host:
+ *   image.astype('float32') / 255 (evaluation/data.py:12-20: the same IEEE fp32 division as lama_mask_compose_u8_fwd),
+ *   scale_image = cv2.resize(fx = fy = factor) with INTER_AREA on the image and INTER_NEAREST on the mask (data.py:42-55,74-77) -- the three
+ *     regimes of INTER_AREA (integer shrink: resizeAreaFast's sums of four and its border loop; fractional shrink: computeResizeAreaTab's taps,
+ *     x pass then y pass; enlarging: the linear path with area coefficients), tap indices and weights computed in fp64 from the destination
+ *     index, 1.0 / factor and the image's own size and rounded to fp32 where OpenCV rounds them,
+ *   pad_img_to_modulo's symmetric padding of the SCALED dh x dw result up to (Hp, Wp) = the views' H x W (data.py:29-33; np.pad mode='symmetric'
+ *     is periodic: the padding may exceed the scaled side),
+ *   mask > 0 (bin/predict.py:84; binarize == 0: the mask stays mask / 255).
+ * out_image [B,3,Hp,Wp], out_mask [B,1,Hp,Wp] fp32: what lama_mask_compose_fwd / lama_blend_fwd take.  Bit-identical to lama_amd.predict's
+ * host restatement of resize.cpp (scale_image + pad_img_to_modulo): no floating-point contraction anywhere in the kernel.
+ * LAMA_ERR_BAD_ARG: a null pointer, factor <= 0 (or not finite), views that are not [.,3,Hp,Wp] / [.,1,Hp,Wp] of one size; LAMA_ERR_UNSUPPORTED:
+ * views that are not fp32.  The per-image sizes live on the device, where the host cannot read them without a synchronisation: an image whose
+ * source size exceeds its slot or whose destination size exceeds the output view is written as zeros, like an empty slot -- nothing is read or
+ * written out of bounds (lama_amd.predict.HostFedStep.put refuses such an image on the host, where the sizes are known). */
+int lama_resize_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes, int32_t Hs,
+                       int32_t Ws, double factor, const lama_tensor* out_image, const lama_tensor* out_mask, int32_t batch, int32_t binarize);
+
 /* Stand-alone per-channel affine + activation: y = act(x*scale[c] + shift[c]) (scale/shift NULL = identity).
  * Used when a caller runs generator.model layer by layer and hits a bare nn.BatchNorm2d (eval) /
  * nn.ReLU / nn.Sigmoid (ffc.py:352-354,362-363); the fused forward never launches it. */

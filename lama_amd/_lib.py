@@ -124,6 +124,8 @@ class LamaLib:
         L.lama_mask_compose_u8_fwd.argtypes = [vp, vp, vp, vp, T, i32, i32]
         L.lama_blend_quantize_u8_fwd.restype = C.c_int
         L.lama_blend_quantize_u8_fwd.argtypes = [vp, vp, vp, vp, T, vp, i32, i32]
+        L.lama_resize_u8_fwd.restype = C.c_int
+        L.lama_resize_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, T, T, i32, i32]
         L.lama_affine_act_fwd.restype = C.c_int
         L.lama_affine_act_fwd.argtypes = [vp, T, vp, vp, i32, T, i32]
         L.lama_reflect_pad_fwd.restype = C.c_int
@@ -385,6 +387,22 @@ class LamaLib:
         """(v110) blend (default.py:71) + u8 HWC quantisation (bin/predict.py:86-92) of the generator's output against the u8 operands."""
         self.check(self._l.lama_blend_quantize_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), None if sizes is None else sizes.data_ptr(),
                                                       C.byref(pred), dst.data_ptr(), batch, int(bool(binarize))), 'lama_blend_quantize_u8_fwd')
+
+    def resize_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, dst_sizes: torch.Tensor, factor: float,
+                  out_image: Tensor4, out_mask: Tensor4, batch: int, binarize: bool = True, stream: int = 0):
+        """lama_resize_u8_fwd: dataset.scale_factor on the device.  u8 HWC source slots [B,Hs,Ws,3] + u8 mask slots [B,Hs,Ws], int32 (h, w) per
+        image of the source and of the scaled result [B,2] -> the loader's fp32 image [B,3,Hp,Wp] / mask [B,1,Hp,Wp] (/ 255, INTER_AREA /
+        INTER_NEAREST, symmetric padding, mask > 0), bit-identical to ``predict.load_item``."""
+        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
+            raise LamaError(f'resize_u8: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
+        for t, dt in ((image_hwc, torch.uint8), (mask, torch.uint8), (src_sizes, torch.int32), (dst_sizes, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise LamaError(f'resize_u8: a contiguous {dt} tensor is needed, got {t.dtype}')
+        if src_sizes.numel() < 2 * batch or dst_sizes.numel() < 2 * batch:
+            raise LamaError('resize_u8: src_sizes / dst_sizes are [B,2] int32')
+        self.check(self._l.lama_resize_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
+                                              int(image_hwc.shape[1]), int(image_hwc.shape[2]), float(factor), C.byref(out_image), C.byref(out_mask),
+                                              batch, int(bool(binarize))), 'lama_resize_u8_fwd')
 
     def quantize_u8_hwc(self, src: Tensor4, dst: torch.Tensor, batch: int, crop_h: int, crop_w: int, stream: int = 0):
         self.check(self._l.lama_quantize_u8_hwc_fwd(stream, C.byref(src), dst.data_ptr(), batch, crop_h, crop_w), 'lama_quantize_u8_hwc_fwd')

@@ -142,6 +142,195 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void blend_quantize_u8_kernel(U8Para
     }
 }
 
+// ---- dataset.scale_factor on the device: the loader's chain for one batch of DECODED u8 images in one launch --
+//   image.astype('float32') / 255 (evaluation/data.py:12-20), cv2.resize(fx = fy = factor) with INTER_AREA on the image and INTER_NEAREST on the
+//   mask (data.py:42-55,74-77), pad_img_to_modulo's symmetric padding of the SCALED result (data.py:29-33), mask > 0 (bin/predict.py:84).
+// The resize is lama_amd/predict.py's restatement of OpenCV's resize.cpp (_resize_area, _area_taps, _resize_nearest) and the contract is
+// BIT-IDENTITY with it: the same IEEE operations in the same order.  Tap indices and weights are computed per output pixel in fp64 from the
+// destination index, scale = 1.0 / factor and the image's OWN size (the images of one batch differ in size: no table can be precomputed), and
+// rounded to fp32 where the Python rounds them.  Every function below switches floating-point contraction OFF (device and host compiler alike):
+// buf + a * w must stay a multiply and an add, f1 + scale must not fuse with the multiply that made f1.
+// Two simplifications that change no bit: sums start from +0 instead of from their first term (every term is non-negative and finite, +0 + x = x),
+// and the zero-weight padding taps of the host's tables are not visited (x + 0 = x).
+#define LAMA_RESIZE_AREA_INT 0      // scale = 1 / factor is an integer: resizeAreaFast
+#define LAMA_RESIZE_AREA_FRAC 1     // scale > 1: computeResizeAreaTab + ResizeArea_Invoker
+#define LAMA_RESIZE_LINEAR 2        // scale < 1: the linear path with area coefficients
+struct ResizeParams {
+    const uint8_t* img;          // [B][Hs][Ws][3], each image's h x w pixels in the top-left corner of its slot
+    const uint8_t* mask;         // [B][Hs][Ws]
+    const int32_t* src_sizes;    // [B][2] = (h, w); h = 0: an empty slot -> zeros
+    const int32_t* dst_sizes;    // [B][2] = scaled_size(h, w, factor), from the host
+    float* out_img;              // [B,3,Hp,Wp]
+    long long img_bs;
+    float* out_mask;             // [B,1,Hp,Wp]
+    long long mask_bs;
+    double factor, scale;        // scale = 1.0 / factor: one fp64 division on the host, as the Python does it
+    float inv_area;              // integer shrink: float32(1.0 / (isc * isc))
+    int B, Hs, Ws, Hp, Wp, binarize, regime, isc;
+};
+__device__ __forceinline__ float rz_px(const uint8_t* q) { return (float)q[0] / 255.0f; }
+// one destination index of computeResizeAreaTab (_area_taps): an optional first tap s1 - 1 (wa), the whole cells s1 .. s2 - 1 (wm), an optional
+// last tap s2 (wb)
+struct AreaTaps {
+    int s1, s2;
+    float wa, wm, wb;
+    bool first, last;
+};
+__device__ __forceinline__ AreaTaps rz_area_taps(int d, int ssize, double scale) {
+#pragma clang fp contract(off)
+    AreaTaps t;
+    const double f1 = (double)d * scale;
+    const double f2 = f1 + scale;
+    const double rem = (double)ssize - f1;
+    const double cell = rem < scale ? rem : scale;
+    const double c1 = ceil(f1), c2 = floor(f2), last = (double)(ssize - 1);
+    int s1 = (int)(c1 < last ? c1 : last), s2 = (int)(c2 < last ? c2 : last);       // s2 = min(s2, ssize - 1); s1 = min(s1, s2) below
+    s1 = s1 < s2 ? s1 : s2;
+    s1 = s1 > 0 ? s1 : 0;                                      // (never taken for sizes the host computed: keeps every read inside the image)
+    s2 = s2 > 0 ? s2 : 0;
+    const double da = (double)s1 - f1;
+    double db = f2 - (double)s2;
+    t.first = da > 1e-3 && s1 > 0;
+    t.last = db > 1e-3;
+    db = db < 1.0 ? db : 1.0;
+    db = db < cell ? db : cell;
+    t.s1 = s1; t.s2 = s2;
+    t.wa = (float)(da / cell);
+    t.wm = (float)(1.0 / cell);
+    t.wb = (float)(db / cell);
+    return t;
+}
+// the x pass of ResizeArea_Invoker over one source row, three channels: buf += S[sx] * alpha, taps in table order
+__device__ __forceinline__ void rz_area_row(const uint8_t* row, const AreaTaps& t, float buf[3]) {
+#pragma clang fp contract(off)
+    buf[0] = buf[1] = buf[2] = 0.0f;
+    if (t.first) {
+        const uint8_t* q = row + (long long)(t.s1 - 1) * 3;
+        for (int c = 0; c < 3; ++c) buf[c] = buf[c] + rz_px(q + c) * t.wa;
+    }
+    for (int sx = t.s1; sx < t.s2; ++sx) {
+        const uint8_t* q = row + (long long)sx * 3;
+        for (int c = 0; c < 3; ++c) buf[c] = buf[c] + rz_px(q + c) * t.wm;
+    }
+    if (t.last) {
+        const uint8_t* q = row + (long long)t.s2 * 3;
+        for (int c = 0; c < 3; ++c) buf[c] = buf[c] + rz_px(q + c) * t.wb;
+    }
+}
+// enlarging (_resize_area's coef): sx = floor(d * scale), fx = float32((d + 1) - (sx + 1) * factor) kept in [0, 1)
+struct LinTaps {
+    int i0, i1;
+    float a0, a1;
+};
+__device__ __forceinline__ LinTaps rz_lin_taps(int d, int ssize, double scale, double factor) {
+#pragma clang fp contract(off)
+    LinTaps t;
+    int sx = (int)floor((double)d * scale);
+    const double prod = (double)(sx + 1) * factor;
+    float fx = (float)((double)(d + 1) - prod);
+    fx = fx <= 0.0f ? 0.0f : fx - floorf(fx);
+    if (sx < 0) { fx = 0.0f; sx = 0; }
+    if (sx >= ssize - 1) { fx = 0.0f; sx = ssize - 1; }
+    t.i0 = sx;
+    t.i1 = sx + 1 < ssize - 1 ? sx + 1 : ssize - 1;
+    t.a0 = 1.0f - fx;
+    t.a1 = fx;
+    return t;
+}
+// np.pad(mode='symmetric') for any amount of padding (a scaled image may be smaller than its padding: 5 x 7 at 0.5 -> 2 x 4, padded to 8 x 8)
+__device__ __forceinline__ int rz_symmetric(int y, int n) {
+    const int t = y % (2 * n);
+    return t < n ? t : 2 * n - 1 - t;
+}
+__global__ __launch_bounds__(LAMA_NTHREADS) void resize_u8_kernel(ResizeParams p) {
+#pragma clang fp contract(off)
+    const long long hw = (long long)p.Hp * p.Wp, total = (long long)p.B * hw;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / hw);
+        const long long px = i - (long long)b * hw;
+        const int y = (int)(px / p.Wp), x = (int)(px - (long long)y * p.Wp);
+        const int h = p.src_sizes[2 * b], w = p.src_sizes[2 * b + 1], dh = p.dst_sizes[2 * b], dw = p.dst_sizes[2 * b + 1];
+        float v[3] = {0.0f, 0.0f, 0.0f}, m = 0.0f;
+        // an empty slot, or sizes that do not fit the slot / the output view (the host cannot see them without a synchronisation): zeros
+        if (h > 0 && w > 0 && dh > 0 && dw > 0 && h <= p.Hs && w <= p.Ws && dh <= p.Hp && dw <= p.Wp) {
+            const int ys = rz_symmetric(y, dh), xs = rz_symmetric(x, dw);
+            const uint8_t* src = p.img + (long long)b * p.Hs * p.Ws * 3;
+            const long long rs = (long long)p.Ws * 3;                              // bytes per source row of the slot
+            if (p.regime == LAMA_RESIZE_AREA_INT) {
+                const int isc = p.isc;
+                const int dh2 = dh < h / isc ? dh : h / isc, dw2 = dw < w / isc ? dw : w / isc;
+                if (ys < dh2 && xs < dw2) {                                          // resizeAreaFast: the box sy-major, four at a time, * float32(1 / area)
+                    const uint8_t* base = src + (long long)ys * isc * rs + (long long)xs * isc * 3;
+                    const int area = isc * isc;
+                    int k = 0, sy = 0, sx = 0;
+                    float t[4][3];
+                    for (; k <= area - 4; k += 4) {
+                        for (int j = 0; j < 4; ++j) {
+                            const uint8_t* q = base + sy * rs + sx * 3;
+                            for (int c = 0; c < 3; ++c) t[j][c] = rz_px(q + c);
+                            if (++sx == isc) { sx = 0; ++sy; }
+                        }
+                        for (int c = 0; c < 3; ++c) v[c] = v[c] + (((t[0][c] + t[1][c]) + t[2][c]) + t[3][c]);
+                    }
+                    for (; k < area; ++k) {
+                        const uint8_t* q = base + sy * rs + sx * 3;
+                        for (int c = 0; c < 3; ++c) v[c] = v[c] + rz_px(q + c);
+                        if (++sx == isc) { sx = 0; ++sy; }
+                    }
+                    for (int c = 0; c < 3; ++c) v[c] = v[c] * p.inv_area;
+                } else {                                                             // its border loop: row-major sum of the pixels inside the image / their count
+                    const long long ly0 = (long long)ys * isc, lx0 = (long long)xs * isc;
+                    const int y0 = (int)(ly0 < h ? ly0 : h), x0 = (int)(lx0 < w ? lx0 : w);
+                    const int y1 = ly0 + isc < h ? (int)(ly0 + isc) : h, x1 = lx0 + isc < w ? (int)(lx0 + isc) : w;
+                    const int cnt = (y1 - y0) * (x1 - x0);
+                    if (cnt > 0) {
+                        for (int yy = y0; yy < y1; ++yy)
+                            for (int xx = x0; xx < x1; ++xx) {
+                                const uint8_t* q = src + yy * rs + (long long)xx * 3;
+                                for (int c = 0; c < 3; ++c) v[c] = v[c] + rz_px(q + c);
+                            }
+                        for (int c = 0; c < 3; ++c) v[c] = v[c] / (float)cnt;
+                    }
+                }
+            } else if (p.regime == LAMA_RESIZE_AREA_FRAC) {                          // the x pass of each source row this pixel needs, then the y pass over them
+                const AreaTaps tx = rz_area_taps(xs, w, p.scale), ty = rz_area_taps(ys, h, p.scale);
+                float buf[3];
+                if (ty.first) {
+                    rz_area_row(src + (long long)(ty.s1 - 1) * rs, tx, buf);
+                    for (int c = 0; c < 3; ++c) v[c] = v[c] + buf[c] * ty.wa;
+                }
+                for (int sy = ty.s1; sy < ty.s2; ++sy) {
+                    rz_area_row(src + sy * rs, tx, buf);
+                    for (int c = 0; c < 3; ++c) v[c] = v[c] + buf[c] * ty.wm;
+                }
+                if (ty.last) {
+                    rz_area_row(src + ty.s2 * rs, tx, buf);
+                    for (int c = 0; c < 3; ++c) v[c] = v[c] + buf[c] * ty.wb;
+                }
+            } else {                                                                 // rows = a[x0] * ax0 + a[x1] * ax1, then the same in y
+                const LinTaps tx = rz_lin_taps(xs, w, p.scale, p.factor), ty = rz_lin_taps(ys, h, p.scale, p.factor);
+                const uint8_t* r0 = src + ty.i0 * rs;
+                const uint8_t* r1 = src + ty.i1 * rs;
+                for (int c = 0; c < 3; ++c) {
+                    const float row0 = rz_px(r0 + tx.i0 * 3 + c) * tx.a0 + rz_px(r0 + tx.i1 * 3 + c) * tx.a1;
+                    const float row1 = rz_px(r1 + tx.i0 * 3 + c) * tx.a0 + rz_px(r1 + tx.i1 * 3 + c) * tx.a1;
+                    v[c] = row0 * ty.a0 + row1 * ty.a1;
+                }
+            }
+            // INTER_NEAREST (_resize_nearest): tap min(floor(d * (1 / factor)), size - 1)
+            const double fy = floor((double)ys * p.scale), fx = floor((double)xs * p.scale);
+            const int my = fy < (double)(h - 1) ? (int)fy : h - 1, mx = fx < (double)(w - 1) ? (int)fx : w - 1;
+            const uint8_t mu = p.mask[((long long)b * p.Hs + my) * p.Ws + mx];
+            m = p.binarize ? (mu > 0 ? 1.0f : 0.0f) : (float)mu / 255.0f;
+        }
+        float* o = p.out_img + b * p.img_bs + px;
+        o[0] = v[0];
+        o[hw] = v[1];
+        o[2 * hw] = v[2];
+        p.out_mask[b * p.mask_bs + px] = m;
+    }
+}
+
 struct AffineParams {
     const float* x;
     long long x_bs;
@@ -302,6 +491,37 @@ extern "C" int lama_blend_quantize_u8_fwd(void* stream, const uint8_t* image_hwc
     p.out_u8 = dst_hwc;
     p.B = batch; p.Hp = pred->H; p.Wp = pred->W; p.binarize = binarize;
     hipLaunchKernelGGL(blend_quantize_u8_kernel, dim3(ew_grid((long long)batch * pred->H * pred->W)), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// dataset.scale_factor inside the u8 predict step: see resize_u8_kernel
+extern "C" int lama_resize_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes,
+                                  int32_t Hs, int32_t Ws, double factor, const lama_tensor* out_image, const lama_tensor* out_mask, int32_t batch,
+                                  int32_t binarize) {
+    if (!image_hwc || !mask || !src_sizes || !dst_sizes || !out_image || !out_mask || !out_image->ptr || !out_mask->ptr) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0 || !(factor > 0.0) || !(factor <= 1.0e9)) return LAMA_ERR_BAD_ARG;
+    if (out_image->C != 3 || out_mask->C != 1 || out_image->H <= 0 || out_image->W <= 0 || !same_hw(out_image, out_mask)) return LAMA_ERR_BAD_ARG;
+    const double scale = 1.0 / factor;
+    if (!(scale <= 1.0e9)) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({out_image, out_mask})) return LAMA_ERR_UNSUPPORTED;
+    ResizeParams p;
+    memset(&p, 0, sizeof(p));
+    p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.dst_sizes = dst_sizes;
+    p.out_img = (float*)out_image->ptr; p.img_bs = out_image->batch_stride;
+    p.out_mask = (float*)out_mask->ptr; p.mask_bs = out_mask->batch_stride;
+    p.factor = factor; p.scale = scale;
+    p.B = batch; p.Hs = Hs; p.Ws = Ws; p.Hp = out_image->H; p.Wp = out_image->W; p.binarize = binarize;
+    p.regime = LAMA_RESIZE_LINEAR;
+    p.isc = 1;
+    if (scale >= 1.0) {                                   // _resize_area: isc = int(round(scale)) (half to even), integer when |scale - isc| < eps
+        const double r = nearbyint(scale);
+        p.isc = (int)r;
+        p.regime = fabs(scale - r) < 2.220446049250313e-16 ? LAMA_RESIZE_AREA_INT : LAMA_RESIZE_AREA_FRAC;
+        if (p.regime == LAMA_RESIZE_AREA_INT && p.isc > 32768) return LAMA_ERR_UNSUPPORTED;      // (isc * isc is an int)
+        p.inv_area = (float)(1.0 / ((double)p.isc * p.isc));
+    }
+    hipLaunchKernelGGL(resize_u8_kernel, dim3(ew_grid((long long)batch * p.Hp * p.Wp)), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }

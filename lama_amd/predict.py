@@ -137,7 +137,9 @@ def pad_img_to_modulo(img: np.ndarray, mod: int) -> np.ndarray:
 # INTER_NEAREST on the float mask.  cv2 is not in this image, so this is a restatement of OpenCV 4's imgproc/resize.cpp from its published
 # algorithm -- PARITY UNPINNED (no cv2 here to generate vectors from): the index / weight tables and the float32 accumulation order follow
 # resize.cpp (computeResizeAreaTab + ResizeArea_Invoker; resizeAreaFast_Invoker's four-at-a-time sums; the INTER_AREA-upscaling coefficients of
-# the linear path; resizeNN's floor(x / f) taps), known-answer tests in tests/test_scale_factor.py.  Host code on purpose: it is the data loader.
+# the linear path; resizeNN's floor(x / f) taps), known-answer tests in tests/test_scale_factor.py.  These host functions are the loader of
+# ``refine=True`` (load_item) and the statement the device kernel is held to, bit for bit: the predict loop runs the same arithmetic inside its
+# u8 step (lama_resize_u8_fwd, csrc/elementwise.hip) and the host only decodes and computes ``scaled_size``.
 
 def scaled_size(h: int, w: int, factor: float) -> Tuple[int, int]:
     """dsize of cv::resize(dsize=None, fx, fy): saturate_cast<int>(size * f) = round half to even."""
@@ -445,11 +447,27 @@ class HostFedStep:
     The caller alternates p = 0, 1, 0, ...: it fills host set 1-p before ``launch(p)`` (after ``wait`` has told it that the launch that last
     read that set is complete), calls ``prime(p0)`` once before the first launch and ``flush(p_last)`` after the last.  ``drain=False``
     (multi-rank: the results go through the gather instead) leaves the D2H branch out.  On a CPU device (the emulator tests) the same body
-    runs synchronously, unpinned."""
+    runs synchronously, unpinned.
+
+    Three input forms: u8 HWC images as decoded, in padded slots (the default; ``put``); the same in SOURCE slots of ``src_hw`` pixels with
+    ``scale_factor`` set -- the step's first launch, lama_resize_u8_fwd, then builds the loader's rescaled, padded fp32 image and 0 / 1 mask on
+    the device and the fp32 chain (mask compose, generator, blend, u8 quantisation) runs on them; fp32 NCHW tensors the caller made
+    (``u8_input=False``).  Every mode serves every form; in 'graph' the resize is one more kernel node of the captured step."""
 
     def __init__(self, model, batch_size: int, Hp: int, Wp: int, device, *, drain: bool = True, binarize: bool = True, mode: str = 'auto',
-                 u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True):
+                 u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True, scale_factor: Optional[float] = None,
+                 src_hw: Optional[Tuple[int, int]] = None):
         self.model, self.n, self.Hp, self.Wp = model, int(batch_size), int(Hp), int(Wp)
+        # ``scale_factor`` (dataset.scale_factor, evaluation/data.py:74-77): the third input form -- the step is fed with the DECODED u8 originals in
+        # source slots of ``src_hw`` = (Hs, Ws) pixels, and its first launch (lama_resize_u8_fwd) does / 255, the INTER_AREA / INTER_NEAREST
+        # rescale, the symmetric padding and mask > 0 on the device; (Hp, Wp) is the padded SCALED size
+        self.scale = None if scale_factor is None else float(scale_factor)
+        if self.scale is not None:
+            if not self.scale > 0:
+                raise L.LamaError(f'scale_factor {scale_factor!r}: a positive factor')
+            if src_hw is None or int(src_hw[0]) < 1 or int(src_hw[1]) < 1:
+                raise L.LamaError(f'scale_factor={scale_factor}: src_hw = (Hs, Ws), the source slot size, is needed (got {src_hw!r})')
+            self.Hs, self.Ws = int(src_hw[0]), int(src_hw[1])
         if out_key not in ('inpainted', 'predicted_image'):                        # bin/predict.py:86: batch[predict_config.out_key]
             raise L.LamaError(f"out_key {out_key!r}: 'inpainted' or 'predicted_image'")
         self.out_key = out_key
@@ -478,8 +496,21 @@ class HostFedStep:
         pin = dict(pin_memory=True) if self.on_gpu else {}
         # round 6: the step is fed with what is on disk -- u8 HWC image, u8 mask, (h, w) per image: 4 bytes per pixel over PCIe instead of 16, no
         # float conversion / padding on the host (forward_u8).  ``u8_input=False`` keeps the fp32 NCHW form of round 5 (A/B runs, callers with float data).
-        self.u8_input = bool(u8_input) and hasattr(model, 'forward_u8')
-        if self.u8_input:
+        self.u8_input = bool(u8_input) and hasattr(model, 'forward_u8') and self.scale is None
+        self.h_dsizes = self.d_dsizes = None
+        if self.scale is not None:
+            self.h_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, **pin) for _ in range(2)]
+            self.h_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, **pin) for _ in range(2)]
+            self.h_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, **pin) for _ in range(2)]           # (h, w) of each source image
+            self.h_dsizes = [torch.zeros(self.n, 2, dtype=torch.int32, **pin) for _ in range(2)]          # scaled_size of it
+            self.d_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self.d_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self.d_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, device=self.device) for _ in range(2)]
+            self.d_dsizes = [torch.zeros(self.n, 2, dtype=torch.int32, device=self.device) for _ in range(2)]
+            # the loader's fp32 tensors exist on the device only (one set: the steps of both parities run in order on one stream)
+            self.f_img = torch.zeros(self.n, 3, Hp, Wp, dtype=torch.float32, device=self.device)
+            self.f_mask = torch.zeros(self.n, 1, Hp, Wp, dtype=torch.float32, device=self.device)
+        elif self.u8_input:
             self.h_img = [torch.zeros(self.n, Hp, Wp, 3, dtype=torch.uint8, **pin) for _ in range(2)]
             self.h_mask = [torch.zeros(self.n, Hp, Wp, dtype=torch.uint8, **pin) for _ in range(2)]
             self.h_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, **pin) for _ in range(2)]
@@ -506,15 +537,31 @@ class HostFedStep:
 
     # -- host views -----------------------------------------------------------------------------------------------
     def host(self, p: int):
-        """The pinned host set p as numpy views: (image, mask) -- u8 [n,Hp,Wp,3] / [n,Hp,Wp] (``u8_input``; ``put`` fills them) or fp32 NCHW."""
+        """The pinned host set p as numpy views: (image, mask) -- u8 [n,Hp,Wp,3] / [n,Hp,Wp] (``u8_input``; ``put`` fills them), u8 source slots
+        [n,Hs,Ws,3] / [n,Hs,Ws] (``scale_factor``) or fp32 NCHW."""
         return self.h_img[p].numpy(), self.h_mask[p].numpy()
 
     def put(self, p: int, j: int, image: Optional[np.ndarray], mask: Optional[np.ndarray]):
         """``u8_input``: image j of host set p = a decoded u8 HWC image [h,w,3] + u8 mask [h,w] (top-left corner of the slot), or None: an empty
-        slot of a partial batch."""
+        slot of a partial batch.  ``scale_factor``: the same pair, the decoded ORIGINAL, into its source slot."""
+        if self.scale is not None:
+            sz, dz = self.h_sizes[p].numpy(), self.h_dsizes[p].numpy()
+            if image is None:
+                sz[j] = dz[j] = (0, 0)
+                return
+            h, w = image.shape[:2]
+            dh, dw = scaled_size(h, w, self.scale)
+            if dh <= 0 or dw <= 0:
+                raise L.LamaError(f'scale_factor {self.scale}: a {w}x{h} image scales to nothing')
+            if h > self.Hs or w > self.Ws or dh > self.Hp or dw > self.Wp:       # (the kernel cannot report it: the sizes are device data there)
+                raise L.LamaError(f'image {h}x{w} (scaled {dh}x{dw}) does not fit the source slot {self.Hs}x{self.Ws} / the bucket {self.Hp}x{self.Wp}')
+            self.h_img[p].numpy()[j, :h, :w] = image
+            self.h_mask[p].numpy()[j, :h, :w] = mask
+            sz[j], dz[j] = (h, w), (dh, dw)
+            return
         if not self.u8_input:
-            # fp32 NCHW form (dataset.scale_factor: the rescaled image is not u8 any more): image [3,Hp,Wp] / mask [1,Hp,Wp] float32 as
-            # ``load_item`` returns them, already padded; an empty slot is zeros
+            # fp32 NCHW form (callers with float data): image [3,Hp,Wp] / mask [1,Hp,Wp] float32 as ``load_item`` returns them, already padded;
+            # an empty slot is zeros
             hi, hm = self.h_img[p].numpy(), self.h_mask[p].numpy()
             if image is None:
                 hi[j] = 0
@@ -546,8 +593,14 @@ class HostFedStep:
             with torch.no_grad():
                 self.model.forward_u8(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.u8[p], binarize=self.binarize, out_key=self.out_key)
             return
-        mask = self.d_mask[p]
-        batch = dict(image=self.d_img[p], mask=(mask > 0) * 1 if self.binarize else mask)          # bin/predict.py:84
+        if self.scale is not None:                                                                 # data.py:69-83 + bin/predict.py:84 in one launch: fp32 image / mask
+            stream = torch.cuda.current_stream(self.device).cuda_stream if self.on_gpu else 0
+            lib.resize_u8(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.d_dsizes[p], self.scale, L.view(self.f_img), L.view(self.f_mask), self.n,
+                          binarize=self.binarize, stream=stream)
+            batch = dict(image=self.f_img, mask=self.f_mask)
+        else:
+            mask = self.d_mask[p]
+            batch = dict(image=self.d_img[p], mask=(mask > 0) * 1 if self.binarize else mask)      # bin/predict.py:84
         keep = self.model.keep_predicted_image
         self.model.keep_predicted_image = False
         try:
@@ -558,12 +611,19 @@ class HostFedStep:
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.on_gpu else 0
         lib.quantize_u8_hwc(L.view(out), self.u8[p], self.n, self.Hp, self.Wp, stream)             # bin/predict.py:92 on the device
 
+    def _upload(self, q: int, non_blocking: bool):
+        """H2D of input set q on the current stream: image, mask and -- the u8 forms -- the per-image sizes."""
+        self.d_img[q].copy_(self.h_img[q], non_blocking=non_blocking)
+        self.d_mask[q].copy_(self.h_mask[q], non_blocking=non_blocking)
+        if self.d_sizes is not None:
+            self.d_sizes[q].copy_(self.h_sizes[q], non_blocking=non_blocking)
+        if self.d_dsizes is not None:
+            self.d_dsizes[q].copy_(self.h_dsizes[q], non_blocking=non_blocking)
+
     def _body(self, p: int):
         q = 1 - p
         if not self.on_gpu:
-            self.d_img[q].copy_(self.h_img[q]); self.d_mask[q].copy_(self.h_mask[q])
-            if self.u8_input:
-                self.d_sizes[q].copy_(self.h_sizes[q])
+            self._upload(q, False)
             if self.drain:
                 self.h_u8[q].copy_(self.u8[q])
             self._compute(p)
@@ -571,10 +631,7 @@ class HostFedStep:
         main = torch.cuda.current_stream(self.device)
         self.s_in.wait_stream(main)
         with torch.cuda.stream(self.s_in):
-            self.d_img[q].copy_(self.h_img[q], non_blocking=True)
-            self.d_mask[q].copy_(self.h_mask[q], non_blocking=True)
-            if self.u8_input:
-                self.d_sizes[q].copy_(self.h_sizes[q], non_blocking=True)
+            self._upload(q, True)
         if self.drain:
             self.s_out.wait_stream(main)
             with torch.cuda.stream(self.s_out):
@@ -610,10 +667,7 @@ class HostFedStep:
     def prime(self, p: int):
         """H2D of host set p on the current stream (before the first launch of a run) and a host wait for it: the caller refills that host
         set for the batch after next before any ``wait`` has covered this copy."""
-        self.d_img[p].copy_(self.h_img[p], non_blocking=self.on_gpu)
-        self.d_mask[p].copy_(self.h_mask[p], non_blocking=self.on_gpu)
-        if self.u8_input:
-            self.d_sizes[p].copy_(self.h_sizes[p], non_blocking=self.on_gpu)
+        self._upload(p, self.on_gpu)
         if self.on_gpu:
             torch.cuda.current_stream(self.device).synchronize()
 
@@ -644,10 +698,7 @@ class HostFedStep:
             if self._launched[q]:
                 self.done[q].synchronize()               # host: step k - 1 is complete (step k is queued behind it: the GPU does not idle)
             with torch.cuda.stream(self.s_in):
-                self.d_img[q].copy_(self.h_img[q], non_blocking=True)
-                self.d_mask[q].copy_(self.h_mask[q], non_blocking=True)
-                if self.u8_input:
-                    self.d_sizes[q].copy_(self.h_sizes[q], non_blocking=True)
+                self._upload(q, True)
                 self.h2d[q].record(self.s_in)
             self._h2d_issued[q] = True
             if self.drain:
@@ -694,8 +745,8 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
             pad_mod: int = 8, batch_size: int = 8, out_ext: str = '.png', device='cuda', rank: int = 0, world: int = 1,
             dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None) -> int:
     """Run every (mask, image) pair through ``model`` and write the results (rank 0).  Returns the number of images written.
-    ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled on the host before the padding, the
-    step is then fed with fp32 tensors and the results have the rescaled size.
+    ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled before the padding -- on the device, by
+    the first launch of the step, which is fed with the decoded u8 originals (lama_resize_u8_fwd) -- and the results have the rescaled size.
 
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
@@ -717,7 +768,7 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
     def header_size(item):                   # padded shape from the IMAGE's PNG header only: every rank builds the same plan
         with Image.open(item[1]) as im:
             w, h = im.size
-        return (h, w) if scale_factor is None else scaled_size(h, w, scale_factor)
+        return (h, w)
 
     lib = model.generator._exec.lib
     pool = ThreadPoolExecutor(io_threads)
@@ -725,18 +776,24 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
     # get workers of their own instead of queueing behind milliseconds of PNG work in ``pool``
     fast = ThreadPoolExecutor(min(4, max(1, io_threads)))
     try:
-        sizes = list(pool.map(header_size, items, chunksize=64))       # (0.15 ms per file on the main thread was a tenth of a long directory's wall time)
+        src_sizes = list(pool.map(header_size, items, chunksize=64))   # (0.15 ms per file on the main thread was a tenth of a long directory's wall time)
+        # dataset.scale_factor: results, buckets and crops have the SCALED size (data.py:74-79); the source sizes size each bucket's upload slots
+        sizes = src_sizes if scale_factor is None else [scaled_size(h, w, scale_factor) for h, w in src_sizes]
+        for (h, w), (sh, sw) in zip(sizes, src_sizes):
+            if h <= 0 or w <= 0:
+                raise L.LamaError(f'scale_factor {scale_factor}: a {sw}x{sh} image scales to nothing')
         shapes = [(ceil_modulo(h, pad_mod), ceil_modulo(w, pad_mod)) if pad_mod and pad_mod > 1 else (h, w) for h, w in sizes]
         rounds = plan_rounds(shapes, batch_size, world)
         return _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext,
-                               device=device, rank=rank, world=world, dist=dist, out_key=out_key, fast=fast, scale_factor=scale_factor)
+                               device=device, rank=rank, world=world, dist=dist, out_key=out_key, fast=fast, scale_factor=scale_factor,
+                               src_sizes=src_sizes)
     finally:
         fast.shutdown()
         pool.shutdown()                      # on every exit path (a raise out of a bucket included): no worker thread outlives the call
 
 
 def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pad_mod, batch_size, out_ext, device, rank, world, dist, out_key='inpainted', fast=None,
-                    scale_factor=None) -> int:
+                    scale_factor=None, src_sizes=None) -> int:
     """The rounds of one attempt.  Per bucket (padded shape) a ``HostFedStep``: round k computes from device input set k & 1 while the SAME graph
     launch uploads round k + 1's decoded images into the other set and (one rank) downloads round k - 1's u8 results; the host fills the
     pinned set of round k + 1 and queues round k - 2's PNG writes while round k runs.  Several ranks: the results go through the one
@@ -756,10 +813,8 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
 
     def submit_loads(r):
         if r < len(rounds) and r not in loads:
-            if scale_factor is None:
-                loads[r] = [pool.submit(load_item_u8, *items[i]) for i in rounds[r]['batches'][rank]]  # decode only: / 255, padding, mask > 0 run on the device
-            else:                                                                                      # data.py:69-83 on the host: decode, / 255, rescale, pad
-                loads[r] = [pool.submit(load_item, *items[i], pad_mod, scale_factor) for i in rounds[r]['batches'][rank]]
+            # decode only: / 255, dataset.scale_factor's rescale, the padding and mask > 0 run on the device
+            loads[r] = [pool.submit(load_item_u8, *items[i]) for i in rounds[r]['batches'][rank]]
 
     snapped = [_Latch(), _Latch()]           # per pinned result set: the workers that still copy their image out of it
 
@@ -788,8 +843,12 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             r1 += 1
         K = r1 - r0
         t_ = time.perf_counter()
+        src_hw = None
+        if scale_factor is not None:             # the bucket's source slots hold its largest source image (every rank: the same plan, the same slots)
+            members = [src_sizes[i] for rd in rounds[r0:r1] for b in rd['batches'] for i in b]
+            src_hw = (max(h for h, _ in members), max(w for _, w in members))
         hs = HostFedStep(model, batch_size, Hp, Wp, device, drain=(world == 1), tune=(K >= TUNE_MIN_ROUNDS), capture=(K >= CAPTURE_MIN_ROUNDS), out_key=out_key,
-                         u8_input=(scale_factor is None))
+                         scale_factor=scale_factor, src_hw=src_hw)
         LOOP_TIMES['bucket_setup'] = LOOP_TIMES.get('bucket_setup', 0.0) + time.perf_counter() - t_
         if PROFILE_SPANS:
             hs.span_events = []
