@@ -364,6 +364,24 @@ size_t lama_ssim_workspace_bytes(int32_t batch, int32_t C, int32_t H, int32_t W)
 int lama_ssim_fwd(void* stream, const lama_tensor* img1, const lama_tensor* img2, int32_t batch, int32_t window_size,
                   const float* window1d, float* out, void* workspace, size_t workspace_bytes);
 
+/* LPIPS (VGG-16, net-lin; saicinpainting/evaluation/losses/lpips.py) around the backbone's 3x3 convs (lama_conv2d_fwd / lama_winograd_conv3x3_fwd with
+ * LAMA_PAD_ZERO).  fp32 tensors only.
+ * lama_lpips_scale_fwd: ScalingLayer (lpips.py:603-610) of both inputs into ONE tensor: y[i] = ((2 x0[i] - 1) - shift_c) / scale_c for i < batch,
+ *   y[batch + i] = the same of x1[i]; normalize = 0 skips the 2 x - 1 (inputs already in [-1, 1]).  x0, x1: [batch, 3, H, W]; y: [2 batch, 3, H, W];
+ *   shift, scale: HOST arrays of 3 floats.  The zero padding of conv1_1 applies to y, so this does not fold into that layer's weights.
+ * lama_lpips_layer_fwd: one feature level.  f0, f1: [batch, C, h, w] (the two halves of the backbone's output), w: device [C] (the level's linear head):
+ *   acc[b] += (1 / (h w)) sum_pixels sum_c w_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2,   |.| = the channel L2 norm of a pixel
+ *   (lpips.py:45-47, 578-586); acc: device [batch] floats that the caller zeroes (or carries from the levels before).  Neither the normalised features nor
+ *   the difference reach memory.  pool0 / pool1 (both or neither; NULL or ptr = NULL: off): [batch, C, h / 2, w / 2] = max_pool2d(f, 2, 2) of the two
+ *   maps, written by the same launch (floor semantics: an odd last row / column is in the distance, not in the pool).  Any C, h, w >= 1 (h, w >= 2 with
+ *   pool).  The sums are formed in a fixed order without atomics: two runs are bit-identical, and f0 == f1 gives exactly 0.  workspace: 8-byte aligned
+ *   device scratch of lama_lpips_layer_workspace_bytes() bytes (LAMA_ERR_WORKSPACE otherwise). */
+int lama_lpips_scale_fwd(void* stream, const lama_tensor* x0, const lama_tensor* x1, const lama_tensor* y, int32_t batch, int32_t normalize,
+                         const float* shift, const float* scale);
+size_t lama_lpips_layer_workspace_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
+int lama_lpips_layer_fwd(void* stream, const lama_tensor* f0, const lama_tensor* f1, int32_t batch, const float* w, float* acc,
+                         const lama_tensor* pool0, const lama_tensor* pool1, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,9 @@ class LamaLib:
         L.lama_dgrad_ring_bytes.restype, L.lama_dgrad_ring_bytes.argtypes = C.c_size_t, [i32, i32, i32, i32]
         L.lama_ssim_workspace_bytes.restype, L.lama_ssim_workspace_bytes.argtypes = C.c_size_t, [i32, i32, i32, i32]
         L.lama_ssim_fwd.restype, L.lama_ssim_fwd.argtypes = C.c_int, [vp, T, T, i32, i32, C.POINTER(C.c_float), vp, vp, C.c_size_t]
+        L.lama_lpips_scale_fwd.restype, L.lama_lpips_scale_fwd.argtypes = C.c_int, [vp, T, T, T, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.lama_lpips_layer_workspace_bytes.restype, L.lama_lpips_layer_workspace_bytes.argtypes = C.c_size_t, [i32, i32, i32, i32]
+        L.lama_lpips_layer_fwd.restype, L.lama_lpips_layer_fwd.argtypes = C.c_int, [vp, T, T, i32, vp, vp, T, T, vp, C.c_size_t]
         L.lama_fuse1_channel_order.restype, L.lama_fuse1_channel_order.argtypes = None, [C.POINTER(C.c_int32)]
         L.lama_winograd_packed_weight_bytes.restype, L.lama_winograd_packed_weight_bytes.argtypes = C.c_int64, [i32, i32, i32]
         L.lama_winograd_pack_weight.restype, L.lama_winograd_pack_weight.argtypes = C.c_int, [vp, vp, vp, i32, i32, i32, vp]
@@ -460,6 +463,28 @@ class LamaLib:
 
     def ssim_workspace_bytes(self, batch: int, c: int, h: int, w: int) -> int:
         return int(self._l.lama_ssim_workspace_bytes(batch, c, h, w))
+
+    def lpips_scale(self, x0: Tensor4, x1: Tensor4, y: Tensor4, batch: int, shift, scale, normalize: bool = True, stream: int = 0):
+        """lama_lpips_scale_fwd: ((2 x - 1) - shift) / scale of x0 | x1 ([batch,3,H,W] each) into the two halves of y [2 batch,3,H,W];
+        shift / scale = host sequences of 3 floats."""
+        sh, sc = (C.c_float * 3)(*[float(v) for v in shift]), (C.c_float * 3)(*[float(v) for v in scale])
+        self.check(self._l.lama_lpips_scale_fwd(stream, C.byref(x0), C.byref(x1), C.byref(y), batch, int(bool(normalize)), sh, sc), 'lama_lpips_scale_fwd')
+
+    def lpips_layer(self, f0: Tensor4, f1: Tensor4, batch: int, w: torch.Tensor, acc: torch.Tensor, workspace: torch.Tensor,
+                    pool0: Optional[Tensor4] = None, pool1: Optional[Tensor4] = None, stream: int = 0):
+        """lama_lpips_layer_fwd: acc[b] += the level's LPIPS term of (f0[b], f1[b]) under the head ``w`` [C]; pool0 / pool1 receive max_pool2d(f, 2, 2)
+        from the same launch.  ``workspace``: device buffer of at least lpips_layer_workspace_bytes() bytes."""
+        for name, t in (('w', w), ('acc', acc), ('workspace', workspace)):
+            if not self.host_emulated and not t.is_cuda:
+                raise LamaError(f'lpips_layer: {name} must be a device tensor')
+        if w.dtype != torch.float32 or acc.dtype != torch.float32 or not w.is_contiguous() or not acc.is_contiguous() or w.numel() != f0.C or acc.numel() < batch:
+            raise LamaError(f'lpips_layer: w is [C] fp32 and acc [batch] fp32, got {tuple(w.shape)} {w.dtype} / {tuple(acc.shape)} {acc.dtype}')
+        self.check(self._l.lama_lpips_layer_fwd(stream, C.byref(f0), C.byref(f1), batch, w.data_ptr(), acc.data_ptr(),
+                                                None if pool0 is None else C.byref(pool0), None if pool1 is None else C.byref(pool1),
+                                                workspace.data_ptr(), workspace.numel() * workspace.element_size()), 'lama_lpips_layer_fwd')
+
+    def lpips_layer_workspace_bytes(self, batch: int, c: int, h: int, w: int) -> int:
+        return int(self._l.lama_lpips_layer_workspace_bytes(batch, c, h, w))
 
     def gauss5(self, x: Tensor4, y: Tensor4, batch: int, stream: int = 0):
         self.check(self._l.lama_gauss5_fwd(stream, C.byref(x), C.byref(y), batch), 'lama_gauss5_fwd')

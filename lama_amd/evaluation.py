@@ -1,15 +1,24 @@
-"""SSIM on the HIP path: ``saicinpainting/evaluation/losses/ssim.py`` ``SSIM`` as one launch pair
-(``lama_ssim_fwd``, csrc/metrics.hip), same constructor, same ``forward(img1, img2)``.
+"""Quality evaluators on the HIP path.
 
-That class is the only arithmetic of the reference's evaluator surface that is not a pretrained network: ``SSIMScore``
-(``losses/base_loss.py``) wraps it, ``InpaintingEvaluator`` / ``InpaintingEvaluatorOnline`` (``evaluator.py``) are bookkeeping around the
-scores.  The switch for a reference user is therefore ONE import -- ``from lama_amd.evaluation import SSIM`` in ``losses/base_loss.py`` --
-and the reference's own evaluator, grouping and reporting code keeps running unchanged.  Round 2 carried a host mirror
-of that bookkeeping here; it was a transcription with no MI355X work in it and has been removed.  LPIPS / FID / the segmentation-aware
-scores are pretrained networks (VGG-16 + heads, Inception-v3, an ADE20k segmenter) that exist only as downloads: out of scope.
+SSIM: ``saicinpainting/evaluation/losses/ssim.py`` ``SSIM`` as one launch pair (``lama_ssim_fwd``, csrc/metrics.hip), same constructor, same
+``forward(img1, img2)``.  ``SSIMScore`` (``losses/base_loss.py``) wraps it, ``InpaintingEvaluator`` / ``InpaintingEvaluatorOnline``
+(``evaluator.py``) are bookkeeping around the scores: the switch for a reference user is ONE import -- ``from lama_amd.evaluation import SSIM`` in
+``losses/base_loss.py`` -- and the reference's own evaluator, grouping and reporting code keeps running unchanged.
+
+LPIPS: ``losses/lpips.py`` ``PerceptualLoss(model='net-lin', net='vgg')`` and ``base_loss.LPIPSScore``.  Pred and target go through the VGG-16
+backbone as ONE batch of 2N images: ``lama_lpips_scale_fwd`` writes both scaled inputs into one tensor, the thirteen zero-padded 3x3 convs + ReLU
+are ``lama_conv2d_fwd`` / ``lama_winograd_conv3x3_fwd`` launches, and one ``lama_lpips_layer_fwd`` per feature level forms the distance term AND
+the 2x2 max-pool that feeds the next slice (csrc/metrics.hip).  Module tree and state-dict keys are the reference's.  Nothing is downloaded: the
+linear heads (``model_path``, the reference's ``models/lpips_models/vgg.pth``) and the backbone (``backbone``, e.g. torchvision's
+``vgg16-397923af.pth``) are files or state dicts the caller supplies.  The other nets / models / ``spatial`` / ``Lab`` raise NotImplementedError.
+
+FID and the segmentation-aware scores are pretrained networks of another order (Inception-v3, an ADE20k segmenter): out of scope.
 """
 from __future__ import annotations
 
+import collections
+import os
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -17,7 +26,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from ._lib import LamaError
+from ._lib import LamaError, LamaRangeError
+from .ffc import _Exec, _HipModule
+from .pix2pixhd import Conv2dBN
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -62,3 +73,363 @@ class SSIM(nn.Module):
 
     def _load_from_state_dict(self, *args, **kwargs):                                     # ssim.py:73-74: the window is never loaded
         return
+
+
+# ----------------------------------------------------------------------------------------------------
+# losses/lpips.py
+# ----------------------------------------------------------------------------------------------------
+
+# VGG-16 (Simonyan & Zisserman, configuration D) as torchvision's ``features`` lays it out: a 3x3 conv takes two indices (conv, ReLU), a
+# max-pool ('M') one.  LPIPS taps the ReLU in front of every pool and the last one, so slice k = the layers from the (k-1)-th pool up to that ReLU.
+_VGG16_D = (64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512)
+_VGG16_FILE = 'vgg16-397923af.pth'           # torchvision's file name of the ImageNet weights
+
+
+def _vgg16_slices():
+    """[(slice number 1..5, [(features index, cin, cout), ...])]"""
+    out, idx, cin, cur = [], 0, 3, []
+    for v in _VGG16_D:
+        if v == 'M':
+            out.append(cur)
+            cur, idx = [], idx + 1
+        else:
+            cur.append((idx, cin, v))
+            cin, idx = v, idx + 2
+    out.append(cur)
+    return list(enumerate(out, 1))
+
+
+class _Slice(nn.Module):
+    """Parameter container of one backbone slice: children named by their torchvision ``features`` index (the convs only)."""
+
+    def convs(self):
+        return list(self.children())
+
+
+class _VGG16(nn.Module):                      # lpips.py:808-846: slice1 .. slice5
+    def __init__(self):
+        super().__init__()
+        self.chns = []
+        for k, convs in _vgg16_slices():
+            sl = _Slice()
+            for idx, cin, cout in convs:
+                sl.add_module(str(idx), Conv2dBN(cin, cout, 3, padding=1))
+            self.add_module(f'slice{k}', sl)
+            self.chns.append(convs[-1][2])
+        for p in self.parameters():
+            p.requires_grad = False
+
+    def slices(self):
+        return [getattr(self, f'slice{k}') for k in range(1, 6)]
+
+    def features_key_map(self) -> dict:
+        """torchvision key 'features.N.weight' -> this module's key 'sliceK.N.weight'."""
+        return {f'features.{idx}.{n}': f'slice{k}.{idx}.{n}' for k, convs in _vgg16_slices() for idx, _, _ in convs for n in ('weight', 'bias')}
+
+
+class _ScalingLayer(nn.Module):               # lpips.py:603-610
+    def __init__(self):
+        super().__init__()
+        self.register_buffer('shift', torch.Tensor([-.030, -.088, -.188])[None, :, None, None])
+        self.register_buffer('scale', torch.Tensor([.458, .448, .450])[None, :, None, None])
+
+
+class _NetLinLayer(nn.Module):                # lpips.py:613-621: model.1 is the 1x1 head (model.0 a Dropout, identity in eval)
+    def __init__(self, chn_in: int):
+        super().__init__()
+        self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(chn_in, 1, 1, stride=1, padding=0, bias=False))
+
+
+class _PNetLin(nn.Module):                    # lpips.py:533-600 with pnet_type='vgg', lpips=True, spatial=False, version '0.1'
+    def __init__(self):
+        super().__init__()
+        self.scaling_layer = _ScalingLayer()
+        self.net = _VGG16()
+        self.chns = self.net.chns
+        self.L = len(self.chns)
+        for k, c in enumerate(self.chns):
+            self.add_module(f'lin{k}', _NetLinLayer(c))
+
+    def heads(self):
+        return [getattr(self, f'lin{k}').model[1].weight for k in range(self.L)]
+
+
+def _load_file(path: str, what: str) -> dict:
+    if not os.path.exists(path):
+        raise LamaError(f'LPIPS: {what} {path!r} not found (lama_amd downloads nothing)')
+    sd = torch.load(path, map_location='cpu', weights_only=True)
+    if not isinstance(sd, dict):
+        raise LamaError(f'LPIPS: {path!r} does not hold a state dict')
+    return sd
+
+
+class _DistModel(_HipModule):
+    """lpips.py:248-338 (model='net-lin', net='vgg', test mode): ``forward(in0, in1, retPerLayer=False)`` on images in [-1, 1].  Owns the per-shape
+    buffers and the launch sequence."""
+
+    _PREFIX = 'model.net.net.'
+
+    def __init__(self, model_path=None, backbone=None):
+        super().__init__()
+        self.model, self.model_name, self.spatial, self.is_train = 'net-lin', 'net-lin [vgg]', False, False
+        self.net = _PNetLin()
+        self.use_graph = False            # capture the launch sequence of a shape into a hipGraph and replay it (inputs are then copied into static buffers)
+        self.auto_fallback = True         # an activation beyond the fp16 split's range: repeat with the 3-term bf16 split and stay on it
+        self.max_plans = 4
+        self._plans = collections.OrderedDict()
+        self._load_heads(model_path)
+        self._load_backbone(backbone)
+        super().train(False)
+
+    # -- weights ---------------------------------------------------------------------------------
+    def _load_heads(self, model_path):
+        if isinstance(model_path, dict):
+            sd = model_path
+        else:
+            if model_path is None:
+                model_path = os.path.abspath(os.path.join(os.path.dirname(__file__), '..', 'models', 'lpips_models', 'vgg.pth'))
+                if not os.path.exists(model_path):
+                    raise LamaError(f"LPIPS: no linear heads at {model_path!r}: pass model_path= the reference's models/lpips_models/vgg.pth "
+                                    '(keys lin{0..4}.model.1.weight)')
+            sd = _load_file(model_path, 'heads file')
+        res = self.net.load_state_dict(sd, strict=False)                  # lpips.py:294
+        missing = [k for k in res.missing_keys if k.startswith('lin')]
+        if missing:
+            raise LamaError(f'LPIPS: the heads state dict lacks {missing} (the format of models/lpips_models/vgg.pth is lin{{k}}.model.1.weight)')
+
+    def _load_backbone(self, backbone):
+        if backbone is None:
+            path = os.path.join(torch.hub.get_dir(), 'checkpoints', _VGG16_FILE)
+            if not os.path.exists(path):
+                raise LamaError(f"LPIPS: no VGG-16 backbone: pass backbone= a state dict or a path to one (torchvision's {_VGG16_FILE} with "
+                                f"'features.N.*' keys, or the reference's '{self._PREFIX}slice*' keys); {path!r} does not exist and nothing is downloaded")
+            backbone = path
+        sd = backbone if isinstance(backbone, dict) else _load_file(os.fspath(backbone), 'backbone')
+        kmap = self.net.net.features_key_map()
+        own = {}
+        for k, v in sd.items():
+            if k in kmap:
+                own[kmap[k]] = v
+            elif k.startswith(self._PREFIX):
+                own[k[len(self._PREFIX):]] = v
+        want = set(self.net.net.state_dict().keys())
+        if set(own) != want:
+            raise LamaError(f'LPIPS: the backbone state dict lacks {sorted(want - set(own))[:4]} ... / has unknown {sorted(set(own) - want)[:4]}: '
+                            f"expected the 26 conv tensors under 'features.N.*' or '{self._PREFIX}sliceK.N.*'")
+        self.net.net.load_state_dict(own, strict=True)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise NotImplementedError('lama_amd.evaluation LPIPS is inference-only')
+        return nn.Module.train(self, False)
+
+    def _invalidate(self):
+        super()._invalidate()
+        self._packed = None
+        self._plans = collections.OrderedDict()
+
+    # -- execution -------------------------------------------------------------------------------
+    def _consts(self, device) -> dict:
+        """Per-precision constants outside the conv layers' own packed weights: the heads as [C] device vectors, shift / scale as host floats."""
+        if self._packed is None:
+            sl = self.net.scaling_layer
+            self._packed = dict(heads=[w.detach().float().reshape(-1).contiguous() for w in self.net.heads()],
+                                shift=sl.shift.detach().float().reshape(-1).tolist(), scale=sl.scale.detach().float().reshape(-1).tolist())
+        return self._packed
+
+    def _build_plan(self, shape, device) -> dict:
+        B, _, H, W = shape
+        lib, prec = self._exec.lib, self.precision
+        bufs = dict(x=torch.empty((2 * B, 3, H, W), device=device, dtype=torch.float32))
+        steps, wino_bytes, ws_bytes = [], 0, 0
+        src, h, w = 'x', H, W
+        for k, sl in enumerate(self.net.net.slices()):
+            convs = sl.convs()
+            for j, cv in enumerate(convs):
+                dst = f'a{k}' if src != f'a{k}' else f'b{k}'
+                if dst not in bufs:
+                    bufs[dst] = torch.empty((2 * B, cv.out_channels, h, w), device=device, dtype=torch.float32)
+                wino = lib.winograd_preferred(2 * B, cv.out_channels, cv.in_channels, h, w, prec) and cv.wino_ok(None)
+                if wino:
+                    wino_bytes = max(wino_bytes, lib.winograd_workspace_bytes(2 * B, cv.out_channels, h, w))
+                steps.append(('conv', cv, src, dst, wino))
+                src = dst
+            C = convs[-1].out_channels
+            ws_bytes = max(ws_bytes, lib.lpips_layer_workspace_bytes(B, C, h, w))
+            pool = None
+            if k + 1 < self.net.L:
+                pool = f'p{k}'
+                bufs[pool] = torch.empty((2 * B, C, h // 2, w // 2), device=device, dtype=torch.float32)
+            steps.append(('layer', k, src, pool))
+            src, h, w = pool, h // 2, w // 2
+        bufs['levels'] = torch.zeros((self.net.L, B), device=device, dtype=torch.float32)
+        bufs['ws'] = torch.empty(max(1, ws_bytes // 8), device=device, dtype=torch.float64)
+        bufs['wino'] = torch.empty(max(1, wino_bytes // 4), device=device, dtype=torch.float32) if wino_bytes else None
+        return dict(bufs=bufs, steps=steps, B=B, graph=None, static=None)
+
+    def conv_paths(self, shape, device):
+        """'wino' / 'direct' per conv of the plan of this input shape (tests, tools)."""
+        return ['wino' if st[4] else 'direct' for st in self._plan_for(shape, torch.device(device))['steps'] if st[0] == 'conv']
+
+    def _plan_for(self, shape, device) -> dict:
+        key = (tuple(int(v) for v in shape), _Exec._dev_key(device), self.precision)
+        plan = self._plans.get(key)
+        if plan is None:
+            while len(self._plans) >= max(1, self.max_plans):
+                self._plans.popitem(last=False)
+            plan = self._plans[key] = self._build_plan(shape, device)
+        else:
+            self._plans.move_to_end(key)
+        return plan
+
+    @staticmethod
+    def _half(t: torch.Tensor, i: int, B: int) -> L.Tensor4:
+        """lama_tensor view of images [i B, (i + 1) B) of a contiguous fp32 [2B, C, H, W] buffer."""
+        _, C, H, W = t.shape
+        return L.Tensor4(t.data_ptr() + 4 * i * B * C * H * W, C * H * W, C, H, W, L.DT_F32)
+
+    def _run_plan(self, plan, in0: torch.Tensor, in1: torch.Tensor, normalize: bool) -> torch.Tensor:
+        ex, lib, B, bufs = self._exec, self._exec.lib, plan['B'], plan['bufs']
+        k = self._consts(in0.device)
+        st = ex.stream(in0)
+        lib.lpips_scale(L.view(in0), L.view(in1), L.view(bufs['x']), B, k['shift'], k['scale'], normalize=normalize, stream=st)
+        levels = bufs['levels']
+        levels.zero_()
+        for step in plan['steps']:
+            if step[0] == 'conv':
+                _, cv, src, dst, wino = step
+                cv.run(bufs[src], bufs[dst], None, L.ACT_RELU, 1, L.PAD_ZERO, None, bufs['wino'] if wino else None)
+            else:
+                _, lvl, src, pool = step
+                f, p = bufs[src], (bufs[pool] if pool else None)
+                lib.lpips_layer(self._half(f, 0, B), self._half(f, 1, B), B, k['heads'][lvl], levels[lvl], bufs['ws'],
+                                None if p is None else self._half(p, 0, B), None if p is None else self._half(p, 1, B), stream=st)
+        return levels
+
+    def _levels(self, in0: torch.Tensor, in1: torch.Tensor, normalize: bool) -> torch.Tensor:
+        plan = self._plan_for(in0.shape, in0.device)
+        if not (self.use_graph and in0.is_cuda):
+            return self._run_plan(plan, in0, in1, normalize)
+        if plan['graph'] is None or plan['static'][2] != normalize:
+            s0, s1 = torch.empty_like(in0), torch.empty_like(in1)
+            s0.copy_(in0)
+            s1.copy_(in1)
+            side = torch.cuda.Stream(device=in0.device)
+            side.wait_stream(torch.cuda.current_stream(in0.device))
+            with torch.cuda.stream(side):                # warm-up outside capture: packs the weights
+                self._run_plan(plan, s0, s1, normalize)
+            torch.cuda.current_stream(in0.device).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._run_plan(plan, s0, s1, normalize)
+            plan['graph'], plan['static'] = g, (s0, s1, normalize)
+        plan['static'][0].copy_(in0)
+        plan['static'][1].copy_(in1)
+        plan['graph'].replay()
+        return plan['bufs']['levels']
+
+    def _check(self, in0: torch.Tensor, in1: torch.Tensor):
+        for t in (in0, in1):
+            if not self._exec.injected and not t.is_cuda:
+                raise LamaError('LPIPS runs on the GPU: move the images to the device (there is no CPU path)')
+        if in0.dim() != 4 or in0.shape != in1.shape or in0.shape[1] != 3:
+            raise LamaError(f'LPIPS: two [N,3,H,W] batches of one shape expected, got {tuple(in0.shape)} and {tuple(in1.shape)}')
+        if min(in0.shape[2:]) < 16:
+            raise LamaError(f'LPIPS (VGG-16): planes of at least 16 x 16 survive the four 2x2 pools, got {tuple(in0.shape[2:])}')
+        if in0.shape[0] < 1:
+            raise LamaError('LPIPS: empty batch')
+        if next(self.net.net.parameters()).device != in0.device and not self._exec.injected:
+            raise LamaError(f'LPIPS: the weights are on {next(self.net.net.parameters()).device}, the images on {in0.device}: move the module (.to(device))')
+
+    def forward(self, in0: torch.Tensor, in1: torch.Tensor, retPerLayer: bool = False, normalize: bool = False):
+        """``in0``, ``in1``: [N,3,H,W] in [-1, 1] (``normalize``: in [0, 1], the 2x - 1 then runs inside the scaling launch).  Returns [N,1,1,1], with
+        ``retPerLayer`` (value, [the five per-level terms, each [N,1,1,1]])."""
+        self._check(in0, in1)
+        a, b = in0.contiguous().float(), in1.contiguous().float()
+        try:
+            with self._exec.range_scope(a, self.precision):
+                levels = self._levels(a, b, bool(normalize)).clone()
+        except LamaRangeError as e:
+            if not (self.auto_fallback and self.precision == L.PREC_F16X3):
+                raise
+            warnings.warn(f'lama_amd: {e}; switching LPIPS to the 3-term bf16 split (PREC_BF16X3)')
+            self.set_precision(L.PREC_BF16X3)
+            return self.forward(in0, in1, retPerLayer, normalize)
+        val = levels[0].clone()
+        for l in range(1, levels.shape[0]):        # lpips.py:593-595: the levels are added in order
+            val += levels[l]
+        val = val.view(-1, 1, 1, 1)
+        if retPerLayer:
+            return val, [levels[l].view(-1, 1, 1, 1) for l in range(levels.shape[0])]
+        return val
+
+
+class PerceptualLoss(nn.Module):
+    """lpips.py:18-42.  ``forward(pred, target, normalize=True) -> [N,1,1,1]`` fp32 on the device.  ``backbone``: the VGG-16 conv weights as a state
+    dict or a path to one (torchvision ``features.N.*`` keys or the reference's ``model.net.net.sliceK.N.*``); None looks for torchvision's file in the
+    torch hub cache directory.  ``model_path``: the linear heads (the reference's ``models/lpips_models/vgg.pth``).  Nothing is downloaded.
+    ``set_precision('f16x3' | 'bf16x3' | 'f32')`` selects the convolution arithmetic (default f16x3 with the range fallback to bf16x3)."""
+
+    def __init__(self, model='net-lin', net='vgg', colorspace='rgb', model_path=None, spatial=False, use_gpu=True, backbone=None):
+        super().__init__()
+        if model != 'net-lin':
+            raise NotImplementedError(f"LPIPS on the HIP path is model='net-lin' only (the linearly calibrated metric), not {model!r}")
+        if net not in ('vgg', 'vgg16'):
+            raise NotImplementedError(f"LPIPS on the HIP path is net='vgg' only (what LPIPSScore uses), not {net!r}")
+        if spatial:
+            raise NotImplementedError('LPIPS on the HIP path: spatial=True (upsampled distance maps) is not served')
+        if str(colorspace).lower() != 'rgb':
+            raise NotImplementedError(f'LPIPS on the HIP path: colorspace {colorspace!r} is not served (rgb only)')
+        self.use_gpu = use_gpu
+        self.spatial = spatial
+        self.model = _DistModel(model_path=model_path, backbone=backbone)
+
+    def set_precision(self, precision):
+        self.model.set_precision(L.PREC_NAMES[precision] if isinstance(precision, str) else int(precision))
+        return self
+
+    def set_exec(self, ex):
+        self.model.set_exec(ex)
+        return self
+
+    def forward(self, pred, target, normalize=True):
+        return self.model(target, pred, normalize=bool(normalize))          # lpips.py:42: the model sees (target, pred)
+
+    def forward_per_layer(self, pred, target, normalize=True):
+        """(value, the five per-level terms): ``DistModel.forward(..., retPerLayer=True)`` of the reference."""
+        return self.model(target, pred, retPerLayer=True, normalize=bool(normalize))
+
+
+# ----------------------------------------------------------------------------------------------------
+# losses/base_loss.py: LPIPSScore
+# ----------------------------------------------------------------------------------------------------
+
+def _mean_std(v: np.ndarray) -> dict:
+    return {'mean': v.mean(), 'std': v.std()}
+
+
+class LPIPSScore(nn.Module):
+    """base_loss.py:54-118 (PairwiseScore + LPIPSScore): ``forward`` returns the batch's values flattened to [N] and appends them to
+    ``individual_values``; ``get_value(groups, states)`` -> ({'mean', 'std'}, per-group dict or None); ``reset``."""
+
+    def __init__(self, model='net-lin', net='vgg', model_path=None, use_gpu=True, backbone=None):
+        super().__init__()
+        self.individual_values = None
+        self.score = PerceptualLoss(model=model, net=net, model_path=model_path, use_gpu=use_gpu, spatial=False, backbone=backbone).eval()
+        self.reset()
+
+    def forward(self, pred_batch, target_batch, mask=None):
+        batch_values = self.score(pred_batch, target_batch).flatten()
+        self.individual_values = np.hstack([self.individual_values, batch_values.detach().cpu().numpy()])
+        return batch_values
+
+    def get_value(self, groups=None, states=None):
+        values = self.individual_values if states is None else torch.cat(states, dim=-1).reshape(-1).cpu().numpy()
+        total = _mean_std(values)
+        if groups is None:
+            return total, None
+        groups = np.asarray(groups)
+        return total, {label: _mean_std(values[np.flatnonzero(groups == label)]) for label in np.unique(groups)}
+
+    def reset(self):
+        self.individual_values = []
