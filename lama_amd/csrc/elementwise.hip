@@ -33,6 +33,11 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void mask_compose_kernel(EwParams p)
     }
 }
 
+// One evaluation of mask * pred + (1 - mask) * img for every kernel that blends: left to the compiler, blend_kernel fused the first product
+// and blend_quantize_u8_kernel the second, and a fractional mask then broke forward_u8's contract (its bytes = quantize_u8_hwc(blend(...)))
+// in about one byte per million.  The first product rides in the FMA, the second is rounded on its own -- what blend_kernel compiled to.
+__device__ __forceinline__ float ew_blend(float m, float k, float pred, float img) { return fmaf(m, pred, k * img); }
+
 // inpainted = mask*pred + (1-mask)*img  (trainers/default.py:71)
 __global__ __launch_bounds__(LAMA_NTHREADS) void blend_kernel(EwParams p) {
     long long total = (long long)p.B * p.hw;
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void blend_kernel(EwParams p) {
         float k = 1.0f - m;
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-            p.out[b * p.out_bs + c * p.hw + px] = m * p.pred[b * p.pred_bs + c * p.hw + px] + k * p.img[b * p.img_bs + c * p.hw + px];
+            p.out[b * p.out_bs + c * p.hw + px] = ew_blend(m, k, p.pred[b * p.pred_bs + c * p.hw + px], p.img[b * p.img_bs + c * p.hw + px]);
     }
 }
 
@@ -73,7 +78,7 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void quantize_u8_hwc_kernel(QuantPar
 // ---- round 6 (v110): the predict step fed with what is on disk -- u8 HWC image + u8 mask, unpadded -- instead of fp32 NCHW tensors the host
 // converted and padded (33.6 MB instead of 8.4 MB over PCIe per 8 x 512^2 step, and a float conversion + np.pad per image on the host).
 //   image / 255 in fp32 (evaluation/data.py:12-20: astype('float32') / 255 -- the same IEEE division), symmetric padding at the bottom / right
-//   up to (Hp, Wp) (data.py:29-33: padded row h + i = row h - 1 - i), mask > 0 (bin/predict.py:84) or mask / 255.
+//   up to (Hp, Wp) (data.py:29-33: np.pad(mode='symmetric'), padded row h + i = row h - 1 - i, periodic beyond row 2 h), mask > 0 (bin/predict.py:84) or mask / 255.
 struct U8Params {
     const uint8_t* img;      // [B][Hp][Wp][3], the valid part in the top-left h x w corner of each image's slot
     const uint8_t* mask;     // [B][Hp][Wp]
@@ -85,12 +90,20 @@ struct U8Params {
     uint8_t* out_u8;         // blend + quantise: [B][Hp][Wp][3]
     int B, Hp, Wp, binarize;
 };
+// np.pad(mode='symmetric') for any amount of padding: the mirror is periodic with period 2 n (an image may be smaller than its padding: 3 rows
+// in an 8-row slot, or a scaled 5 x 7 at 0.5 -> 2 x 4 padded to 8 x 8).  Shared by the u8 predict-step ends and resize_u8_kernel.
+__device__ __forceinline__ int ew_symmetric(int y, int n) {
+    if (y < n) return y;                                 // inside the image (every pixel of a full slot): no division
+    const int t = y % (2 * n);
+    return t < n ? t : 2 * n - 1 - t;
+}
 __device__ __forceinline__ bool u8_src(const U8Params& p, int b, int y, int x, long long& pix) {
     int h = p.Hp, w = p.Wp;
     if (p.sizes) { h = p.sizes[2 * b]; w = p.sizes[2 * b + 1]; }
     if (h <= 0 || w <= 0) return false;                  // an empty slot of a partial batch: zeros
-    const int ys = y < h ? y : 2 * h - 1 - y, xs = x < w ? x : 2 * w - 1 - x;
-    pix = ((long long)b * p.Hp + (ys < 0 ? 0 : ys)) * p.Wp + (xs < 0 ? 0 : xs);
+    if (h > p.Hp) h = p.Hp;                              // (never taken for sizes that fit the slot: keeps every read inside it)
+    if (w > p.Wp) w = p.Wp;
+    pix = ((long long)b * p.Hp + ew_symmetric(y, h)) * p.Wp + ew_symmetric(x, w);
     return true;
 }
 // masked_img = cat(img * (1 - mask), mask)  (trainers/default.py:59,67-68) from the u8 operands
@@ -135,7 +148,7 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void blend_quantize_u8_kernel(U8Para
         uint8_t* d = p.out_u8 + i * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float v = (m * p.pred[b * p.pred_bs + c * hw + px] + k * im[c]) * 255.0f;
+            float v = ew_blend(m, k, p.pred[b * p.pred_bs + c * hw + px], im[c]) * 255.0f;
             v = fminf(fmaxf(v, 0.0f), 255.0f);
             d[c] = (uint8_t)v;
         }
@@ -237,11 +250,6 @@ __device__ __forceinline__ LinTaps rz_lin_taps(int d, int ssize, double scale, d
     t.a1 = fx;
     return t;
 }
-// np.pad(mode='symmetric') for any amount of padding (a scaled image may be smaller than its padding: 5 x 7 at 0.5 -> 2 x 4, padded to 8 x 8)
-__device__ __forceinline__ int rz_symmetric(int y, int n) {
-    const int t = y % (2 * n);
-    return t < n ? t : 2 * n - 1 - t;
-}
 __global__ __launch_bounds__(LAMA_NTHREADS) void resize_u8_kernel(ResizeParams p) {
 #pragma clang fp contract(off)
     const long long hw = (long long)p.Hp * p.Wp, total = (long long)p.B * hw;
@@ -253,7 +261,7 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void resize_u8_kernel(ResizeParams p
         float v[3] = {0.0f, 0.0f, 0.0f}, m = 0.0f;
         // an empty slot, or sizes that do not fit the slot / the output view (the host cannot see them without a synchronisation): zeros
         if (h > 0 && w > 0 && dh > 0 && dw > 0 && h <= p.Hs && w <= p.Ws && dh <= p.Hp && dw <= p.Wp) {
-            const int ys = rz_symmetric(y, dh), xs = rz_symmetric(x, dw);
+            const int ys = ew_symmetric(y, dh), xs = ew_symmetric(x, dw);
             const uint8_t* src = p.img + (long long)b * p.Hs * p.Ws * 3;
             const long long rs = (long long)p.Ws * 3;                              // bytes per source row of the slot
             if (p.regime == LAMA_RESIZE_AREA_INT) {

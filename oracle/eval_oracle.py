@@ -23,10 +23,11 @@ def gaussian_1d(window_size: int, sigma: float = 1.5) -> torch.Tensor:
 
 
 def ssim_per_image(img1: torch.Tensor, img2: torch.Tensor, window_size: int = 11) -> torch.Tensor:
-    """ssim.py:42-71 with size_average=False: [B] means of the SSIM map."""
+    """ssim.py:42-71 with size_average=False: [B] means of the SSIM map.  fp64 images evaluate the same expression in fp64 (the fp32 window
+    values, every product and sum in fp64): the reference of the per-kernel tests."""
     c = img1.shape[1]
-    g = gaussian_1d(window_size).unsqueeze(1)
-    window = g.mm(g.t()).float()[None, None].expand(c, 1, window_size, window_size).contiguous()
+    g = gaussian_1d(window_size).unsqueeze(1).to(img1.dtype)
+    window = g.mm(g.t())[None, None].expand(c, 1, window_size, window_size).contiguous()
     pad = window_size // 2
     conv = lambda x: F.conv2d(x, window, padding=pad, groups=c)          # noqa: E731
     mu1, mu2 = conv(img1), conv(img2)

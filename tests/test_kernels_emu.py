@@ -540,14 +540,16 @@ WINO_CASES = [
 ]
 
 
-@pytest.mark.parametrize('prec', [L.PREC_BF16X3, L.PREC_F16X3], ids=['bf16x3', 'f16x3'])
-@pytest.mark.parametrize('case', WINO_CASES, ids=lambda c: f"c{c['cin']}o{c['cout']}_{c['H']}x{c['W']}b{c['B']}")
-def test_winograd_conv3x3_emulated(case, prec, monkeypatch):
-    """lama_winograd_conv3x3_fwd against the plain torch conv (reflect pad 1) -- the same function as lama_conv2d_fwd on this layer --
-    and against the direct HIP kernel on the same inputs."""
-    lib = emu_lib()
-    if case.get('qr'):
-        monkeypatch.setenv('LAMA_WG_QR', str(case['qr']))
+# the cases on which the deferred-output and the zero-padding checks below run (tests/test_glue_kernels_gpu.py reruns them on the MI355X)
+WINO_DEFER_CASES = [c for c in WINO_CASES if c['cin'] == 32 and c['cout'] == 128]
+WINO_ZERO_CASES = [c for c in WINO_CASES if c['cin'] <= 64 and c['cout'] == 128]
+WINO_TOL = {L.PREC_BF16X3: dict(atol=1.2e-3, rtol=4e-4), L.PREC_F16X3: dict(atol=3e-4, rtol=1e-4)}   # sums of 4 inputs x transformed weights: 2x the direct kernel's bound
+WINO_ID = lambda c: f"c{c['cin']}o{c['cout']}_{c['H']}x{c['W']}b{c['B']}"   # noqa: E731
+
+
+def wino_operands(lib, case, prec, dev='cpu'):
+    """The operands of one WINO_CASES entry on ``dev``, the packed weights, the workspace and the plain torch result (reflect pad 1)."""
+    import types
     g = torch.Generator().manual_seed(5)
     B, cin, cout, H, W = case['B'], case['cin'], case['cout'], case['H'], case['W']
     x = torch.randn(B, cin + 2, H, W, generator=g)[:, 1:1 + cin]            # a channel slice of a wider buffer
@@ -559,49 +561,96 @@ def test_winograd_conv3x3_emulated(case, prec, monkeypatch):
     ref0 = _conv_ref(x, w, 1, 1, True, False, None, 0, None, scale=scale)
     resid = torch.randn(ref0.shape, generator=g) if case['resid'] else None
     ref = _conv_ref(x, w, 1, 1, True, False, bias, case['act'], resid, scale=scale)
+    o = types.SimpleNamespace(g=g, B=B, cin=cin, cout=cout, H=H, W=W, act=case['act'], prec=prec, dev=dev, x=x, w=w, scale=scale, bias=bias,
+                              resid=resid, ref=ref, tol=WINO_TOL[prec])
+    o.st = 0 if dev == 'cpu' else torch.cuda.current_stream().cuda_stream
+    o.xbuf = xbuf.to(dev)
+    o.bias_d = None if bias is None else bias.to(dev)
+    o.resid_d = None if resid is None else resid.to(dev)
+    o.wp = lib.pack_winograd_weight(w.to(dev), None if scale is None else scale.to(dev), prec)
+    o.ws = torch.zeros(lib.winograd_workspace_bytes(B, cout, H, W) // 4, device=dev)
+    return o
+
+
+def wino_run(lib, o, ybuf, ws=None, **kw):
+    """lama_winograd_conv3x3_fwd of the operands ``o`` into channels [2, 2 + cout) of ``ybuf``."""
+    return lib.winograd_conv3x3(L.view(o.xbuf, 1, o.cin), o.wp, L.view(ybuf, 2, o.cout), o.B, o.ws if ws is None else ws, o.bias_d, o.act,
+                                None if o.resid_d is None else L.view(o.resid_d), precision=o.prec, stream=o.st, **kw)
+
+
+def _dev_sync(dev):
+    if dev != 'cpu':
+        torch.cuda.synchronize()
+
+
+def check_winograd_deferred_out(lib, o, ybuf):
+    """round 4 (v108): the GEMM half alone (LAMA_CONV_DEFER_OUT), then the output transform on its own / inside an rfft2 launch -- the same
+    bits as the one-call form left in ``ybuf`` (sentinel channels included); the deferred call itself writes nothing."""
+    dev, st = o.dev, o.st
+    for fused in (False, True):
+        y2 = torch.full((o.B, o.cout + 3, o.H, o.W), 7.0, device=dev)
+        o.ws.zero_()
+        pend = wino_run(lib, o, y2, defer_out=True)
+        _dev_sync(dev)
+        assert float(y2.min()) == 7.0 and float(y2.max()) == 7.0 and pend is not None
+        if fused:
+            xf = torch.randn(1, 2, 64, 64, generator=o.g).to(dev)
+            sp, sp0 = torch.zeros(1, 4, 64, 33, device=dev), torch.zeros(1, 4, 64, 33, device=dev)
+            lib.rfft2_wino_out(L.view(xf), L.view(sp), 1, None, pend, o.ws, stream=st)
+            lib.rfft2(L.view(xf), L.view(sp0), 1, None, stream=st)
+            _dev_sync(dev)
+            assert torch.equal(sp, sp0)
+            xs, sps = xf[:, :, :32, :32].contiguous(), torch.zeros(1, 4, 32, 17, device=dev)
+            with pytest.raises(L.LamaError) as ei:                       # 32 x 32 planes: no kernel does both
+                lib.rfft2_wino_out(L.view(xs), L.view(sps), 1, None, pend, o.ws, stream=st)
+            assert ei.value.code == L.ERR_UNSUPPORTED
+        else:
+            lib.winograd_out(pend, o.ws, stream=st)
+        _dev_sync(dev)
+        assert torch.equal(y2, ybuf)
+
+
+def check_winograd_pad_zero(lib, o, ybuf):
+    """round 4: zero padding (the dgrad convs of the reverse pass): rows / columns outside the plane read as zeros, first / last band and
+    column.  Overwrites channels [2, 2 + cout) of ``ybuf``."""
+    refz = _conv_ref(o.x, o.w, 1, 1, False, False, o.bias, o.act, o.resid, scale=o.scale)
+    flag = torch.zeros(1, dtype=torch.int32, device=o.dev)
+    wino_run(lib, o, ybuf, range_flag=flag, pad_mode=L.PAD_ZERO)
+    _dev_sync(o.dev)
+    yz = ybuf[:, 2:2 + o.cout].cpu()
+    assert torch.allclose(yz, refz, **o.tol), float((yz - refz).abs().max())
+    assert float((refz - o.ref).abs().max()) > 0.1
+    assert float(ybuf[:, :2].min()) == 7.0 and float(ybuf[:, -1].max()) == 7.0 and int(flag) == 0
+
+
+@pytest.mark.parametrize('prec', [L.PREC_BF16X3, L.PREC_F16X3], ids=['bf16x3', 'f16x3'])
+@pytest.mark.parametrize('case', WINO_CASES, ids=WINO_ID)
+def test_winograd_conv3x3_emulated(case, prec, monkeypatch):
+    """lama_winograd_conv3x3_fwd against the plain torch conv (reflect pad 1) -- the same function as lama_conv2d_fwd on this layer --
+    and against the direct HIP kernel on the same inputs; then the deferred output transform and the zero-padded form (the two check
+    functions above, shared with the GPU suite)."""
+    lib = emu_lib()
+    if case.get('qr'):
+        monkeypatch.setenv('LAMA_WG_QR', str(case['qr']))
+    B, cin, cout, H, W = case['B'], case['cin'], case['cout'], case['H'], case['W']
+    o = wino_operands(lib, case, prec)
+    ref, tol = o.ref, o.tol
     assert lib.winograd_supported(cout, cin, H, W, prec) and not lib.winograd_supported(cout, cin, 3, W, prec) and not lib.winograd_supported(cout, cin, H, 6, prec)
     assert not lib.winograd_supported(cout, cin, H, W, L.PREC_F32) and not lib.winograd_supported(96, cin, H, W, prec)
-    wp = lib.pack_winograd_weight(w, scale, prec)
-    ws = torch.zeros(lib.winograd_workspace_bytes(B, cout, H, W) // 4)
     ybuf = torch.full((B, cout + 3, H, W), 7.0)
     flag = torch.zeros(1, dtype=torch.int32)
-    lib.winograd_conv3x3(L.view(xbuf, 1, cin), wp, L.view(ybuf, 2, cout), B, ws, bias, case['act'], None if resid is None else L.view(resid),
-                         precision=prec, range_flag=flag)
+    wino_run(lib, o, ybuf, range_flag=flag)
     y = ybuf[:, 2:2 + cout]
-    tol = dict(atol=1.2e-3, rtol=4e-4) if prec == L.PREC_BF16X3 else dict(atol=3e-4, rtol=1e-4)   # sums of 4 inputs x transformed weights: 2x the direct kernel's bound
     assert torch.allclose(y, ref, **tol), float((y - ref).abs().max())
     assert float(ybuf[:, :2].min()) == 7.0 and float(ybuf[:, -1].max()) == 7.0 and int(flag) == 0
-    wd = lib.pack_conv_weight(w, scale, precision=prec)
+    wd = lib.pack_conv_weight(o.w, o.scale, precision=prec)
     yd = torch.zeros(B, cout, H, W)
-    lib.conv2d(L.view(xbuf, 1, cin), wd, L.view(yd), B, 3, 1, 1, L.PAD_REFLECT, False, bias, case['act'], None if resid is None else L.view(resid),
+    lib.conv2d(L.view(o.xbuf, 1, cin), wd, L.view(yd), B, 3, 1, 1, L.PAD_REFLECT, False, o.bias, case['act'], None if o.resid is None else L.view(o.resid),
                precision=prec)
     assert float((y - yd).abs().max()) < 2 * tol['atol']
     with pytest.raises(L.LamaError):                                         # workspace too small
-        lib.winograd_conv3x3(L.view(xbuf, 1, cin), wp, L.view(ybuf, 2, cout), B, ws[:16], bias, case['act'], None, precision=prec)
-    if case['cin'] == 32 and cout == 128:
-        # round 4 (v108): the GEMM half alone (LAMA_CONV_DEFER_OUT), then the output transform on its own / inside an rfft2 launch -- the same bits
-        for fused in (False, True):
-            y2 = torch.full((B, cout + 3, H, W), 7.0)
-            ws.zero_()
-            pend = lib.winograd_conv3x3(L.view(xbuf, 1, cin), wp, L.view(y2, 2, cout), B, ws, bias, case['act'], None if resid is None else L.view(resid),
-                                        precision=prec, defer_out=True)
-            assert float(y2.min()) == 7.0 and pend is not None
-            if fused:
-                xf = torch.randn(1, 2, 64, 64, generator=g)
-                sp, sp0 = torch.zeros(1, 4, 64, 33), torch.zeros(1, 4, 64, 33)
-                lib.rfft2_wino_out(L.view(xf), L.view(sp), 1, None, pend, ws)
-                lib.rfft2(L.view(xf), L.view(sp0), 1, None)
-                assert torch.equal(sp, sp0)
-                with pytest.raises(L.LamaError) as ei:                       # 32 x 32 planes: no kernel does both
-                    lib.rfft2_wino_out(L.view(xf[:, :, :32, :32].contiguous()), L.view(torch.zeros(1, 4, 32, 17)), 1, None, pend, ws)
-                assert ei.value.code == L.ERR_UNSUPPORTED
-            else:
-                lib.winograd_out(pend, ws)
-            assert torch.equal(y2, ybuf)
-    if case['cin'] <= 64 and cout == 128:
-        # round 4: zero padding (the dgrad convs of the reverse pass): rows / columns outside the plane read as zeros, first / last band and column
-        refz = _conv_ref(x, w, 1, 1, False, False, bias, case['act'], resid, scale=scale)
-        lib.winograd_conv3x3(L.view(xbuf, 1, cin), wp, L.view(ybuf, 2, cout), B, ws, bias, case['act'], None if resid is None else L.view(resid),
-                             precision=prec, range_flag=flag, pad_mode=L.PAD_ZERO)
-        assert torch.allclose(ybuf[:, 2:2 + cout], refz, **tol), float((ybuf[:, 2:2 + cout] - refz).abs().max())
-        assert float((refz - ref).abs().max()) > 0.1
+        wino_run(lib, o, ybuf, ws=o.ws[:16])
+    if case in WINO_DEFER_CASES:
+        check_winograd_deferred_out(lib, o, ybuf)
+    if case in WINO_ZERO_CASES:
+        check_winograd_pad_zero(lib, o, ybuf)
