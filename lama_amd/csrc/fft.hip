@@ -7,7 +7,21 @@
 // exist here: the forward kernel writes the two planes the spectral 1x1 GEMM reads, the inverse
 // kernel reads the two planes it wrote.
 //
-// Fast path (h, w powers of two, 16..128): one workgroup owns PPW whole planes in LDS.
+// Six kernel families serve the two entry points.  fft_route() (host half, below the kernels) sends a call to the FIRST row that takes it;
+// both directions use the same rows.  "aligned": every real-side view starts on, and strides by, 4 elements (16 B fp32, 8 B fp16).
+//   1. plane in LDS, power of two : h, w powers of two in 16..128, aligned.  One workgroup owns ppw whole planes.  Kernels: one-buffer
+//                                   64 x 64 (rfft2_ip64 / irfft2_ip64; the forward one also with the Winograd output transform of the layer
+//                                   before) and 128 x 128 (ipn) where the spectrum view is aligned too; else the two-buffer *_lds kernels, sized
+//                                   instances at 32 / 64 / 128 squares (profiling build: sequential-plane and traced variants), generic otherwise
+//   2. one-launch mixed radix     : any h, w whose plane fits one workgroup's LDS (fft_mr_dev.inc); no workspace
+//   -- from here on the float2 workspace [B*C][h][wf] is required (LAMA_ERR_WORKSPACE) --
+//   3. fq                         : fp32 256 x 256, aligned views and workspace: compile-time rows + columns pair; the only kernels that apply a mask
+//   4. two-pass power of two      : h, w powers of two in 16..1024 that row 1 cannot hold: rows + columns pair
+//   5. two-launch mixed radix     : mr2_* rows + columns pair (fft_mr_dev.inc), lengths whose factors its passes take
+//   6. separable DFT              : the last resort, rows + columns pair, O(n) more flops; LAMA_ERR_UNSUPPORTED beyond 160 KB of LDS
+// A masked entry is served by row 3 only, the Winograd-output entry by the 64 x 64 one-buffer kernel of row 1 only (LAMA_ERR_UNSUPPORTED otherwise).
+//
+// The plane-in-LDS power-of-two kernels:
 //   rows  : two real rows are transformed as ONE complex FFT (z = row_2f + i*row_2f+1) and untangled,
 //   cols  : the purely real DC and Nyquist columns are packed into ONE complex column, so a plane
 //           costs h/2 row FFTs of length w plus w/2 column FFTs of length h (both directions);
@@ -17,8 +31,6 @@
 //   inverse: irfftn on a non-Hermitian spectrum = complex inverse along h, then c2r along w that
 //           ignores Im of bins 0 and w/2.  Re(ifft_h(col)) of those two columns equals the inverse of
 //           their Hermitian-symmetrised parts, which are packed into one complex column again.
-// Generic path (any h, w): separable direct DFT, rows and columns in two kernels through a float2
-// workspace [B*C][h][wf] (O(n) more flops; used for non power-of-two planes and planes > 128).
 #include "common.h"
 
 #define FFT_SQRT1_2 0.70710678118654752440f
@@ -1669,11 +1681,6 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void fq_rows_inv_kernel(FftParams p,
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// two-pass LDS FFT: power-of-two planes the one-pass kernels cannot hold
-bool fft_two_pass_ok(int h, int w) {
-    return lama_is_pow2(h) && lama_is_pow2(w) && h >= 16 && w >= 16 && h <= 1024 && w <= 1024 && (h > 128 || w > 128);
-}
-
 // one Cooley-Tukey split of the generic path: n = n1 * n2 with n1 the largest divisor <= sqrt(n) (1 for a prime)
 static void fft_split1(int n, int& n1, int& n2) {
     n1 = 1;
@@ -1681,12 +1688,9 @@ static void fft_split1(int n, int& n1, int& n2) {
         if (n % d == 0) n1 = d;
     n2 = n / n1;
 }
-static void fft_dft_split(FftParams& p) {
-    fft_split1(p.w, p.w1, p.w2);
-    fft_split1(p.h, p.h1, p.h2);
-}
 
-bool fft_fast_ok(int h, int w) { return lama_is_pow2(h) && lama_is_pow2(w) && h >= 16 && w >= 16 && h <= 128 && w <= 128; }
+// plane-in-LDS kernels: powers of two from 16 to 128, views that allow the vector accesses.  They need no workspace.
+bool fft_lds_ok(int h, int w, bool real_al) { return lama_is_pow2(h) && lama_is_pow2(w) && h >= 16 && w >= 16 && h <= 128 && w <= 128 && real_al; }
 // the compile-time two-pass kernels (fp32 planes of 256 x 256); LAMA_FFT_Q=0 (profiling build) keeps the generic two-pass kernels
 bool fq_ok(int h, int w, bool hf) {
 #ifdef LAMA_PROFILING
@@ -1806,16 +1810,6 @@ bool mr2_fill(MrParams& q, const FftParams& p, size_t* lds_rows, size_t* lds_col
     return *lds_rows <= 160 * 1024 && *lds_cols <= 160 * 1024;
 }
 
-#ifdef MR_BENCH_ONLY      // tools/ubench/mk_mr_bench.sh: one instantiation per kernel (compile time of the ablation builds)
-#define MR_GO(name, nt, lds, q) hipLaunchKernelGGL((name<MR_BENCH_ONLY, false>), dim3((q).f.nplanes), dim3(MR_BENCH_ONLY), lds, st, q)
-#else
-#define MR_GO(name, nt, lds, q)                                                                     \
-    do {                                                                                            \
-        if (nt == 256) FFT_GO(name, (256), dim3((q).f.nplanes), dim3(256), lds, q);                 \
-        else FFT_GO(name, (1024), dim3((q).f.nplanes), dim3(1024), lds, q);                         \
-    } while (0)
-#endif
-
 bool fft_args_ok(const lama_tensor* real, const lama_tensor* spec, int batch) {
     if (!real || !spec || !real->ptr || !spec->ptr || batch <= 0) return false;
     if (real->C <= 0 || real->H <= 0 || real->W <= 0) return false;
@@ -1825,272 +1819,229 @@ bool fft_args_ok(const lama_tensor* real, const lama_tensor* spec, int batch) {
     return true;
 }
 
-}  // namespace
+// the float2 workspace [B*C][h][wf] of the two-launch families
+size_t fft_ws_bytes(size_t nplanes, int h, int w) { return nplanes * h * (w / 2 + 1) * sizeof(float2); }
 
-extern "C" size_t lama_fft_workspace_bytes(int32_t batch, int32_t C, int32_t h, int32_t w) {
-    if (batch <= 0 || C <= 0 || h <= 0 || w <= 0) return 0;
-    if (fft_fast_ok(h, w)) return 0;
-    return (size_t)batch * C * h * (w / 2 + 1) * sizeof(float2);
-}
+// The route of one call: the family (in routing order, see the table at the top of this file) and what its launches need.
+enum FftFamily { FFT_LDS, FFT_MR1, FFT_FQ, FFT_2P, FFT_MR2, FFT_DFT };
+enum FftLdsKind { LDS_WINO64, LDS_IP64, LDS_IP128, LDS_TRACE64, LDS_SEQ, LDS_SIZED, LDS_GENERIC };
+struct FftRoute {
+    FftFamily family;
+    FftLdsKind kind;         // FFT_LDS: which of its kernels
+    int seq, nt;             // LDS_SEQ: planes a workgroup walks (2 or 3); FFT_MR1: threads per workgroup (256 or 1024)
+    size_t lds, lds_cols;    // LDS bytes of the one launch, or of the row and the column launch
+    MrParams q;              // FFT_MR1 / FFT_MR2: the pass lists around a copy of the FftParams
+};
 
-// launch kernel<targs..., HF> with HF = (dtype == LAMA_DT_F16); targs is a parenthesised template-argument list
-#define FFT_UNPAREN(...) __VA_ARGS__
-#define FFT_GO(name, targs, grid, blk, lds, ...)                                                        \
-    do {                                                                                                \
-        if (hf) hipLaunchKernelGGL((name<FFT_UNPAREN targs, true>), grid, blk, lds, st, __VA_ARGS__);   \
-        else hipLaunchKernelGGL((name<FFT_UNPAREN targs, false>), grid, blk, lds, st, __VA_ARGS__);     \
-    } while (0)
-
-static int rfft2_impl(void* stream, const lama_tensor* x, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
-                      void* workspace, size_t workspace_bytes, const WoParams* wo = nullptr) {
-    if (!fft_args_ok(x, spec, batch)) return LAMA_ERR_BAD_ARG;
-    if (x->dtype != spec->dtype || (x->dtype != LAMA_DT_F32 && x->dtype != LAMA_DT_F16)) return LAMA_ERR_UNSUPPORTED;
-    const bool hf = x->dtype == LAMA_DT_F16;
-    const int es = hf ? 2 : 4;                    // vector accesses are 4 elements: 16-byte (fp32) / 8-byte (fp16) alignment
-    const uintptr_t amask = hf ? 7 : 15;
-    FftParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = x->ptr;
-    p.x_bstride = x->batch_stride;
-    p.spec = spec->ptr;
-    p.spec_bstride = spec->batch_stride;
-    p.C = x->C; p.h = x->H; p.w = x->W; p.wf = x->W / 2 + 1;
-    p.nplanes = batch * x->C;
-    p.scale = (float)(1.0 / sqrt((double)p.h * (double)p.w));
-    hipStream_t st = (hipStream_t)stream;
-    const bool spec_al = (((uintptr_t)spec->ptr | (uintptr_t)(spec->batch_stride * es)) & amask) == 0;
-    if (mask) {   // only the compile-time two-pass kernels apply a mask: anything else is the caller's separate lama_act_bwd launch
-        if (!mask->ptr || mask->dtype != LAMA_DT_F32 || mask->C != spec->C || mask->H != spec->H || mask->W != spec->W) return LAMA_ERR_BAD_ARG;
-        if (!(fq_ok(p.h, p.w, hf) && (((uintptr_t)x->ptr | (uintptr_t)(x->batch_stride * 4) | (uintptr_t)workspace) & 15) == 0)) return LAMA_ERR_UNSUPPORTED;
-        p.mask = (const float*)mask->ptr;
-        p.mask_bstride = mask->batch_stride;
-    }
-    if (fft_fast_ok(p.h, p.w) && (((uintptr_t)x->ptr | (uintptr_t)(x->batch_stride * es)) & amask) == 0) {
-        p.ppw = fft_ppw(p.h, p.w);
-        size_t lds = fft_lds_bytes(p.h, p.w, p.ppw);
-        const dim3 grid(lama_ceil_div(p.nplanes, p.ppw)), blk(LAMA_NTHREADS);
-        const bool even = p.nplanes % p.ppw == 0;
+// Decides which kernels serve a call, for both directions: every predicate of the cascade is here and nowhere else.  `real_al` / `spec_al`:
+// the real-side views (x; y, resid and the inverse mask) / the spectrum allow the 4-element vector accesses; `wo`: a Winograd output
+// transform rides along (forward only).  Completes the fields of `p` that follow from the route (ppw, trace, prio, the DFT's split).
+// LAMA_OK and `r`, or the code of a call that no kernel serves -- nothing is launched then.
+int fft_route(FftParams& p, bool inv, bool hf, bool real_al, bool spec_al, bool mask, bool wo, const void* workspace, size_t workspace_bytes,
+              FftRoute& r) {
+    const int h = p.h, w = p.w;
+    const auto is = [&r](FftFamily f) { r.family = f; return (int)LAMA_OK; };
+    const auto fq = [&] { return fq_ok(h, w, hf) && real_al && ((uintptr_t)workspace & 15) == 0; };   // (fp32: real_al = 16-byte aligned)
+    // only the compile-time two-pass kernels apply a mask: anything else is the caller's separate lama_act_bwd launch
+    if (mask && !fq()) return LAMA_ERR_UNSUPPORTED;
+    if (fft_lds_ok(h, w, real_al)) {
+        p.ppw = fft_ppw(h, w);
         p.trace = hf ? nullptr : fft_trace_buf();
         p.prio = lama_side_prio();
+        const bool even = p.nplanes % p.ppw == 0, sq64 = h == 64 && w == 64, sq128 = h == 128 && w == 128;
+        const bool one_buf = fft_inplace() && spec_al;      // the one-buffer kernels, a workgroup per plane
+        r.lds = sq64 ? (size_t)(IP_N + IP_BUF) * sizeof(float2) : (size_t)(128 + 128 * 65) * sizeof(float2);
         if (wo) {   // with the Winograd output transform of the layer before in the same launch: the one-buffer 64 x 64 kernel only
-            if (!(p.h == 64 && p.w == 64 && !hf && fft_inplace() && spec_al)) return LAMA_ERR_UNSUPPORTED;
+            if (!(sq64 && !hf && one_buf)) return LAMA_ERR_UNSUPPORTED;
             p.trace = nullptr;
+            r.kind = LDS_WINO64;
+        } else if (!p.trace && sq64 && one_buf) r.kind = LDS_IP64;
+        else if (sq128 && one_buf) r.kind = LDS_IP128;
+        else {      // the two-buffer kernels, ppw planes per workgroup: sized instances where one exists
+            r.lds = fft_lds_bytes(h, w, p.ppw);
+            r.kind = even && ((!hf && (sq64 || sq128) && p.ppw == 1) || (h == 32 && w == 32 && p.ppw == 4)) ? LDS_SIZED : LDS_GENERIC;
+#ifdef LAMA_PROFILING
+            if (!hf && p.trace && even && sq64) r.kind = LDS_TRACE64;
+            else if (!hf && spec_al && p.ppw == 1 && (sq64 || sq128) && (r.seq = fft_seq(p.nplanes)) > 1) r.kind = LDS_SEQ;
+#endif
+        }
+        return is(FFT_LDS);
+    }
+    if (wo) return LAMA_ERR_UNSUPPORTED;
+    if (!mask && !(fq() && workspace)) {   // any plane that fits one workgroup's LDS: the mixed-radix one-pass kernel (no workspace)
+        r.nt = mr_threads(h, w, &r.lds);
+        if (r.nt && mr_fill(r.q, p, r.nt)) return is(FFT_MR1);
+    }
+    if (!workspace || workspace_bytes < fft_ws_bytes((size_t)p.nplanes, h, w)) return LAMA_ERR_WORKSPACE;
+    if (fq()) {       // (a masked call ends here at the latest)
+        r.lds = (size_t)(FQ_N + FQ_PAIRS * (FQ_N + 1)) * sizeof(float2);
+        r.lds_cols = (size_t)(FQ_N + FQ_N * FQ_CP) * sizeof(float2);
+        return is(FFT_FQ);
+    }
+    // two-pass LDS FFT: power-of-two planes the one-pass kernels cannot hold
+    if (lama_is_pow2(h) && lama_is_pow2(w) && h >= 16 && w >= 16 && h <= 1024 && w <= 1024 && (h > 128 || w > 128)) {
+        r.lds = ((size_t)w + 2 * (size_t)FFT2P_PAIRS * (w + 1)) * sizeof(float2);
+        r.lds_cols = ((size_t)h + 2 * (size_t)FFT2P_COLS * (h + 1)) * sizeof(float2);
+        return is(FFT_2P);
+    }
+    // any other plane: the two-launch form of the mixed-radix passes (fft_mr_dev.inc); lengths with a prime factor too large for them keep the DFT
+    if (mr2_fill(r.q, p, &r.lds, &r.lds_cols)) return is(FFT_MR2);
+    fft_split1(w, p.w1, p.w2);
+    fft_split1(h, p.h1, p.h2);
+    r.lds = inv ? ((size_t)w * (1 + 2 * DFT_ROWS_PER_WG) + (size_t)DFT_ROWS_PER_WG * p.w1) * sizeof(float2)
+                : (size_t)w * sizeof(float2) + (size_t)DFT_ROWS_PER_WG * ((size_t)(w + p.w1) * sizeof(float2) + w * sizeof(float));
+    r.lds_cols = (size_t)h * sizeof(float2) * (1 + 2 * DFT_COLS_PER_WG);
+    return r.lds > 160 * 1024 || r.lds_cols > 160 * 1024 ? (int)LAMA_ERR_UNSUPPORTED : is(FFT_DFT);
+}
+
+}  // namespace
+
+// callers allocate for aligned views: none where the plane-in-LDS kernels serve them, the two-launch families' elsewhere
+extern "C" size_t lama_fft_workspace_bytes(int32_t batch, int32_t C, int32_t h, int32_t w) {
+    if (batch <= 0 || C <= 0 || h <= 0 || w <= 0) return 0;
+    return fft_lds_ok(h, w, true) ? 0 : fft_ws_bytes((size_t)batch * C, h, w);
+}
+
+// Launch fwd<targs...> or inv<targs...> by the direction INV of the enclosing launcher; targs is a parenthesised template-argument list.
+// FFT_GO appends HF = (dtype == LAMA_DT_F16) to it, FFT_GO32 is for kernels that exist for fp32 only, FFT_GO1 for one name in both directions.
+#define FFT_UNPAREN(...) __VA_ARGS__
+#define FFT_TARGS(...) __VA_ARGS__ __VA_OPT__(,)
+#define FFT_GO32(fwd, inv, targs, grid, blk, lds, ...)                                                              \
+    do {                                                                                                            \
+        if constexpr (INV) hipLaunchKernelGGL((inv<FFT_UNPAREN targs>), grid, blk, lds, st, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((fwd<FFT_UNPAREN targs>), grid, blk, lds, st, __VA_ARGS__);                         \
+    } while (0)
+#define FFT_GO(fwd, inv, targs, grid, blk, lds, ...)                                                                \
+    do {                                                                                                            \
+        if (hf) FFT_GO32(fwd, inv, (FFT_TARGS targs true), grid, blk, lds, __VA_ARGS__);                            \
+        else FFT_GO32(fwd, inv, (FFT_TARGS targs false), grid, blk, lds, __VA_ARGS__);                              \
+    } while (0)
+#define FFT_GO1(name, targs, grid, blk, lds, ...) FFT_GO(name, name, targs, grid, blk, lds, __VA_ARGS__)
+// the two launches through the workspace: rows then columns forward, columns then rows inverse
+#define FFT_ROWS_COLS(rows, cols)                                     \
+    do {                                                              \
+        if constexpr (INV) { cols; LAMA_CHECK_LAUNCH(); }             \
+        rows;                                                         \
+        LAMA_CHECK_LAUNCH();                                          \
+        if constexpr (!INV) { cols; LAMA_CHECK_LAUNCH(); }            \
+    } while (0)
+
+// The launches of a route.  Forward and inverse differ in the kernel names, in the INV argument of the column kernels and in the order of
+// the two launches through the workspace.
+template <bool INV>
+static int fft_launch(hipStream_t st, FftRoute& r, const FftParams& p, bool hf, float2* ws, const WoParams* wo) {
+    const dim3 blk(LAMA_NTHREADS), planes(p.nplanes);
+    const MrParams& q = r.q;
+    switch (r.family) {
+    case FFT_LDS: {
+        const dim3 grid(lama_ceil_div(p.nplanes, p.ppw)), seq(p.nplanes / (r.kind == LDS_SEQ ? r.seq : 1));
+        if (r.kind == LDS_WINO64) {
             int nout = 512;                            // two streaming workgroups per CU next to the six FFT workgroups
 #ifdef LAMA_PROFILING
             { static const int v = lama_env_int("LAMA_FFT_NOUT", 0); if (v > 0) nout = v; }
 #endif
-            hipLaunchKernelGGL(rfft2_ip64_wino_out_kernel, dim3(nout + p.nplanes), blk, (size_t)(IP_N + IP_BUF) * sizeof(float2), st, p, *wo, nout);
-        } else if (!p.trace && p.h == 64 && p.w == 64 && fft_inplace() && spec_al)
-            FFT_GO(rfft2_ip64_kernel, (false), dim3(p.nplanes), blk, (size_t)(IP_N + IP_BUF) * sizeof(float2), p);
-        else if (p.h == 128 && p.w == 128 && fft_inplace() && spec_al)
-            FFT_GO(rfft2_ipn_kernel, (128), dim3(p.nplanes), blk, (size_t)(128 + 128 * 65) * sizeof(float2), p);
+            if constexpr (!INV) hipLaunchKernelGGL(rfft2_ip64_wino_out_kernel, dim3(nout + p.nplanes), blk, r.lds, st, p, *wo, nout);
+        } else if (r.kind == LDS_IP64) FFT_GO(rfft2_ip64_kernel, irfft2_ip64_kernel, (false), planes, blk, r.lds, p);
+        else if (r.kind == LDS_IP128) FFT_GO(rfft2_ipn_kernel, irfft2_ipn_kernel, (128), planes, blk, r.lds, p);
 #ifdef LAMA_PROFILING
-        else if (!hf && p.trace && even && p.h == 64 && p.w == 64) hipLaunchKernelGGL((rfft2_lds_kernel<64, 64, 1, 1, true>), grid, blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 2 && p.h == 64 && p.w == 64) hipLaunchKernelGGL((rfft2_lds_kernel<64, 64, 1, 2>), dim3(p.nplanes / 2), blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 3 && p.h == 64 && p.w == 64) hipLaunchKernelGGL((rfft2_lds_kernel<64, 64, 1, 3>), dim3(p.nplanes / 3), blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 2 && p.h == 128 && p.w == 128) hipLaunchKernelGGL((rfft2_lds_kernel<128, 128, 1, 2>), dim3(p.nplanes / 2), blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 3 && p.h == 128 && p.w == 128) hipLaunchKernelGGL((rfft2_lds_kernel<128, 128, 1, 3>), dim3(p.nplanes / 3), blk, lds, st, p);
+        else if (r.kind == LDS_TRACE64) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (64, 64, 1, 1, true), grid, blk, r.lds, p);
+        else if (r.kind == LDS_SEQ && p.h == 64 && r.seq == 2) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (64, 64, 1, 2), seq, blk, r.lds, p);
+        else if (r.kind == LDS_SEQ && p.h == 64) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (64, 64, 1, 3), seq, blk, r.lds, p);
+        else if (r.kind == LDS_SEQ && r.seq == 2) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (128, 128, 1, 2), seq, blk, r.lds, p);
+        else if (r.kind == LDS_SEQ) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (128, 128, 1, 3), seq, blk, r.lds, p);
 #endif
-        else if (!hf && even && p.h == 64 && p.w == 64 && p.ppw == 1) hipLaunchKernelGGL((rfft2_lds_kernel<64, 64, 1>), grid, blk, lds, st, p);
-        else if (even && p.h == 32 && p.w == 32 && p.ppw == 4) FFT_GO(rfft2_lds_kernel, (32, 32, 4, 1, false), grid, blk, lds, p);
-        else if (!hf && even && p.h == 128 && p.w == 128 && p.ppw == 1) hipLaunchKernelGGL((rfft2_lds_kernel<128, 128, 1>), grid, blk, lds, st, p);
-        else FFT_GO(rfft2_lds_kernel, (0, 0, 0, 1, false), grid, blk, lds, p);
-        LAMA_CHECK_LAUNCH();
-        return LAMA_OK;
+        else if (r.kind == LDS_SIZED && p.h == 64) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (64, 64, 1), grid, blk, r.lds, p);
+        else if (r.kind == LDS_SIZED && p.h == 32) FFT_GO(rfft2_lds_kernel, irfft2_lds_kernel, (32, 32, 4, 1, false), grid, blk, r.lds, p);
+        else if (r.kind == LDS_SIZED) FFT_GO32(rfft2_lds_kernel, irfft2_lds_kernel, (128, 128, 1), grid, blk, r.lds, p);
+        else FFT_GO(rfft2_lds_kernel, irfft2_lds_kernel, (0, 0, 0, 1, false), grid, blk, r.lds, p);
+        break;
     }
-    if (wo) return LAMA_ERR_UNSUPPORTED;
-    const bool fq = fq_ok(p.h, p.w, hf) && (((uintptr_t)x->ptr | (uintptr_t)(x->batch_stride * 4) | (uintptr_t)workspace) & 15) == 0;
-    if (!mask && !(fq && workspace)) {   // any plane that fits one workgroup's LDS: the mixed-radix one-pass kernel (no workspace)
-        size_t lds = 0;
-        MrParams q;
-        const int nt = mr_threads(p.h, p.w, &lds);
-        if (nt && mr_fill(q, p, nt)) {
+    case FFT_MR1:
 #ifdef MR_TRACE
-            q.f.trace = fft_trace_buf();
+        if (!INV) r.q.f.trace = fft_trace_buf();
 #endif
-            MR_GO(rfft2_mr_kernel, nt, lds, q);
-            LAMA_CHECK_LAUNCH();
-            return LAMA_OK;
-        }
-    }
-    size_t need = (size_t)p.nplanes * p.h * p.wf * sizeof(float2);
-    if (!workspace || workspace_bytes < need) return LAMA_ERR_WORKSPACE;
-    float2* ws = (float2*)workspace;
-    if (fq) {
-        hipLaunchKernelGGL(fq_rows_fwd_kernel, dim3(p.nplanes * (FQ_N / 2 / FQ_PAIRS)), dim3(LAMA_NTHREADS), (size_t)(FQ_N + FQ_PAIRS * (FQ_N + 1)) * sizeof(float2), st, p, ws);
-        LAMA_CHECK_LAUNCH();
-        hipLaunchKernelGGL(fq_cols_kernel<false>, dim3(p.nplanes * (FQ_N / 2 / FQ_CW)), dim3(LAMA_NTHREADS), (size_t)(FQ_N + FQ_N * FQ_CP) * sizeof(float2), st, p, ws);
-        LAMA_CHECK_LAUNCH();
+#ifdef MR_BENCH_ONLY      // tools/ubench/mk_mr_bench.sh: one instantiation per kernel (compile time of the ablation builds)
+        FFT_GO32(rfft2_mr_kernel, irfft2_mr_kernel, (MR_BENCH_ONLY, false), planes, dim3(MR_BENCH_ONLY), r.lds, q);
+#else
+        if (r.nt == 256) FFT_GO(rfft2_mr_kernel, irfft2_mr_kernel, (256), planes, dim3(256), r.lds, q);
+        else FFT_GO(rfft2_mr_kernel, irfft2_mr_kernel, (1024), planes, dim3(1024), r.lds, q);
+#endif
+        break;
+    case FFT_FQ:
+        FFT_ROWS_COLS(if constexpr (INV) hipLaunchKernelGGL(fq_rows_inv_kernel, dim3(p.nplanes * (FQ_N / 2 / FQ_PAIRS)), blk, r.lds, st, p, ws);
+                      else hipLaunchKernelGGL(fq_rows_fwd_kernel, dim3(p.nplanes * (FQ_N / 2 / FQ_PAIRS)), blk, r.lds, st, p, ws),
+                      hipLaunchKernelGGL(fq_cols_kernel<INV>, dim3(p.nplanes * (FQ_N / 2 / FQ_CW)), blk, r.lds_cols, st, p, ws));
+        return LAMA_OK;
+    case FFT_2P:
+        FFT_ROWS_COLS(FFT_GO(fft2p_rows_fwd_kernel, fft2p_rows_inv_kernel, (), dim3(p.nplanes * lama_ceil_div(p.h / 2, FFT2P_PAIRS)), blk, r.lds, p, ws),
+                      FFT_GO1(fft2p_cols_kernel, (INV), dim3(p.nplanes * lama_ceil_div(p.wf, FFT2P_COLS)), blk, r.lds_cols, p, ws));
+        return LAMA_OK;
+    case FFT_MR2:
+        FFT_ROWS_COLS(FFT_GO(mr2_rows_fwd_kernel, mr2_rows_inv_kernel, (), dim3(p.nplanes * lama_ceil_div((p.h + 1) / 2, MR2_PAIRS)), dim3(MR2_NT), r.lds, q, ws),
+                      FFT_GO1(mr2_cols_kernel, (INV), dim3(p.nplanes * lama_ceil_div(p.wf, MR2_COLS)), dim3(MR2_NT), r.lds_cols, q, ws));
+        return LAMA_OK;
+    case FFT_DFT:
+        FFT_ROWS_COLS(FFT_GO(dft_rows_fwd_kernel, dft_rows_inv_kernel, (), dim3((unsigned)lama_ceil_div64((long long)p.nplanes * p.h, DFT_ROWS_PER_WG)), blk, r.lds, p, ws),
+                      FFT_GO1(dft_cols_kernel, (INV), dim3(p.nplanes * lama_ceil_div(p.wf, DFT_COLS_PER_WG)), blk, r.lds_cols, p, ws));
         return LAMA_OK;
     }
-    if (fft_two_pass_ok(p.h, p.w)) {
-        size_t ldsr = ((size_t)p.w + 2 * (size_t)FFT2P_PAIRS * (p.w + 1)) * sizeof(float2);
-        size_t ldsc = ((size_t)p.h + 2 * (size_t)FFT2P_COLS * (p.h + 1)) * sizeof(float2);
-        if (hf) hipLaunchKernelGGL(fft2p_rows_fwd_kernel<true>, dim3(p.nplanes * lama_ceil_div(p.h / 2, FFT2P_PAIRS)), dim3(LAMA_NTHREADS), ldsr, st, p, ws);
-        else hipLaunchKernelGGL(fft2p_rows_fwd_kernel<false>, dim3(p.nplanes * lama_ceil_div(p.h / 2, FFT2P_PAIRS)), dim3(LAMA_NTHREADS), ldsr, st, p, ws);
-        LAMA_CHECK_LAUNCH();
-        FFT_GO(fft2p_cols_kernel, (false), dim3(p.nplanes * lama_ceil_div(p.wf, FFT2P_COLS)), dim3(LAMA_NTHREADS), ldsc, p, ws);
-        LAMA_CHECK_LAUNCH();
-        return LAMA_OK;
-    }
-    if (!mask) {   // any other plane: the two-launch form of the mixed-radix passes (fft_mr_dev.inc); lengths with a prime factor too large for them keep the DFT
-        MrParams q;
-        size_t ldr = 0, ldc = 0;
-        if (mr2_fill(q, p, &ldr, &ldc)) {
-            if (hf) hipLaunchKernelGGL(mr2_rows_fwd_kernel<true>, dim3(p.nplanes * lama_ceil_div((p.h + 1) / 2, MR2_PAIRS)), dim3(MR2_NT), ldr, st, q, ws);
-            else hipLaunchKernelGGL(mr2_rows_fwd_kernel<false>, dim3(p.nplanes * lama_ceil_div((p.h + 1) / 2, MR2_PAIRS)), dim3(MR2_NT), ldr, st, q, ws);
-            LAMA_CHECK_LAUNCH();
-            FFT_GO(mr2_cols_kernel, (false), dim3(p.nplanes * lama_ceil_div(p.wf, MR2_COLS)), dim3(MR2_NT), ldc, q, ws);
-            LAMA_CHECK_LAUNCH();
-            return LAMA_OK;
-        }
-    }
-    long long nrows = (long long)p.nplanes * p.h;
-    fft_dft_split(p);
-    size_t lds1 = (size_t)p.w * sizeof(float2) + (size_t)DFT_ROWS_PER_WG * ((size_t)(p.w + p.w1) * sizeof(float2) + p.w * sizeof(float));
-    size_t lds2 = (size_t)p.h * sizeof(float2) * (1 + 2 * DFT_COLS_PER_WG);
-    if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return LAMA_ERR_UNSUPPORTED;
-    if (hf) hipLaunchKernelGGL(dft_rows_fwd_kernel<true>, dim3((unsigned)lama_ceil_div64(nrows, DFT_ROWS_PER_WG)), dim3(LAMA_NTHREADS), lds1, st, p, ws);
-    else hipLaunchKernelGGL(dft_rows_fwd_kernel<false>, dim3((unsigned)lama_ceil_div64(nrows, DFT_ROWS_PER_WG)), dim3(LAMA_NTHREADS), lds1, st, p, ws);
-    LAMA_CHECK_LAUNCH();
-    int ncb = lama_ceil_div(p.wf, DFT_COLS_PER_WG);
-    FFT_GO(dft_cols_kernel, (false), dim3(p.nplanes * ncb), dim3(LAMA_NTHREADS), lds2, p, ws);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }
 
-static int irfft2_impl(void* stream, const lama_tensor* spec, const lama_tensor* resid, const lama_tensor* mask, const lama_tensor* y,
-                       int32_t batch, void* workspace, size_t workspace_bytes) {
-    if (!fft_args_ok(y, spec, batch)) return LAMA_ERR_BAD_ARG;
+// rfft2 (INV = false: `real` is the input x, no resid) and irfft2 (INV = true: `real` is the output y, `resid` may be absent).  `mask` is laid
+// out like the output: spec forward, y inverse.
+template <bool INV>
+static int fft2_impl(void* stream, const lama_tensor* real, const lama_tensor* resid, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
+                     void* workspace, size_t workspace_bytes, const WoParams* wo = nullptr) {
+    if (!fft_args_ok(real, spec, batch)) return LAMA_ERR_BAD_ARG;
     const bool has_r = resid && resid->ptr;
-    if (has_r && (resid->C != y->C || resid->H != y->H || resid->W != y->W)) return LAMA_ERR_BAD_ARG;
-    if (y->dtype != spec->dtype || (has_r && resid->dtype != y->dtype) || (y->dtype != LAMA_DT_F32 && y->dtype != LAMA_DT_F16))
+    if (has_r && (resid->C != real->C || resid->H != real->H || resid->W != real->W)) return LAMA_ERR_BAD_ARG;
+    if (real->dtype != spec->dtype || (has_r && resid->dtype != real->dtype) || (real->dtype != LAMA_DT_F32 && real->dtype != LAMA_DT_F16))
         return LAMA_ERR_UNSUPPORTED;
-    const bool hf = y->dtype == LAMA_DT_F16;
-    const int es = hf ? 2 : 4;
-    const uintptr_t amask = hf ? 7 : 15;
+    const lama_tensor *out = INV ? real : spec, *x = INV ? (has_r ? resid : nullptr) : real;
+    if (mask && (!mask->ptr || mask->dtype != LAMA_DT_F32 || mask->C != out->C || mask->H != out->H || mask->W != out->W)) return LAMA_ERR_BAD_ARG;
     FftParams p;
     memset(&p, 0, sizeof(p));
-    p.x = has_r ? resid->ptr : nullptr;
-    p.x_bstride = has_r ? resid->batch_stride : 0;
+    if (x) { p.x = x->ptr; p.x_bstride = x->batch_stride; }
     p.spec = spec->ptr;
     p.spec_bstride = spec->batch_stride;
-    p.y = y->ptr;
-    p.y_bstride = y->batch_stride;
-    p.C = y->C; p.h = y->H; p.w = y->W; p.wf = y->W / 2 + 1;
-    p.nplanes = batch * y->C;
+    if (INV) { p.y = real->ptr; p.y_bstride = real->batch_stride; }
+    if (mask) { p.mask = (const float*)mask->ptr; p.mask_bstride = mask->batch_stride; }
+    p.C = real->C; p.h = real->H; p.w = real->W; p.wf = real->W / 2 + 1;
+    p.nplanes = batch * real->C;
     p.scale = (float)(1.0 / sqrt((double)p.h * (double)p.w));
-    hipStream_t st = (hipStream_t)stream;
-    uintptr_t al = (uintptr_t)y->ptr | (uintptr_t)(y->batch_stride * es);
+    // vector accesses are 4 elements: 16-byte (fp32) / 8-byte (fp16) alignment of every view they touch (the forward mask is read by element)
+    const bool hf = real->dtype == LAMA_DT_F16;
+    const int es = hf ? 2 : 4;
+    const uintptr_t amask = hf ? 7 : 15;
+    uintptr_t al = (uintptr_t)real->ptr | (uintptr_t)(real->batch_stride * es);
     if (has_r) al |= (uintptr_t)resid->ptr | (uintptr_t)(resid->batch_stride * es);
+    if (INV && mask) al |= (uintptr_t)mask->ptr | (uintptr_t)(mask->batch_stride * 4);
     const bool spec_al = (((uintptr_t)spec->ptr | (uintptr_t)(spec->batch_stride * es)) & amask) == 0;
-    if (mask) {
-        if (!mask->ptr || mask->dtype != LAMA_DT_F32 || mask->C != y->C || mask->H != y->H || mask->W != y->W) return LAMA_ERR_BAD_ARG;
-        al |= (uintptr_t)mask->ptr | (uintptr_t)(mask->batch_stride * 4);
-        if (!(fq_ok(p.h, p.w, hf) && ((al | (uintptr_t)workspace) & 15) == 0)) return LAMA_ERR_UNSUPPORTED;
-        p.mask = (const float*)mask->ptr;
-        p.mask_bstride = mask->batch_stride;
-    }
-    if (fft_fast_ok(p.h, p.w) && (al & amask) == 0) {
-        p.ppw = fft_ppw(p.h, p.w);
-        size_t lds = fft_lds_bytes(p.h, p.w, p.ppw);
-        const dim3 grid(lama_ceil_div(p.nplanes, p.ppw)), blk(LAMA_NTHREADS);
-        const bool even = p.nplanes % p.ppw == 0;
-        p.trace = hf ? nullptr : fft_trace_buf();
-        p.prio = lama_side_prio();
-        if (!p.trace && p.h == 64 && p.w == 64 && fft_inplace() && spec_al)
-            FFT_GO(irfft2_ip64_kernel, (false), dim3(p.nplanes), blk, (size_t)(IP_N + IP_BUF) * sizeof(float2), p);
-        else if (p.h == 128 && p.w == 128 && fft_inplace() && spec_al)
-            FFT_GO(irfft2_ipn_kernel, (128), dim3(p.nplanes), blk, (size_t)(128 + 128 * 65) * sizeof(float2), p);
-#ifdef LAMA_PROFILING
-        else if (!hf && p.trace && even && p.h == 64 && p.w == 64) hipLaunchKernelGGL((irfft2_lds_kernel<64, 64, 1, 1, true>), grid, blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 2 && p.h == 64 && p.w == 64) hipLaunchKernelGGL((irfft2_lds_kernel<64, 64, 1, 2>), dim3(p.nplanes / 2), blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 3 && p.h == 64 && p.w == 64) hipLaunchKernelGGL((irfft2_lds_kernel<64, 64, 1, 3>), dim3(p.nplanes / 3), blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 2 && p.h == 128 && p.w == 128) hipLaunchKernelGGL((irfft2_lds_kernel<128, 128, 1, 2>), dim3(p.nplanes / 2), blk, lds, st, p);
-        else if (!hf && spec_al && p.ppw == 1 && fft_seq(p.nplanes) == 3 && p.h == 128 && p.w == 128) hipLaunchKernelGGL((irfft2_lds_kernel<128, 128, 1, 3>), dim3(p.nplanes / 3), blk, lds, st, p);
-#endif
-        else if (!hf && even && p.h == 64 && p.w == 64 && p.ppw == 1) hipLaunchKernelGGL((irfft2_lds_kernel<64, 64, 1>), grid, blk, lds, st, p);
-        else if (even && p.h == 32 && p.w == 32 && p.ppw == 4) FFT_GO(irfft2_lds_kernel, (32, 32, 4, 1, false), grid, blk, lds, p);
-        else if (!hf && even && p.h == 128 && p.w == 128 && p.ppw == 1) hipLaunchKernelGGL((irfft2_lds_kernel<128, 128, 1>), grid, blk, lds, st, p);
-        else FFT_GO(irfft2_lds_kernel, (0, 0, 0, 1, false), grid, blk, lds, p);
-        LAMA_CHECK_LAUNCH();
-        return LAMA_OK;
-    }
-    const bool fq = fq_ok(p.h, p.w, hf) && ((al | (uintptr_t)workspace) & 15) == 0;
-    if (!mask && !(fq && workspace)) {
-        size_t lds = 0;
-        MrParams q;
-        const int nt = mr_threads(p.h, p.w, &lds);
-        if (nt && mr_fill(q, p, nt)) {
-            MR_GO(irfft2_mr_kernel, nt, lds, q);
-            LAMA_CHECK_LAUNCH();
-            return LAMA_OK;
-        }
-    }
-    size_t need = (size_t)p.nplanes * p.h * p.wf * sizeof(float2);
-    if (!workspace || workspace_bytes < need) return LAMA_ERR_WORKSPACE;
-    float2* ws = (float2*)workspace;
-    if (fq) {
-        hipLaunchKernelGGL(fq_cols_kernel<true>, dim3(p.nplanes * (FQ_N / 2 / FQ_CW)), dim3(LAMA_NTHREADS), (size_t)(FQ_N + FQ_N * FQ_CP) * sizeof(float2), st, p, ws);
-        LAMA_CHECK_LAUNCH();
-        hipLaunchKernelGGL(fq_rows_inv_kernel, dim3(p.nplanes * (FQ_N / 2 / FQ_PAIRS)), dim3(LAMA_NTHREADS), (size_t)(FQ_N + FQ_PAIRS * (FQ_N + 1)) * sizeof(float2), st, p, (const float2*)ws);
-        LAMA_CHECK_LAUNCH();
-        return LAMA_OK;
-    }
-    if (fft_two_pass_ok(p.h, p.w)) {
-        size_t ldsr = ((size_t)p.w + 2 * (size_t)FFT2P_PAIRS * (p.w + 1)) * sizeof(float2);
-        size_t ldsc = ((size_t)p.h + 2 * (size_t)FFT2P_COLS * (p.h + 1)) * sizeof(float2);
-        FFT_GO(fft2p_cols_kernel, (true), dim3(p.nplanes * lama_ceil_div(p.wf, FFT2P_COLS)), dim3(LAMA_NTHREADS), ldsc, p, ws);
-        LAMA_CHECK_LAUNCH();
-        if (hf) hipLaunchKernelGGL(fft2p_rows_inv_kernel<true>, dim3(p.nplanes * lama_ceil_div(p.h / 2, FFT2P_PAIRS)), dim3(LAMA_NTHREADS), ldsr, st, p, (const float2*)ws);
-        else hipLaunchKernelGGL(fft2p_rows_inv_kernel<false>, dim3(p.nplanes * lama_ceil_div(p.h / 2, FFT2P_PAIRS)), dim3(LAMA_NTHREADS), ldsr, st, p, (const float2*)ws);
-        LAMA_CHECK_LAUNCH();
-        return LAMA_OK;
-    }
-    if (!mask) {
-        MrParams q;
-        size_t ldr = 0, ldc = 0;
-        if (mr2_fill(q, p, &ldr, &ldc)) {
-            FFT_GO(mr2_cols_kernel, (true), dim3(p.nplanes * lama_ceil_div(p.wf, MR2_COLS)), dim3(MR2_NT), ldc, q, ws);
-            LAMA_CHECK_LAUNCH();
-            if (hf) hipLaunchKernelGGL(mr2_rows_inv_kernel<true>, dim3(p.nplanes * lama_ceil_div((p.h + 1) / 2, MR2_PAIRS)), dim3(MR2_NT), ldr, st, q, (const float2*)ws);
-            else hipLaunchKernelGGL(mr2_rows_inv_kernel<false>, dim3(p.nplanes * lama_ceil_div((p.h + 1) / 2, MR2_PAIRS)), dim3(MR2_NT), ldr, st, q, (const float2*)ws);
-            LAMA_CHECK_LAUNCH();
-            return LAMA_OK;
-        }
-    }
-    long long nrows = (long long)p.nplanes * p.h;
-    fft_dft_split(p);
-    size_t lds1 = ((size_t)p.w * (1 + 2 * DFT_ROWS_PER_WG) + (size_t)DFT_ROWS_PER_WG * p.w1) * sizeof(float2);
-    size_t lds2 = (size_t)p.h * sizeof(float2) * (1 + 2 * DFT_COLS_PER_WG);
-    if (lds1 > 160 * 1024 || lds2 > 160 * 1024) return LAMA_ERR_UNSUPPORTED;
-    int ncb = lama_ceil_div(p.wf, DFT_COLS_PER_WG);
-    FFT_GO(dft_cols_kernel, (true), dim3(p.nplanes * ncb), dim3(LAMA_NTHREADS), lds2, p, ws);
-    LAMA_CHECK_LAUNCH();
-    if (hf) hipLaunchKernelGGL(dft_rows_inv_kernel<true>, dim3((unsigned)lama_ceil_div64(nrows, DFT_ROWS_PER_WG)), dim3(LAMA_NTHREADS), lds1, st, p, (const float2*)ws);
-    else hipLaunchKernelGGL(dft_rows_inv_kernel<false>, dim3((unsigned)lama_ceil_div64(nrows, DFT_ROWS_PER_WG)), dim3(LAMA_NTHREADS), lds1, st, p, (const float2*)ws);
-    LAMA_CHECK_LAUNCH();
-    return LAMA_OK;
+    FftRoute r;
+    const int rc = fft_route(p, INV, hf, (al & amask) == 0, spec_al, mask != nullptr, wo != nullptr, workspace, workspace_bytes, r);
+    return rc ? rc : fft_launch<INV>((hipStream_t)stream, r, p, hf, (float2*)workspace, wo);
 }
 
 extern "C" int lama_rfft2_fwd(void* stream, const lama_tensor* x, const lama_tensor* spec, int32_t batch, void* workspace, size_t workspace_bytes) {
-    return rfft2_impl(stream, x, spec, nullptr, batch, workspace, workspace_bytes);
+    return fft2_impl<false>(stream, x, nullptr, spec, nullptr, batch, workspace, workspace_bytes);
 }
 extern "C" int lama_irfft2_fwd(void* stream, const lama_tensor* spec, const lama_tensor* resid, const lama_tensor* y, int32_t batch, void* workspace,
                                size_t workspace_bytes) {
-    return irfft2_impl(stream, spec, resid, nullptr, y, batch, workspace, workspace_bytes);
+    return fft2_impl<true>(stream, y, resid, spec, nullptr, batch, workspace, workspace_bytes);
 }
 // (v108) the transforms of the reverse pass with the ReLU derivative that follows them: out = transform(...) * [mask_y > 0].  Only where the
 // compile-time two-pass kernels run (fp32 planes of 256 x 256, 16-byte aligned views); LAMA_ERR_UNSUPPORTED otherwise, nothing launched.
 extern "C" int lama_rfft2_masked_fwd(void* stream, const lama_tensor* x, const lama_tensor* spec, const lama_tensor* mask_y, int32_t batch,
                                      void* workspace, size_t workspace_bytes) {
     if (!mask_y) return LAMA_ERR_BAD_ARG;
-    return rfft2_impl(stream, x, spec, mask_y, batch, workspace, workspace_bytes);
+    return fft2_impl<false>(stream, x, nullptr, spec, mask_y, batch, workspace, workspace_bytes);
 }
 extern "C" int lama_irfft2_masked_fwd(void* stream, const lama_tensor* spec, const lama_tensor* resid, const lama_tensor* mask_y, const lama_tensor* y,
                                       int32_t batch, void* workspace, size_t workspace_bytes) {
     if (!mask_y) return LAMA_ERR_BAD_ARG;
-    return irfft2_impl(stream, spec, resid, mask_y, y, batch, workspace, workspace_bytes);
+    return fft2_impl<true>(stream, y, resid, spec, mask_y, batch, workspace, workspace_bytes);
 }
 // (v108) rfft2 of one layer and the output transform of the Winograd local conv of the layer before (lama_winograd_conv3x3_fwd called with
 // LAMA_CONV_DEFER_OUT and the same `wino_args` / workspace) in ONE launch: both are memory-bound and independent, and the FFT workgroups leave
@@ -2101,5 +2052,5 @@ extern "C" int lama_rfft2_winograd_out_fwd(void* stream, const lama_tensor* x, c
     WoParams wo;
     const int rc = lama_wino_out_params(wino_args, wino_workspace, wino_workspace_bytes, &wo);
     if (rc) return rc;
-    return rfft2_impl(stream, x, spec, nullptr, batch, workspace, workspace_bytes, &wo);
+    return fft2_impl<false>(stream, x, nullptr, spec, nullptr, batch, workspace, workspace_bytes, &wo);
 }

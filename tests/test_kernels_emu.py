@@ -281,6 +281,72 @@ def test_fft_masked_entries_emulated():
     assert ei.value.code == L.ERR_UNSUPPORTED and float(ss.abs().max()) == 0.0
 
 
+def check_fft_route_contract(lib, dev='cpu'):
+    """The contract of the FFT entries at the edges of their routes (include/lama_hip.h), for rfft2 and irfft2 alike, B = 1 and C = 2: the
+    masked entries refuse planes the compile-time 256 x 256 fp32 kernels do not serve, a plane that needs the workspace is refused without
+    one or with one four bytes short, planes one workgroup holds in LDS need none, and lama_rfft2_winograd_out_fwd refuses anything but
+    64 x 64 -- every refusal with nothing launched (outputs keep their sentinel).  Shared with tests/test_kernels_gpu.py."""
+    g = torch.Generator().manual_seed(41)
+    B, Cn = 1, 2
+    st = 0 if dev == 'cpu' else torch.cuda.current_stream().cuda_stream
+
+    def planes(h, w, dtype=torch.float32):
+        x = torch.randn(B, Cn, h, w, generator=g).to(dtype).to(dev)
+        spec = torch.relu(torch.randn(B, 2 * Cn, h, w // 2 + 1, generator=g)).to(dtype).to(dev)
+        return x, spec
+
+    def run(inverse, x, spec, ws, masked=False):
+        """One transform into a sentinel-filled output: (return code, output)."""
+        out = torch.full_like(x if inverse else spec, 7.0)
+        ones = torch.ones(out.shape, device=dev)
+        mask = L.view(ones) if masked else None
+        try:
+            if inverse:
+                lib.irfft2(L.view(spec), L.view(x), L.view(out), B, ws, stream=st, mask=mask)
+            else:
+                lib.rfft2(L.view(x), L.view(out), B, ws, stream=st, mask=mask)
+        except L.LamaError as e:
+            _dev_sync(dev)
+            return e.code, out
+        _dev_sync(dev)
+        return 0, out
+
+    def refused(code, out, want):
+        assert code == want, (code, want)
+        assert float(out.float().min()) == 7.0 and float(out.float().max()) == 7.0
+
+    for inverse in (False, True):
+        for (h, w, dtype) in [(64, 64, torch.float32), (256, 256, torch.float16)]:        # masked entries: fp32 planes of 256 x 256 only
+            x, spec = planes(h, w, dtype)
+            ws = torch.zeros(max(lib.fft_workspace_bytes(B, Cn, h, w), 16) // 4, device=dev)
+            refused(*run(inverse, x, spec, ws, masked=True), L.ERR_UNSUPPORTED)
+        x, spec = planes(192, 256)                                                       # two launches through the workspace
+        need = lib.fft_workspace_bytes(B, Cn, 192, 256)
+        assert need == B * Cn * 192 * 129 * 8
+        refused(*run(inverse, x, spec, None), L.ERR_WORKSPACE)
+        refused(*run(inverse, x, spec, torch.zeros(need // 4 - 1, device=dev)), L.ERR_WORKSPACE)
+        for (h, w) in [(10, 12), (16, 16)]:                                              # one-launch mixed-radix / LDS path: no workspace
+            x, spec = planes(h, w)
+            code, out = run(inverse, x, spec, None)
+            ref = x.cpu() + _inv_ref(spec.cpu(), h, w) if inverse else _spec_ref(x.cpu())
+            assert code == 0 and torch.allclose(out.cpu(), ref, atol=3e-5, rtol=1e-4), (code, float((out.cpu() - ref).abs().max()))
+    # lama_rfft2_winograd_out_fwd (forward only) with a pending output transform: 32 x 32 planes are refused, neither output is written
+    o = wino_operands(lib, WINO_DEFER_CASES[1], L.PREC_F16X3, dev)
+    y2 = torch.full((o.B, o.cout + 3, o.H, o.W), 7.0, device=dev)
+    pend = wino_run(lib, o, y2, defer_out=True)
+    x, _ = planes(32, 32)
+    sp = torch.full((B, 2 * Cn, 32, 17), 7.0, device=dev)
+    with pytest.raises(L.LamaError) as ei:
+        lib.rfft2_wino_out(L.view(x), L.view(sp), B, None, pend, o.ws, stream=o.st)
+    _dev_sync(dev)
+    refused(ei.value.code, sp, L.ERR_UNSUPPORTED)
+    assert float(y2.min()) == 7.0 and float(y2.max()) == 7.0
+
+
+def test_fft_route_contract_emulated():
+    check_fft_route_contract(emu_lib())
+
+
 @pytest.mark.parametrize('hw_seq', [(64, 1), (64, 2), (64, 3), (128, 3)], ids=lambda s: f'{s[0]}x{s[0]}seq{s[1]}')
 def test_fft_sequential_planes_emulated(hw_seq, monkeypatch):
     """Sized one-plane kernels walking SEQ consecutive planes per workgroup with the next plane prefetched (LAMA_FFT_SEQ)."""

@@ -11,7 +11,7 @@ from lama_amd import _lib as L
 pytestmark = pytest.mark.gpu
 
 from tests.test_kernels_emu import (WINO_CASES, CONV_CASES, CONV_TOL, F16_CASES, F16_MIXED, F16_STEM_HEAD, FFT_SIZES, PREC_IDS, PRECISIONS, _conv_f16_ref, _conv_ref,  # noqa: E402
-                                    _inv_ref, _spec_ref)
+                                    _inv_ref, _spec_ref, check_fft_route_contract)
 
 
 @pytest.fixture(scope='module')
@@ -308,6 +308,11 @@ def test_fft_masked_entries(lib):
         lib.rfft2(L.view(wide[:, :, :64, :64].contiguous(), 0, 4), L.view(torch.zeros(B, 8, 64, 33, device=DEV)), B, ws, stream=st,
                   mask=L.view(torch.ones(B, 8, 64, 33, device=DEV)))
     assert ei.value.code == L.ERR_UNSUPPORTED
+
+
+def test_fft_route_contract(anylib):
+    """The refusals and the no-workspace routes of the FFT entries, both directions (tests/test_kernels_emu.py check_fft_route_contract)."""
+    check_fft_route_contract(anylib, DEV)
 
 
 @pytest.mark.parametrize('n_seq', [(64, 1), (64, 2), (64, 3), (128, 2), (128, 3)], ids=lambda s: f'{s[0]}seq{s[1]}')
