@@ -281,6 +281,31 @@ int lama_blend_quantize_u8_fwd(void* stream, const uint8_t* image_hwc, const uin
 int lama_resize_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes, int32_t Hs,
                        int32_t Ws, double factor, const lama_tensor* out_image, const lama_tensor* out_mask, int32_t batch, int32_t binarize);
 
+/* (added to v112 without a version bump: one new symbol, nothing else changes) The evaluator's loader on what is on DISK: a batch of decoded
+ * (ground truth, prediction, mask) triples in one launch, so that scoring uploads 7 bytes per pixel instead of 28 and the host only decodes.
+ *   image_hwc, pred_hwc u8 [B][Hs][Ws][3], mask u8 [B][Hs][Ws] (device pointers): slots, each image's own h x w pixels in the top-left corner;
+ *   sizes: HOST array int32 [B][2] = (h, w), or NULL: every image fills its slot.  It is read during the call (the checks below need it) and
+ *     rides in the kernel's argument block: the launch stays asynchronous and capturable, 64 images per launch (a larger batch is more launches);
+ *   pad_mod: dataset_kwargs.pad_out_to_modulo (1 = no padding); out_image, out_pred: [B,3,Hp,Wp] fp32 with Hp = ceil_modulo(h, pad_mod),
+ *     Wp = ceil_modulo(w, pad_mod) (evaluation/data.py:23-26) for EVERY image of the call.
+ * Per image the kernel does what PrecomputedInpaintingResultsDataset.__getitem__ and InpaintingEvaluator.evaluate do on the host:
+ *   out = u8.astype('float32') / 255 of both images (data.py:12-20: the same IEEE fp32 division as lama_mask_compose_u8_fwd), pad_img_to_modulo's
+ *   symmetric padding bottom / right (data.py:29-33: row h + i = row h - 1 - i), torch.clamp(image, clamp_lo, clamp_hi) of the ground truth ONLY
+ *   and only when clamp != 0 (evaluator.py:87-90: clamp_image_range; the prediction is never clamped).
+ *   mask_sum[b] (device int64 [B]) = the exact sum of the u8 mask values over the symmetric-padded Hp x Wp mask plane of image b: integer adds
+ *   in a fixed order, no atomics, nothing to zero.  The evaluator needs the mask only as its mean (evaluator.py:58,164), which the host forms as
+ *   mask_sum / (255 Hp Wp) in fp64; no float mask plane is written.
+ * Bit-identical to the host chain.  Any Hs, Ws, Hp, Wp >= 1 (dword loads where Ws % 4 == 0, float4 stores where Wp % 4 == 0 and the views are
+ * 16-byte aligned with batch strides that are multiples of 4; element accesses otherwise).
+ * LAMA_ERR_BAD_ARG: a null pointer, batch / Hs / Ws / pad_mod <= 0, views that are not two [.,3,Hp,Wp] of one size, outputs that are not
+ *   4-byte aligned or a mask_sum that is not 8-byte aligned, clamp_lo > clamp_hi, an image with h or w outside 1 .. Hs / Ws, an image whose
+ *   padded size is not (Hp, Wp) (one padded size per call);
+ * LAMA_ERR_UNSUPPORTED: views that are not fp32; an image whose padding exceeds its own extent (Hp > 2 h or Wp > 2 w: np.pad's periodic
+ *   mirror, which lama_mask_compose_u8_fwd serves and this entry does not).  Nothing is launched on an error. */
+int lama_eval_ingest_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* pred_hwc, const uint8_t* mask, const int32_t* sizes, int32_t Hs,
+                            int32_t Ws, int32_t pad_mod, int32_t clamp, float clamp_lo, float clamp_hi, const lama_tensor* out_image,
+                            const lama_tensor* out_pred, int64_t* mask_sum, int32_t batch);
+
 /* Stand-alone per-channel affine + activation: y = act(x*scale[c] + shift[c]) (scale/shift NULL = identity).
  * Used when a caller runs generator.model layer by layer and hits a bare nn.BatchNorm2d (eval) /
  * nn.ReLU / nn.Sigmoid (ffc.py:352-354,362-363); the fused forward never launches it. */

@@ -126,6 +126,8 @@ class LamaLib:
         L.lama_blend_quantize_u8_fwd.argtypes = [vp, vp, vp, vp, T, vp, i32, i32]
         L.lama_resize_u8_fwd.restype = C.c_int
         L.lama_resize_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, T, T, i32, i32]
+        L.lama_eval_ingest_u8_fwd.restype = C.c_int
+        L.lama_eval_ingest_u8_fwd.argtypes = [vp, vp, vp, vp, C.POINTER(i32), i32, i32, i32, i32, C.c_float, C.c_float, T, T, vp, i32]
         L.lama_affine_act_fwd.restype = C.c_int
         L.lama_affine_act_fwd.argtypes = [vp, T, vp, vp, i32, T, i32]
         L.lama_reflect_pad_fwd.restype = C.c_int
@@ -406,6 +408,41 @@ class LamaLib:
         self.check(self._l.lama_resize_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
                                               int(image_hwc.shape[1]), int(image_hwc.shape[2]), float(factor), C.byref(out_image), C.byref(out_mask),
                                               batch, int(bool(binarize))), 'lama_resize_u8_fwd')
+
+    def eval_ingest_u8(self, image_hwc: torch.Tensor, pred_hwc: torch.Tensor, mask: torch.Tensor, sizes, pad_mod: int,
+                       out_image: Optional[torch.Tensor], out_pred: Optional[torch.Tensor], mask_sum: Optional[torch.Tensor], batch: int,
+                       clamp=None, stream: int = 0):
+        """lama_eval_ingest_u8_fwd: the evaluator's loader on the device.  u8 HWC ground truth / prediction slots [B,Hs,Ws,3] + u8 mask slots
+        [B,Hs,Ws], ``sizes`` = a HOST sequence of (h, w) per image or None (every image fills its slot) -> fp32 ``out_image`` / ``out_pred``
+        [B,3,Hp,Wp] (/ 255, symmetric padding to ``pad_mod``, ``clamp`` = (lo, hi) on the ground truth only) and ``mask_sum`` int64 [B], the
+        exact sum of the padded u8 mask.  Shapes and codes: include/lama_hip.h."""
+        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(pred_hwc.shape) != tuple(image_hwc.shape) \
+                or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
+            raise LamaError(f'eval_ingest_u8: image / prediction slots {tuple(image_hwc.shape)} / {tuple(pred_hwc.shape)}, mask slots '
+                            f'{tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
+        for t in (image_hwc, pred_hwc, mask):
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise LamaError(f'eval_ingest_u8: contiguous uint8 slots are needed, got {t.dtype}')
+        if mask_sum is not None and (mask_sum.dtype != torch.int64 or not mask_sum.is_contiguous() or mask_sum.numel() < batch):
+            raise LamaError('eval_ingest_u8: mask_sum is a contiguous int64 [B] tensor')
+        for t in (image_hwc, pred_hwc, mask, out_image, out_pred, mask_sum):
+            if t is not None and not self.host_emulated and not t.is_cuda:
+                raise LamaError('eval_ingest_u8: the slots and the outputs are device tensors (there is no CPU path)')
+        for t in (out_image, out_pred):
+            if t is not None and t.shape[0] < batch:
+                raise LamaError(f'eval_ingest_u8: output {tuple(t.shape)} holds fewer than {batch} images')
+        hw = None
+        if sizes is not None:
+            flat = [int(v) for hw_ in sizes for v in hw_]
+            if len(flat) != 2 * batch:
+                raise LamaError(f'eval_ingest_u8: sizes holds {len(flat) // 2} (h, w) pairs for a batch of {batch}')
+            hw = (C.c_int32 * len(flat))(*flat)
+        lo, hi = (0.0, 0.0) if clamp is None else (float(clamp[0]), float(clamp[1]))
+        self.check(self._l.lama_eval_ingest_u8_fwd(stream, image_hwc.data_ptr(), pred_hwc.data_ptr(), mask.data_ptr(), hw, int(image_hwc.shape[1]),
+                                                   int(image_hwc.shape[2]), int(pad_mod), int(clamp is not None), lo, hi,
+                                                   None if out_image is None else C.byref(view(out_image)),
+                                                   None if out_pred is None else C.byref(view(out_pred)),
+                                                   None if mask_sum is None else mask_sum.data_ptr(), batch), 'lama_eval_ingest_u8_fwd')
 
     def quantize_u8_hwc(self, src: Tensor4, dst: torch.Tensor, batch: int, crop_h: int, crop_w: int, stream: int = 0):
         self.check(self._l.lama_quantize_u8_hwc_fwd(stream, C.byref(src), dst.data_ptr(), batch, crop_h, crop_w), 'lama_quantize_u8_hwc_fwd')

@@ -155,6 +155,138 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void blend_quantize_u8_kernel(U8Para
     }
 }
 
+// ---- the evaluator's loader on the device: a batch of DECODED u8 (ground truth, prediction, mask) triples in one launch --
+//   PrecomputedInpaintingResultsDataset.__getitem__ (evaluation/data.py:110-124): image.astype('float32') / 255 of both images (data.py:16, the same
+//   IEEE division as mask_compose_u8_kernel), pad_img_to_modulo's symmetric padding bottom / right (data.py:29-33), and the clamp of the ground
+//   truth alone (evaluator.py:87-90).  The evaluator reads the mask only through its mean (evaluator.py:58,164): the float mask plane is never
+//   formed, the launch leaves the exact integer sum of the padded u8 mask per image instead.
+// The host has checked every size (the sizes ride in the kernel's argument block): 0 < h <= Hs, 0 < w <= Ws, padding <= extent, so a padded
+// row Hp > y >= h mirrors to row 2 h - 1 - y >= 0 without the periodic form of ew_symmetric.
+// Roles by workgroup: block b < B sums the mask of image b (its h x Ws bytes are one contiguous run: 16-byte loads, per-thread partial sums, one
+// fixed-order pass over them in LDS -- integer adds, no atomics, no workspace); the others convert, one thread per 4 consecutive output pixels:
+// 12 bytes in (three dword loads where the row pitch allows), one float4 per colour plane out (a wave writes 1 KB runs of each plane).
+#define LAMA_EI_MAX_BATCH 64
+struct EvalIngestParams {
+    const uint8_t* gt;       // [B][Hs][Ws][3]
+    const uint8_t* pred;     // [B][Hs][Ws][3]
+    const uint8_t* mask;     // [B][Hs][Ws]
+    float* out_img;          // [B,3,Hp,Wp]
+    long long img_bs;
+    float* out_pred;         // [B,3,Hp,Wp]
+    long long pred_bs;
+    long long* sums;         // [B]
+    float lo, hi;
+    int B, Hs, Ws, Hp, Wp, clamp, vec_ld, vec_st;
+    int32_t sizes[LAMA_EI_MAX_BATCH][2];
+};
+typedef uint32_t __attribute__((may_alias)) ei_u32;
+// pixel j (0..3), channel c of 12 HWC bytes held in three little-endian dwords
+__device__ __forceinline__ float ei_byte(const uint32_t (&d)[3], int k) { return (float)((d[k >> 2] >> (8 * (k & 3))) & 255u) / 255.0f; }
+
+__device__ __forceinline__ void ei_load4(const uint8_t* src, long long row, int x0, int w, int Wp, bool vec, float (&v)[3][4]) {
+    if (vec && x0 + 4 <= w) {
+        const ei_u32* s = reinterpret_cast<const ei_u32*>(src + (row + x0) * 3);
+        const uint32_t d[3] = {s[0], s[1], s[2]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][j] = ei_byte(d, 3 * j + c);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int x = x0 + j;
+        if (x < Wp) {
+            const uint8_t* s = src + (row + (x < w ? x : 2 * w - 1 - x)) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][j] = (float)s[c] / 255.0f;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][j] = 0.0f;
+        }
+    }
+}
+__device__ __forceinline__ void ei_store4(float* o, long long hw, int x0, int Wp, bool vec, const float (&v)[3][4]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (vec) {
+            *reinterpret_cast<float4*>(o + c * hw) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < Wp) o[c * hw + j] = v[c][j];
+        }
+    }
+}
+
+__global__ __launch_bounds__(LAMA_NTHREADS) void eval_ingest_u8_kernel(EvalIngestParams p) {
+    if ((int)blockIdx.x < p.B) {
+        // sum over the padded plane = sum over the h x w pixels, each counted once per padded position that mirrors onto it: rows / columns
+        // from 2 n - Np on count twice
+        const int b = blockIdx.x, h = p.sizes[b][0], w = p.sizes[b][1];
+        const int y2 = 2 * h - p.Hp, x2 = 2 * w - p.Wp;
+        const uint8_t* m = p.mask + (long long)b * p.Hs * p.Ws;
+        const long long n = (long long)h * p.Ws;
+        const long long mis = (long long)(reinterpret_cast<uintptr_t>(m) & 15);      // the run's first byte inside its 16-byte line
+        const long long nchunks = (mis + n + 15) >> 4;
+        unsigned long long acc = 0;
+        for (long long ch = threadIdx.x; ch < nchunks; ch += LAMA_NTHREADS) {
+            const long long f0 = ch * 16 - mis;
+            uint32_t d[4] = {0u, 0u, 0u, 0u};
+            const bool whole = f0 >= 0 && f0 + 16 <= n;
+            if (whole) {
+                const ei_u32* s = reinterpret_cast<const ei_u32*>(m + f0);
+                d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+            } else {
+                for (int k = 0; k < 16; ++k)
+                    if (f0 + k >= 0 && f0 + k < n) d[k >> 2] |= (uint32_t)m[f0 + k] << (8 * (k & 3));
+            }
+            const long long fc = f0 < 0 ? 0 : f0;                                   // (bytes in front of the run are zero in d)
+            int y = (int)(fc / p.Ws), x = (int)(fc - (long long)y * p.Ws);
+            uint32_t part = 0;
+            for (int k = (int)(fc - f0); k < 16; ++k) {
+                const uint32_t u = (d[k >> 2] >> (8 * (k & 3))) & 255u;
+                const uint32_t wt = x < w ? (x >= x2 ? 2u : 1u) * (y >= y2 ? 2u : 1u) : 0u;
+                part += u * wt;
+                if (++x == p.Ws) { x = 0; ++y; }
+            }
+            acc += part;
+        }
+        unsigned long long* red = reinterpret_cast<unsigned long long*>(lama_smem);
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long s = 0;
+            for (int t = 0; t < LAMA_NTHREADS; ++t) s += red[t];
+            p.sums[b] = (long long)s;
+        }
+        return;
+    }
+    const int qpr = (p.Wp + 3) >> 2;
+    const long long hw = (long long)p.Hp * p.Wp, total = (long long)p.B * p.Hp * qpr;
+    const long long step = (long long)(gridDim.x - p.B) * LAMA_NTHREADS;
+    for (long long i = (long long)(blockIdx.x - p.B) * LAMA_NTHREADS + threadIdx.x; i < total; i += step) {
+        const int q = (int)(i % qpr);
+        const long long r = i / qpr;
+        const int y = (int)(r % p.Hp), b = (int)(r / p.Hp);
+        const int h = p.sizes[b][0], w = p.sizes[b][1];
+        const int x0 = 4 * q;
+        const long long row = ((long long)b * p.Hs + (y < h ? y : 2 * h - 1 - y)) * p.Ws;
+        const bool vst = p.vec_st && x0 + 4 <= p.Wp;
+        float v[3][4];
+        ei_load4(p.gt, row, x0, w, p.Wp, p.vec_ld != 0, v);
+        if (p.clamp) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[c][j] = fminf(fmaxf(v[c][j], p.lo), p.hi);
+        }
+        ei_store4(p.out_img + b * p.img_bs + (long long)y * p.Wp + x0, hw, x0, p.Wp, vst, v);
+        ei_load4(p.pred, row, x0, w, p.Wp, p.vec_ld != 0, v);
+        ei_store4(p.out_pred + b * p.pred_bs + (long long)y * p.Wp + x0, hw, x0, p.Wp, vst, v);
+    }
+}
+
 // ---- dataset.scale_factor on the device: the loader's chain for one batch of DECODED u8 images in one launch --
 //   image.astype('float32') / 255 (evaluation/data.py:12-20), cv2.resize(fx = fy = factor) with INTER_AREA on the image and INTER_NEAREST on the
 //   mask (data.py:42-55,74-77), pad_img_to_modulo's symmetric padding of the SCALED result (data.py:29-33), mask > 0 (bin/predict.py:84).
@@ -500,6 +632,51 @@ extern "C" int lama_blend_quantize_u8_fwd(void* stream, const uint8_t* image_hwc
     p.B = batch; p.Hp = pred->H; p.Wp = pred->W; p.binarize = binarize;
     hipLaunchKernelGGL(blend_quantize_u8_kernel, dim3(ew_grid((long long)batch * pred->H * pred->W)), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
     LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// the evaluator's loader on u8 operands: see eval_ingest_u8_kernel
+extern "C" int lama_eval_ingest_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* pred_hwc, const uint8_t* mask, const int32_t* sizes,
+                                       int32_t Hs, int32_t Ws, int32_t pad_mod, int32_t clamp, float clamp_lo, float clamp_hi,
+                                       const lama_tensor* out_image, const lama_tensor* out_pred, int64_t* mask_sum, int32_t batch) {
+    if (!image_hwc || !pred_hwc || !mask || !out_image || !out_pred || !out_image->ptr || !out_pred->ptr || !mask_sum) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0 || pad_mod <= 0) return LAMA_ERR_BAD_ARG;
+    if (out_image->C != 3 || out_pred->C != 3 || out_image->H <= 0 || out_image->W <= 0 || !same_hw(out_image, out_pred)) return LAMA_ERR_BAD_ARG;
+    if (clamp && !(clamp_lo <= clamp_hi)) return LAMA_ERR_BAD_ARG;
+    if (((uintptr_t)out_image->ptr & 3) || ((uintptr_t)out_pred->ptr & 3) || ((uintptr_t)mask_sum & 7)) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({out_image, out_pred})) return LAMA_ERR_UNSUPPORTED;
+    const int Hp = out_image->H, Wp = out_image->W;
+    const auto ceil_mod = [pad_mod](long long v) { return (v + pad_mod - 1) / pad_mod * pad_mod; };           // data.py:23-26
+    bool small = false;
+    for (int b = 0; b < batch; ++b) {
+        const int h = sizes ? sizes[2 * b] : Hs, w = sizes ? sizes[2 * b + 1] : Ws;
+        if (h <= 0 || w <= 0 || h > Hs || w > Ws) return LAMA_ERR_BAD_ARG;
+        if (ceil_mod(h) != Hp || ceil_mod(w) != Wp) return LAMA_ERR_BAD_ARG;          // one padded size per launch: the outputs are one tensor
+        small = small || Hp - h > h || Wp - w > w;
+    }
+    if (small) return LAMA_ERR_UNSUPPORTED;                   // padding beyond the image's own extent (np.pad's periodic mirror) is not served
+    const size_t slot = (size_t)Hs * Ws;
+    for (int b0 = 0; b0 < batch; b0 += LAMA_EI_MAX_BATCH) {   // the sizes ride in the argument block: LAMA_EI_MAX_BATCH images per launch
+        EvalIngestParams p;
+        memset(&p, 0, sizeof(p));
+        p.B = batch - b0 < LAMA_EI_MAX_BATCH ? batch - b0 : LAMA_EI_MAX_BATCH;
+        p.gt = image_hwc + b0 * slot * 3; p.pred = pred_hwc + b0 * slot * 3; p.mask = mask + b0 * slot;
+        p.out_img = (float*)out_image->ptr + b0 * out_image->batch_stride; p.img_bs = out_image->batch_stride;
+        p.out_pred = (float*)out_pred->ptr + b0 * out_pred->batch_stride; p.pred_bs = out_pred->batch_stride;
+        p.sums = (long long*)mask_sum + b0;
+        p.lo = clamp_lo; p.hi = clamp_hi; p.clamp = clamp != 0;
+        p.Hs = Hs; p.Ws = Ws; p.Hp = Hp; p.Wp = Wp;
+        p.vec_ld = Ws % 4 == 0 && !((uintptr_t)p.gt & 3) && !((uintptr_t)p.pred & 3);
+        p.vec_st = Wp % 4 == 0 && !((uintptr_t)p.out_img & 15) && !((uintptr_t)p.out_pred & 15) && p.img_bs % 4 == 0 && p.pred_bs % 4 == 0;
+        for (int b = 0; b < p.B; ++b) {
+            p.sizes[b][0] = sizes ? sizes[2 * (b0 + b)] : Hs;
+            p.sizes[b][1] = sizes ? sizes[2 * (b0 + b) + 1] : Ws;
+        }
+        const int grid = p.B + ew_grid((long long)p.B * Hp * ((Wp + 3) / 4));
+        hipLaunchKernelGGL(eval_ingest_u8_kernel, dim3(grid), dim3(LAMA_NTHREADS), LAMA_NTHREADS * sizeof(unsigned long long), (hipStream_t)stream,
+                           p);
+        LAMA_CHECK_LAUNCH();
+    }
     return LAMA_OK;
 }
 

@@ -1,9 +1,12 @@
 """Quality evaluators on the HIP path.
 
 SSIM: ``saicinpainting/evaluation/losses/ssim.py`` ``SSIM`` as one launch pair (``lama_ssim_fwd``, csrc/metrics.hip), same constructor, same
-``forward(img1, img2)``.  ``SSIMScore`` (``losses/base_loss.py``) wraps it, ``InpaintingEvaluator`` / ``InpaintingEvaluatorOnline``
-(``evaluator.py``) are bookkeeping around the scores: the switch for a reference user is ONE import -- ``from lama_amd.evaluation import SSIM`` in
-``losses/base_loss.py`` -- and the reference's own evaluator, grouping and reporting code keeps running unchanged.
+``forward(img1, img2)``.  Around the scores, with the reference's names, constructor arguments and result dicts: ``get_groupings``,
+``PairwiseScore``, ``SSIMScore``, ``LPIPSScore`` (``losses/base_loss.py``), ``InpaintingEvaluator`` / ``InpaintingEvaluatorOnline``
+(``evaluator.py``), ``make_evaluator`` (``evaluation/__init__.py``) and ``PrecomputedInpaintingResultsDataset`` (``data.py``), which yields the
+u8 arrays that are on disk: ``InpaintingEvaluator.evaluate()`` then runs the device loop of ``lama_amd/evaluate.py`` (the counterpart of
+``bin/evaluate_predicts.py``; one ``lama_eval_ingest_u8_fwd`` launch per batch).  A reference user may still switch ONE import --
+``from lama_amd.evaluation import SSIM`` in ``losses/base_loss.py`` -- and keep the reference's own evaluator code.
 
 LPIPS: ``losses/lpips.py`` ``PerceptualLoss(model='net-lin', net='vgg')`` and ``base_loss.LPIPSScore``.  Pred and target go through the VGG-16
 backbone as ONE batch of 2N images: ``lama_lpips_scale_fwd`` writes both scaled inputs into one tensor, the thirteen zero-padded 3x3 convs + ReLU
@@ -17,6 +20,8 @@ FID and the segmentation-aware scores are pretrained networks of another order (
 from __future__ import annotations
 
 import collections
+import glob
+import math
 import os
 import warnings
 from typing import Optional
@@ -401,25 +406,33 @@ class PerceptualLoss(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------------
-# losses/base_loss.py: LPIPSScore
+# losses/base_loss.py: get_groupings, PairwiseScore, SSIMScore, LPIPSScore
 # ----------------------------------------------------------------------------------------------------
 
 def _mean_std(v: np.ndarray) -> dict:
     return {'mean': v.mean(), 'std': v.std()}
 
 
-class LPIPSScore(nn.Module):
-    """base_loss.py:54-118 (PairwiseScore + LPIPSScore): ``forward`` returns the batch's values flattened to [N] and appends them to
-    ``individual_values``; ``get_value(groups, states)`` -> ({'mean', 'std'}, per-group dict or None); ``reset``."""
+def get_groupings(groups) -> dict:
+    """{group label: the indices of its elements}; inside a group the indices come in the order ``np.argsort(groups)`` leaves them, as in the
+    reference's function of this name (losses/base_loss.py)."""
+    groups = np.asarray(groups)
+    order = np.argsort(groups)
+    labels, first = np.unique(groups[order], return_index=True)        # groups[order] is sorted: one run per label
+    return dict(zip(labels, np.split(order, first[1:])))
 
-    def __init__(self, model='net-lin', net='vgg', model_path=None, use_gpu=True, backbone=None):
+
+class PairwiseScore(nn.Module):
+    """What every per-image score of the evaluator keeps (the reference's class of this name): ``individual_values``, the float64 vector of the
+    values seen since ``reset()``; ``get_value(groups, states)`` -> ({'mean', 'std'}, {label: {'mean', 'std'}} or None), over
+    ``individual_values`` or, when given, over the concatenated ``states`` (the batches' returned tensors).  A subclass sets ``self.score`` (the
+    module that maps (prediction, target) to one value per image) and returns ``self._keep(values)`` from ``forward``."""
+
+    def __init__(self):
         super().__init__()
         self.individual_values = None
-        self.score = PerceptualLoss(model=model, net=net, model_path=model_path, use_gpu=use_gpu, spatial=False, backbone=backbone).eval()
-        self.reset()
 
-    def forward(self, pred_batch, target_batch, mask=None):
-        batch_values = self.score(pred_batch, target_batch).flatten()
+    def _keep(self, batch_values: torch.Tensor) -> torch.Tensor:
         self.individual_values = np.hstack([self.individual_values, batch_values.detach().cpu().numpy()])
         return batch_values
 
@@ -433,3 +446,265 @@ class LPIPSScore(nn.Module):
 
     def reset(self):
         self.individual_values = []
+
+
+class SSIMScore(PairwiseScore):
+    """The reference's SSIMScore: per-image SSIM (``SSIM(window_size, size_average=False)``) of (prediction, target); the mask is not used."""
+
+    def __init__(self, window_size: int = 11):
+        super().__init__()
+        self.score = SSIM(window_size=window_size, size_average=False).eval()
+        self.reset()
+
+    def forward(self, pred_batch, target_batch, mask=None):
+        return self._keep(self.score(pred_batch, target_batch))
+
+
+class LPIPSScore(PairwiseScore):
+    """The reference's LPIPSScore: ``forward`` returns the batch's values flattened to [N] and appends them to ``individual_values``."""
+
+    def __init__(self, model='net-lin', net='vgg', model_path=None, use_gpu=True, backbone=None):
+        super().__init__()
+        self.score = PerceptualLoss(model=model, net=net, model_path=model_path, use_gpu=use_gpu, spatial=False, backbone=backbone).eval()
+        self.reset()
+
+    def forward(self, pred_batch, target_batch, mask=None):
+        return self._keep(self.score(pred_batch, target_batch).flatten())
+
+
+# ----------------------------------------------------------------------------------------------------
+# evaluation/evaluator.py, evaluation/__init__.py, evaluation/data.py: the bookkeeping around the scores
+# ----------------------------------------------------------------------------------------------------
+
+def _interval_names(bins: int, bin_edges: np.ndarray) -> list:
+    """The rows of the report: '0-10%' ... '90-100%' for 10 bins, one more decimal per further power of ten of ``bins``."""
+    digits = max(0, math.ceil(math.log10(bins)) - 1)
+    percent = ['%.*f' % (digits, round(100 * edge, digits)) for edge in bin_edges]
+    return [f'{lo}-{hi}%' for lo, hi in zip(percent, percent[1:])]
+
+
+def mask_area(mask_sums, plane) -> np.ndarray:
+    """The mask area of the device path, BY DEFINITION: ``sum of the padded u8 mask / (255 * Hp * Wp)`` in fp64, from the exact integer sums
+    ``lama_eval_ingest_u8_fwd`` leaves.  (The reference's fp32 ``mask.mean()`` depends on the reduction order in its last ulp; this does not.)"""
+    sums = mask_sums.detach().cpu().numpy() if torch.is_tensor(mask_sums) else np.asarray(mask_sums)
+    return sums.astype(np.float64) / (255.0 * np.asarray(plane, dtype=np.float64))      # plane: Hp * Wp, one number or one per image
+
+
+def _result_table(scores, groups, interval_names, states=None, integral=(None, None)) -> dict:
+    """{(score name, 'total' | interval name): {'mean', 'std'}}: per score its total, then its non-empty groups in label order; ``states`` =
+    the per-batch dicts an online evaluator returned; ``integral`` = (title, function of this table) adds one more 'total' row."""
+    table = {}
+    for name, score in scores.items():
+        own = None if states is None else [batch[name] for batch in states]
+        total, per_group = score.get_value(groups=groups, states=own)
+        table[(name, 'total')] = total
+        for label, stats in (per_group or {}).items():
+            table[(name, interval_names[label])] = stats
+    title, func = integral
+    if func is not None:
+        table[(title, 'total')] = dict(mean=func(table))
+    return table
+
+
+class InpaintingEvaluator:
+    """evaluator.py:16-109.  ``evaluate()`` returns {(score name, 'total' | 'a-b%'): {'mean', 'std'}}.  A dataset of u8 items
+    (``PrecomputedInpaintingResultsDataset`` below) is scored by the device loop of ``lama_amd.evaluate`` -- u8 upload, one ingest launch per
+    batch, every score on the same tensors; any other dataset (float ``image`` / ``mask`` / ``inpainted`` items of one size, as the reference's
+    loaders yield them) by the reference's loop: one pass over the dataset for the groups and one per score."""
+
+    def __init__(self, dataset, scores, area_grouping=True, bins=10, batch_size=32, device='cuda', integral_func=None, integral_title=None,
+                 clamp_image_range=None):
+        self.dataset, self.scores = dataset, scores
+        self.area_grouping, self.bins = area_grouping, bins
+        self.batch_size, self.device = batch_size, torch.device(device)
+        self.integral_func, self.integral_title = integral_func, integral_title
+        self.clamp_image_range = clamp_image_range
+
+    def _dataloader(self):
+        return torch.utils.data.DataLoader(self.dataset, shuffle=False, batch_size=self.batch_size)
+
+    def bin_edges(self):
+        bin_edges = np.linspace(0, 1, self.bins + 1)
+        return bin_edges, _interval_names(self.bins, bin_edges)
+
+    def bins_of_area(self, area: np.ndarray) -> np.ndarray:
+        """evaluator.py:59-61: ``searchsorted(side='right') - 1``; an area of exactly 1 belongs to the last bin."""
+        bin_indices = np.searchsorted(self.bin_edges()[0], area, side='right') - 1
+        bin_indices[bin_indices == self.bins] = self.bins - 1
+        return bin_indices
+
+    def bins_of_mask_sums(self, mask_sums, plane) -> np.ndarray:
+        return self.bins_of_area(mask_area(mask_sums, plane))
+
+    def _get_bin_edges(self):
+        _, interval_names = self.bin_edges()
+        groups = []
+        for batch in self._dataloader():
+            mask = batch['mask']
+            area = mask.to(self.device).reshape(mask.shape[0], -1).mean(dim=-1)
+            groups.append(self.bins_of_area(area.detach().cpu().numpy()))
+        return np.hstack(groups), interval_names
+
+    def results_of(self, groups, interval_names) -> dict:
+        """The result dict of scores that hold their values."""
+        return _result_table(self.scores, groups, interval_names, integral=(self.integral_title, self.integral_func))
+
+    def _float_batches(self):
+        """(image, mask, prediction or None) of every batch of a float dataset, on the device, the image clamped."""
+        for batch in self._dataloader():
+            image, mask, inpainted = (None if batch.get(k) is None else batch[k].to(self.device) for k in ('image', 'mask', 'inpainted'))
+            if self.clamp_image_range is not None:
+                image = image.clamp(*self.clamp_image_range)
+            yield image, mask, inpainted
+
+    def evaluate(self, model=None):
+        if getattr(self.dataset, 'u8_items', False):
+            if model is not None:
+                raise NotImplementedError('InpaintingEvaluator on u8 items scores precomputed predictions (model=None); run lama_amd.predict first')
+            from . import evaluate as _loop                      # the device loop lives beside its CLI
+            groups, interval_names = _loop.score_dataset(self.dataset, self.scores, batch_size=self.batch_size, device=self.device,
+                                                         clamp_image_range=self.clamp_image_range, evaluator=self)
+            return self.results_of(groups if self.area_grouping else None, interval_names)
+        groups, interval_names = self._get_bin_edges() if self.area_grouping else (None, None)
+        with torch.no_grad():
+            for score in self.scores.values():               # as the reference: one pass over the dataset per score
+                score.to(self.device)
+                score.reset()
+                for image, mask, inpainted in self._float_batches():
+                    if model is not None:
+                        inpainted = model(image, mask)
+                    elif inpainted is None:
+                        raise LamaError("InpaintingEvaluator.evaluate(model=None) scores precomputed predictions: the items need an 'inpainted' entry")
+                    score(inpainted, image, mask)
+        return self.results_of(groups, interval_names)
+
+
+def _fid_absent(what: str):
+    return NotImplementedError(f'{what}: FID is not served on the HIP path (it needs a pretrained Inception-v3, whose definition and weights '
+                               'lama_amd neither ships nor downloads); use ssim / lpips, or the reference evaluator for the FID column')
+
+
+def ssim_fid100_f1(metrics, fid_scale=100):          # evaluator.py:112-117
+    raise _fid_absent('ssim_fid100_f1')
+
+
+def lpips_fid100_f1(metrics, fid_scale=100):         # evaluator.py:120-125
+    raise _fid_absent('lpips_fid100_f1')
+
+
+class InpaintingEvaluatorOnline(nn.Module):
+    """evaluator.py:129-220: ``forward(batch)`` scores one batch and records its groups, ``evaluation_end(states)`` returns the result dict and
+    resets.  ``batch['mask']`` is the float mask as in the reference; a batch of the device loop carries ``batch['mask_sum']`` (int64 [B], from
+    ``lama_eval_ingest_u8_fwd``) instead and the area is ``mask_area`` of it over the image plane."""
+
+    def __init__(self, scores, bins=10, image_key='image', inpainted_key='inpainted', integral_func=None, integral_title=None,
+                 clamp_image_range=None):
+        super().__init__()
+        self.scores = nn.ModuleDict(scores)
+        self.image_key, self.inpainted_key = image_key, inpainted_key
+        self.integral_func, self.integral_title = integral_func, integral_title
+        self.clamp_image_range = clamp_image_range
+        self.bins_num, self.bin_edges = bins, np.linspace(0, 1, bins + 1)
+        self.interval_names = _interval_names(bins, self.bin_edges)
+        self.groups = []                                     # the bin of every image seen since the last evaluation_end
+
+    def bins_of_area(self, area: np.ndarray) -> np.ndarray:
+        """evaluator.py:165: ``clip(searchsorted - 1, 0, bins - 1)`` (side='left': an area ON an edge belongs to the bin below)."""
+        return np.clip(np.searchsorted(self.bin_edges, area) - 1, 0, self.bins_num - 1)
+
+    def _get_bins(self, mask_batch):
+        area = mask_batch.view(mask_batch.shape[0], -1).mean(dim=-1).detach().cpu().numpy()
+        return self.bins_of_area(area)
+
+    def forward(self, batch):
+        image, inpainted, mask = batch[self.image_key], batch[self.inpainted_key], batch.get('mask')
+        with torch.no_grad():
+            if self.clamp_image_range is not None:
+                image = image.clamp(*self.clamp_image_range)
+            if mask is not None:
+                bins = self._get_bins(mask)
+            else:
+                bins = self.bins_of_area(mask_area(batch['mask_sum'], image.shape[-2] * image.shape[-1]))
+            self.groups.extend(bins)
+            return {name: score(inpainted, image, mask) for name, score in self.scores.items()}
+
+    def process_batch(self, batch):
+        return self(batch)
+
+    def evaluation_end(self, states=None):
+        """The result dict over everything seen since the last call (``states``: the dicts ``forward`` returned, when the caller gathered them
+        itself); forgets the groups and resets the scores."""
+        results = _result_table(self.scores, np.array(self.groups), self.interval_names, states=states,
+                                integral=(self.integral_title, self.integral_func))
+        self.groups = []
+        for score in self.scores.values():
+            score.reset()
+        return results
+
+
+def make_evaluator(kind='default', ssim=True, lpips=True, fid=False, integral_kind=None, **kwargs):
+    """evaluation/__init__.py:9-33 without FID (``fid`` defaults to False here; True raises, as does an integral kind built on FID).
+    ``lpips_kwargs`` = dict(model_path=..., backbone=...) reaches ``LPIPSScore`` (nothing is downloaded)."""
+    lpips_kwargs = kwargs.pop('lpips_kwargs', None) or {}
+    if fid:
+        raise _fid_absent('make_evaluator(fid=True)')
+    if integral_kind is not None:
+        if integral_kind not in ('ssim_fid100_f1', 'lpips_fid100_f1'):
+            raise ValueError(f'Unexpected integral_kind={integral_kind}')
+        raise _fid_absent(f'make_evaluator(integral_kind={integral_kind!r})')
+    metrics = {}
+    if ssim:
+        metrics['ssim'] = SSIMScore()
+    if lpips:
+        metrics['lpips'] = LPIPSScore(**lpips_kwargs)
+    if kind == 'default':
+        return InpaintingEvaluatorOnline(scores=metrics, integral_func=None, integral_title=integral_kind, **kwargs)
+
+
+class PrecomputedInpaintingResultsDataset:
+    """data.py:58-67,110-124: the (image, mask, prediction) triples of a dataset directory and a prediction directory, paired as the reference
+    pairs them.  Items are what is on disk: ``image`` / ``inpainted`` u8 [h, w, 3] (RGB), ``mask`` u8 [h, w] (PIL decode) -- the / 255, the padding
+    to ``pad_out_to_modulo`` and the layout change happen on the device (``lama_eval_ingest_u8_fwd``)."""
+
+    u8_items = True
+
+    def __init__(self, datadir, predictdir, inpainted_suffix='_inpainted.jpg', img_suffix='.jpg', pad_out_to_modulo=None, scale_factor=None):
+        if scale_factor is not None:
+            raise NotImplementedError('PrecomputedInpaintingResultsDataset: scale_factor is not served by the evaluator (score predictions at '
+                                      'the size they were made: lama_amd.predict applies dataset.scale_factor itself)')
+        self.datadir, self.predictdir = datadir, predictdir
+        self.pad_out_to_modulo, self.scale_factor = pad_out_to_modulo, None
+        # <name>_mask<anything>.png anywhere under datadir belongs to <name><img_suffix> beside it and to the prediction at the same relative
+        # path under predictdir, its '.png' replaced by inpainted_suffix
+        root = os.path.join(datadir, '')                      # (with its trailing separator)
+        self.mask_filenames = sorted(glob.glob(os.path.join(datadir, '**', '*mask*.png'), recursive=True))
+        self.img_filenames = [(m.rpartition('_mask')[0] or m) + img_suffix for m in self.mask_filenames]
+        self.pred_filenames = [os.path.join(predictdir, os.path.splitext(m[len(root):])[0] + inpainted_suffix) for m in self.mask_filenames]
+
+    @property
+    def pad_mod(self) -> int:
+        return int(self.pad_out_to_modulo) if self.pad_out_to_modulo is not None and self.pad_out_to_modulo > 1 else 1
+
+    def __len__(self):
+        return len(self.mask_filenames)
+
+    @staticmethod
+    def _load(fname, mode):
+        from PIL import Image
+        return np.array(Image.open(fname).convert(mode))
+
+    def size(self, i):
+        """(h, w) of item i from the mask file's header (no decode)."""
+        from PIL import Image
+        with Image.open(self.mask_filenames[i]) as im:
+            return im.size[1], im.size[0]
+
+    def __getitem__(self, i):
+        result = dict(image=self._load(self.img_filenames[i], 'RGB'), mask=self._load(self.mask_filenames[i], 'L'),
+                      inpainted=self._load(self.pred_filenames[i], 'RGB'))
+        if result['image'].shape[:2] != result['mask'].shape or result['inpainted'].shape != result['image'].shape:
+            raise LamaError(f"{self.mask_filenames[i]}: image {result['image'].shape}, mask {result['mask'].shape} and prediction "
+                            f"{result['inpainted'].shape} differ in size")
+        if self.pad_mod > 1:
+            result['unpad_to_size'] = result['image'].shape[:2]
+        return result
