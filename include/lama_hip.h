@@ -407,6 +407,46 @@ size_t lama_lpips_layer_workspace_bytes(int32_t batch, int32_t C, int32_t H, int
 int lama_lpips_layer_fwd(void* stream, const lama_tensor* f0, const lama_tensor* f1, int32_t batch, const float* w, float* acc,
                          const lama_tensor* pool0, const lama_tensor* pool1, void* workspace, size_t workspace_bytes);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) FID: the Inception-v3 feature extractor (saicinpainting/evaluation/losses/fid/inception.py, fid_score.py) -----------------------
+ * What torchvision's Inception3 needs beyond lama_conv2d_fwd: rectangular kernels with per-axis zero padding, any channel count, 3x3 max / average
+ * pooling, the global average pool and the bilinear resize of the input.  fp32 NCHW views; x and y may be channel slices of wider buffers (an
+ * Inception branch stores straight into its block's concatenation buffer: torch.cat is free).
+ *
+ * lama_conv2d_rect_fwd: y = act( conv2d(x, w, stride, padding=(pad_h, pad_w)) + bias ), zero padding, not transposed, cin = x.C >= 1, cout = y.C >= 1,
+ *   kh, kw in 1..7, stride 1 or 2, act LAMA_ACT_NONE / LAMA_ACT_RELU.  y.H = (x.H + 2 pad_h - kh) / stride + 1 (floor), y.W likewise: any other
+ *   y view is LAMA_ERR_BAD_ARG; a kernel size or stride outside the ranges is LAMA_ERR_UNSUPPORTED.  Implicit GEMM on v_mfma_f32_32x32x16 with the
+ *   3-term split (LAMA_PREC_F16X3 / LAMA_PREC_BF16X3; LAMA_PREC_F32: LAMA_ERR_UNSUPPORTED) and fp32 accumulation; M = cout and N = batch * Ho * Wo
+ *   are tiled, K = cin * kh * kw never is split: every output is one k-ordered sum, bit-identical run to run.  range_flag: as in lama_conv2d_args.
+ *   w_packed = lama_conv2d_rect_pack_weight(Conv2d weights [cout, cin, kh, kw], scale[o] folded (NULL = 1)); 16-byte aligned,
+ *   lama_conv2d_rect_packed_weight_bytes bytes (0: unsupported geometry / precision).  The K tail and the M tail are zero-filled. */
+typedef struct lama_conv2d_rect_args {
+    lama_tensor x;
+    const void* w_packed;
+    const float* bias; /* [cout] (the folded BatchNorm shift) or NULL */
+    int32_t act;
+    lama_tensor y;
+    int32_t batch;
+    int32_t kh, kw, stride, pad_h, pad_w;
+    int32_t precision;
+    uint32_t* range_flag;
+} lama_conv2d_rect_args;
+int64_t lama_conv2d_rect_packed_weight_bytes(int32_t cout, int32_t cin, int32_t kh, int32_t kw, int32_t precision);
+int lama_conv2d_rect_pack_weight(void* stream, const float* w, const float* scale, int32_t cout, int32_t cin, int32_t kh, int32_t kw,
+                                 int32_t precision, void* dst);
+int lama_conv2d_rect_fwd(void* stream, const lama_conv2d_rect_args* args);
+/* lama_pool3x3_fwd: 3x3 window, stride 1 or 2, pad 0 or 1, y.H = (x.H + 2 pad - 3) / stride + 1.  LAMA_POOL_MAX = F.max_pool2d (padding never wins);
+ * LAMA_POOL_AVG_EXCLUDE_PAD = F.avg_pool2d(count_include_pad=False): the taps inside the plane are added in one fixed order (rows, then columns) in
+ * fp32 and divided once by their number. */
+#define LAMA_POOL_MAX 0
+#define LAMA_POOL_AVG_EXCLUDE_PAD 1
+int lama_pool3x3_fwd(void* stream, const lama_tensor* x, const lama_tensor* y, int32_t batch, int32_t mode, int32_t stride, int32_t pad);
+/* lama_global_avgpool_fwd: x [batch, C, h, w] -> y [batch, C] (contiguous device floats): the fp64 sum in index order, divided and rounded once. */
+int lama_global_avgpool_fwd(void* stream, const lama_tensor* x, float* y, int32_t batch);
+/* lama_fid_input_fwd: pred, target [batch, 3, H, W] in [0, 1] -> y [2 batch, 3, y.H, y.W] (pred first): F.interpolate(mode='bilinear',
+ * align_corners=False) without antialiasing (the coordinate arithmetic of lama_bilinear_fwd) to y's size (299 x 299 for FID), then 2 x - 1
+ * (inception.py:196-203).  resize = 0: 2 x - 1 only, y.H = H, y.W = W. */
+int lama_fid_input_fwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* y, int32_t batch, int32_t resize);
+
 #ifdef __cplusplus
 }
 #endif

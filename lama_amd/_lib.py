@@ -19,6 +19,7 @@ CONV_COOPERATIVE = 1
 CONV_DEFER_OUT = 2          # lama_winograd_conv3x3_fwd: the GEMM launch only (include/lama_hip.h)
 CONV_SIBLINGS_SHIFT = 8     # (v109) bits 8..10: log2 of the number of sibling launches that share the chip with this one
 DT_F32, DT_F16 = 0, 1
+POOL_MAX, POOL_AVG_EXCLUDE_PAD = 0, 1      # lama_pool3x3_fwd mode
 ABI_VERSION = 112      # LAMA_HIP_VERSION of include/lama_hip.h
 PREC_NAMES = {'f32': PREC_F32, 'bf16x3': PREC_BF16X3, 'f16x3': PREC_F16X3, 'f16': PREC_F16}
 
@@ -55,6 +56,13 @@ class Conv2dArgs(C.Structure):
                 ('resid', Tensor4), ('y', Tensor4), ('batch', C.c_int32), ('precision', C.c_int32),
                 ('range_flag', C.c_void_p), ('fuse1_w', C.c_void_p), ('fuse1_bias', C.c_void_p), ('fuse1_y', Tensor4),
                 ('flags', C.c_int32)]
+
+
+class Conv2dRectArgs(C.Structure):
+    """struct lama_conv2d_rect_args"""
+    _fields_ = [('x', Tensor4), ('w_packed', C.c_void_p), ('bias', C.c_void_p), ('act', C.c_int32), ('y', Tensor4), ('batch', C.c_int32),
+                ('kh', C.c_int32), ('kw', C.c_int32), ('stride', C.c_int32), ('pad_h', C.c_int32), ('pad_w', C.c_int32),
+                ('precision', C.c_int32), ('range_flag', C.c_void_p)]
 
 
 def view(t: Optional[torch.Tensor], c0: int = 0, c: Optional[int] = None) -> Tensor4:
@@ -161,6 +169,12 @@ class LamaLib:
         L.lama_winograd_preferred.restype, L.lama_winograd_preferred.argtypes = i32, [i32, i32, i32, i32, i32, i32]
         L.lama_winograd_conv3x3_fwd.restype, L.lama_winograd_conv3x3_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dArgs), vp, C.c_size_t]
         L.lama_multidilated_conv3x3_fwd.restype, L.lama_multidilated_conv3x3_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dArgs), i32, i32]
+        L.lama_conv2d_rect_packed_weight_bytes.restype, L.lama_conv2d_rect_packed_weight_bytes.argtypes = i64, [i32] * 5
+        L.lama_conv2d_rect_pack_weight.restype, L.lama_conv2d_rect_pack_weight.argtypes = C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+        L.lama_conv2d_rect_fwd.restype, L.lama_conv2d_rect_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dRectArgs)]
+        L.lama_pool3x3_fwd.restype, L.lama_pool3x3_fwd.argtypes = C.c_int, [vp, T, T, i32, i32, i32, i32]
+        L.lama_global_avgpool_fwd.restype, L.lama_global_avgpool_fwd.argtypes = C.c_int, [vp, T, vp, i32]
+        L.lama_fid_input_fwd.restype, L.lama_fid_input_fwd.argtypes = C.c_int, [vp, T, T, T, i32, i32]
         del dp
         if L.lama_version() != ABI_VERSION:
             raise LamaError(f'{path}: ABI version {L.lama_version()} != {ABI_VERSION}')
@@ -522,6 +536,56 @@ class LamaLib:
 
     def lpips_layer_workspace_bytes(self, batch: int, c: int, h: int, w: int) -> int:
         return int(self._l.lama_lpips_layer_workspace_bytes(batch, c, h, w))
+
+    # -- FID: Inception-v3 (new symbols in v112) ----------------------------------------------------------------
+    def pack_conv_rect_weight(self, w: torch.Tensor, scale: Optional[torch.Tensor], precision: int = PREC_F16X3) -> torch.Tensor:
+        """Conv2d weight [cout, cin, kh, kw] (+ folded BatchNorm scale) -> the packed device buffer of lama_conv2d_rect_fwd."""
+        if not self.host_emulated and not w.is_cuda:
+            raise LamaError('pack_conv_rect_weight: the weights are on the CPU: move the module to the GPU first')
+        w = w.contiguous().float()
+        if scale is not None and scale.device != w.device:
+            raise LamaError(f'pack_conv_rect_weight: weight on {w.device} but BatchNorm scale on {scale.device}')
+        cout, cin, kh, kw = w.shape
+        nbytes = self._l.lama_conv2d_rect_packed_weight_bytes(cout, cin, kh, kw, precision)
+        if nbytes <= 0:
+            raise LamaError(f'unsupported rect conv geometry {tuple(w.shape)} / precision {precision}', code=ERR_UNSUPPORTED)
+        if precision == PREC_F16X3 and w.numel():
+            ws = w if scale is None else w * scale.float().view(-1, 1, 1, 1)
+            amax = float(ws.abs().max())
+            if not amax <= F16_MAX:
+                raise LamaRangeError(f'folded conv weight |w| max {amax:.3g} exceeds the fp16 split range ({F16_MAX}); use bf16x3')
+        dst = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+        sc = None if scale is None else scale.contiguous().float()
+        self.check(self._l.lama_conv2d_rect_pack_weight(self.stream_of(w), w.data_ptr(), None if sc is None else sc.data_ptr(), cout, cin, kh, kw,
+                                                        precision, dst.data_ptr()), 'lama_conv2d_rect_pack_weight')
+        if w.is_cuda:
+            torch.cuda.current_stream(w.device).synchronize()  # w / sc may be temporaries
+        return dst
+
+    def conv2d_rect(self, x: Tensor4, w_packed: torch.Tensor, y: Tensor4, batch: int, kh: int, kw: int, stride: int = 1, pad_h: int = 0,
+                    pad_w: int = 0, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, precision: int = PREC_F16X3, stream: int = 0,
+                    range_flag: Optional[torch.Tensor] = None):
+        """lama_conv2d_rect_fwd: zero-padded kh x kw convolution with per-axis padding; x / y may be channel-slice views."""
+        a = Conv2dRectArgs()
+        a.x, a.w_packed, a.y = x, w_packed.data_ptr(), y
+        a.bias = None if bias is None else bias.data_ptr()
+        a.act, a.batch, a.kh, a.kw, a.stride, a.pad_h, a.pad_w, a.precision = act, batch, kh, kw, stride, pad_h, pad_w, precision
+        a.range_flag = None if range_flag is None else range_flag.data_ptr()
+        self.check(self._l.lama_conv2d_rect_fwd(stream, C.byref(a)), 'lama_conv2d_rect_fwd')
+
+    def pool3x3(self, x: Tensor4, y: Tensor4, batch: int, mode: int, stride: int, pad: int, stream: int = 0):
+        """lama_pool3x3_fwd: POOL_MAX or POOL_AVG_EXCLUDE_PAD (count_include_pad=False) over a 3x3 window."""
+        self.check(self._l.lama_pool3x3_fwd(stream, C.byref(x), C.byref(y), batch, mode, stride, pad), 'lama_pool3x3_fwd')
+
+    def global_avgpool(self, x: Tensor4, y: torch.Tensor, batch: int, stream: int = 0):
+        """lama_global_avgpool_fwd: [batch, C, h, w] -> y [batch, C] fp32 (fp64 sum, rounded once)."""
+        if y.dtype != torch.float32 or not y.is_contiguous() or y.numel() != batch * x.C or (not self.host_emulated and not y.is_cuda):
+            raise LamaError(f'global_avgpool: y is a contiguous device [batch, C] fp32 tensor, got {tuple(y.shape)} {y.dtype}')
+        self.check(self._l.lama_global_avgpool_fwd(stream, C.byref(x), y.data_ptr(), batch), 'lama_global_avgpool_fwd')
+
+    def fid_input(self, pred: Tensor4, target: Tensor4, y: Tensor4, batch: int, resize: bool = True, stream: int = 0):
+        """lama_fid_input_fwd: bilinear resize of pred | target to y's plane (resize) and 2 x - 1, into one [2 batch, 3, ., .] tensor."""
+        self.check(self._l.lama_fid_input_fwd(stream, C.byref(pred), C.byref(target), C.byref(y), batch, int(bool(resize))), 'lama_fid_input_fwd')
 
     def gauss5(self, x: Tensor4, y: Tensor4, batch: int, stream: int = 0):
         self.check(self._l.lama_gauss5_fwd(stream, C.byref(x), C.byref(y), batch), 'lama_gauss5_fwd')

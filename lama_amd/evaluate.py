@@ -1,21 +1,24 @@
 """Score precomputed predictions on the device: the counterpart of the reference's ``bin/evaluate_predicts.py``.
 
     python -m lama_amd.evaluate <config.yaml> <datadir> <predictdir> <outpath> [model_path=<heads .pth>] [backbone=<vgg16 .pth>]
-                                [batch_size=N] [io_threads=8] [precision=f16x3|bf16x3|f32]
+                                [fid_weights=<inception .pth>] [batch_size=N] [io_threads=8] [precision=f16x3|bf16x3|f32]
 
 ``config.yaml`` is one of the reference's ``configs/eval*.yaml``: ``evaluator_kwargs`` (batch_size, device, ...) and ``dataset_kwargs``
 (img_suffix, inpainted_suffix, pad_out_to_modulo) are honoured, ``segmentation.enable: true`` raises (the segmentation-aware scores need an
-ADE20k segmenter) and there is no FID column (evaluation.py).  ``outpath`` receives the table ``evaluate_predicts.py:41-43`` writes with pandas
--- rows ``total`` and the non-empty mask-area bins, columns (ssim | lpips) x (mean | std), tab-separated, ``%.4f`` -- written here without pandas.
+ADE20k segmenter).  ``outpath`` receives the table ``evaluate_predicts.py:41-43`` writes with pandas -- rows ``total`` and the non-empty
+mask-area bins, columns (ssim | lpips) x (mean | std), with ``fid_weights=`` also fid x mean and (when LPIPS is on) lpips_fid100_f1 x mean,
+tab-separated, ``%.4f`` -- written here without pandas.
 
 What differs from the reference's loop (one pass over the dataset per score, fp32 batches built on the host): the items are bucketed by padded
 size as ``lama_amd.predict`` buckets them, decoded on ``io_threads`` host threads (at most 16) into pinned u8 slots, uploaded as u8 (7 bytes per
 pixel instead of 28), and ONE pass serves everything: per batch the ingest launch (``lama_eval_ingest_u8_fwd``: / 255, symmetric padding, NCHW,
-clamp, the mask's integer sum), then SSIM, then LPIPS on the same two tensors, all on the current stream.  Nothing is read back per batch: the
-values of a bucket stay on the device until the bucket is done and are then put back in dataset order.
+clamp, the mask's integer sum), then SSIM, then LPIPS, then the FID Inception on the same two tensors, all on the current stream.  Nothing is
+read back per batch: the values of a bucket (for FID: its [n, 2048] activation rows) stay on the device until the bucket is done and are then
+put back in dataset order.
 
 LPIPS needs the linear heads (``model_path``: the reference's ``models/lpips_models/vgg.pth``) and the VGG-16 backbone (``backbone``:
-torchvision's ``vgg16-397923af.pth``); nothing is downloaded.  With neither given the run scores SSIM only and says so."""
+torchvision's ``vgg16-397923af.pth``); nothing is downloaded.  With neither given the run scores SSIM only and says so.  FID needs the FID
+Inception-v3 weights (``fid_weights``: ``pt_inception-2015-12-05-6726825d.pth``); without them the run says so and has no fid column."""
 from __future__ import annotations
 
 import math
@@ -93,9 +96,16 @@ class DeviceIngest:
         return self.out_image[:n], self.out_pred[:n], self.sums[:n]
 
 
+def _keeps_activations(score) -> bool:
+    return hasattr(score, 'activations') and hasattr(score, 'activations_pred')
+
+
 def _score_module(name: str, score):
+    if _keeps_activations(score):                           # FIDScore: two [n, dims] activation batches per call, no per-image value
+        return score.activations
     if not hasattr(score, 'score') or not hasattr(score, 'individual_values'):
-        raise TypeError(f'score {name!r} ({type(score).__name__}): the device loop serves the pairwise scores (SSIMScore, LPIPSScore)')
+        raise TypeError(f'score {name!r} ({type(score).__name__}): the device loop serves the pairwise scores (SSIMScore, LPIPSScore) and the '
+                        'scores that keep activations (FIDScore)')
     return score.score
 
 
@@ -115,7 +125,8 @@ def score_dataset(dataset, scores: dict, *, batch_size: int = 8, device='cuda', 
     for s in scores.values():
         s.to(device)
         s.reset()
-    values = {name: np.zeros(n_items, dtype=np.float64) for name in scores}
+    acts = {name: _keeps_activations(s) for name, s in scores.items()}
+    values = {name: ([None, None] if acts[name] else np.zeros(n_items, dtype=np.float64)) for name in scores}
     groups = np.zeros(n_items, dtype=np.int64)
     pool = ThreadPoolExecutor(max(1, min(MAX_IO_THREADS, int(io_threads))))
     try:
@@ -135,18 +146,31 @@ def score_dataset(dataset, scores: dict, *, batch_size: int = 8, device='cuda', 
                     image, pred, sums = ing.run(r & 1, ing.fill(r & 1, items))
                     kept_sums.append(sums.clone())
                     for name, m in modules.items():
-                        kept[name].append(m(pred, image).flatten().clone())
+                        if acts[name]:
+                            kept[name].append(tuple(a.clone() for a in m(pred, image)))
+                        else:
+                            kept[name].append(m(pred, image).flatten().clone())
                     if tap is not None:
                         tap(idx, image, pred, {name: kept[name][-1] for name in scores}, kept_sums[-1])
                 flat = np.asarray(bucket['items'])
                 for name in scores:                          # the bucket's one read-back
-                    values[name][flat] = torch.cat(kept[name]).cpu().numpy()
+                    if acts[name]:
+                        for side in (0, 1):                  # [N, dims] rows of the predictions / the ground truth, dataset order
+                            rows = torch.cat([k[side] for k in kept[name]]).cpu().numpy()
+                            if values[name][side] is None:
+                                values[name][side] = np.zeros((n_items, rows.shape[1]), dtype=rows.dtype)
+                            values[name][side][flat] = rows
+                    else:
+                        values[name][flat] = torch.cat(kept[name]).cpu().numpy()
                 Hp, Wp = bucket['shape']
                 groups[flat] = evaluator.bins_of_mask_sums(torch.cat(kept_sums), Hp * Wp)
     finally:
         pool.shutdown()
     for name, s in scores.items():
-        s.individual_values = values[name]                   # what np.hstack([[], fp32 batches]) leaves: float64, dataset order
+        if acts[name]:
+            s.activations_pred, s.activations_target = ([torch.from_numpy(v)] for v in values[name])      # one [N, dims] array each: ``groups`` indexes them
+        else:
+            s.individual_values = values[name]               # what np.hstack([[], fp32 batches]) leaves: float64, dataset order
     return groups, evaluator.bin_edges()[1]
 
 
@@ -181,7 +205,7 @@ def format_report(results: dict) -> str:
 
 # ---- the CLI -----------------------------------------------------------------------------------------------------------------------------
 
-OWN_KEYS = ('model_path', 'backbone', 'batch_size', 'io_threads', 'precision')
+OWN_KEYS = ('model_path', 'backbone', 'fid_weights', 'batch_size', 'io_threads', 'precision')
 DATASET_KEYS = ('img_suffix', 'inpainted_suffix', 'pad_out_to_modulo', 'scale_factor')
 EVALUATOR_KEYS = ('batch_size', 'device', 'area_grouping', 'bins', 'clamp_image_range')
 
@@ -200,7 +224,7 @@ def load_config(path: str) -> dict:
     return cfg
 
 
-def build_evaluator(config: dict, datadir: str, predictdir: str, *, model_path=None, backbone=None, batch_size=None,
+def build_evaluator(config: dict, datadir: str, predictdir: str, *, model_path=None, backbone=None, fid_weights=None, batch_size=None,
                     precision: Optional[str] = None, log=print) -> EV.InpaintingEvaluator:
     """The dataset, the scores and the evaluator an eval config asks for (``.dataset``, ``.scores`` of the returned evaluator)."""
     dataset = EV.PrecomputedInpaintingResultsDataset(datadir, predictdir, **(config.get('dataset_kwargs') or {}))
@@ -214,6 +238,16 @@ def build_evaluator(config: dict, datadir: str, predictdir: str, *, model_path=N
         if precision is not None:
             metrics['lpips'].score.set_precision(precision)
     kw = dict(config.get('evaluator_kwargs') or {})
+    if fid_weights is None:
+        log('lama_amd.evaluate: no fid_weights= (the FID Inception-v3 state dict) given: no fid column')
+    else:
+        metrics['fid'] = EV.FIDScore(weights=fid_weights)
+        if precision is not None:
+            if precision not in ('f16x3', 'bf16x3'):
+                raise L.LamaError(f'precision={precision}: the FID Inception runs in f16x3 or bf16x3 (lama_conv2d_rect_fwd has no {precision} form)')
+            metrics['fid'].model.set_precision(L.PREC_NAMES[precision])
+        if 'lpips' in metrics:                               # bin/evaluate_predicts.py:29-30: the integral row of the reference's report
+            kw.update(integral_func=EV.lpips_fid100_f1, integral_title='lpips_fid100_f1')
     if batch_size is not None:
         kw['batch_size'] = int(batch_size)
     return EV.InpaintingEvaluator(dataset, scores=metrics, **kw)
@@ -245,7 +279,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             print(f'unknown options: {unknown}', file=sys.stderr)
         return 2
     config = load_config(pos[0])
-    results = evaluate_predicts(config, pos[1], pos[2], pos[3], model_path=opts.get('model_path'), backbone=opts.get('backbone'),
+    results = evaluate_predicts(config, pos[1], pos[2], pos[3], model_path=opts.get('model_path'), backbone=opts.get('backbone'), fid_weights=opts.get('fid_weights'),
                                 batch_size=opts.get('batch_size'), io_threads=int(opts.get('io_threads', 8)), precision=opts.get('precision'))
     print(format_report(results), end='')
     return 0

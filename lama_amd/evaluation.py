@@ -15,7 +15,15 @@ the 2x2 max-pool that feeds the next slice (csrc/metrics.hip).  Module tree and 
 linear heads (``model_path``, the reference's ``models/lpips_models/vgg.pth``) and the backbone (``backbone``, e.g. torchvision's
 ``vgg16-397923af.pth``) are files or state dicts the caller supplies.  The other nets / models / ``spatial`` / ``Lab`` raise NotImplementedError.
 
-FID and the segmentation-aware scores are pretrained networks of another order (Inception-v3, an ADE20k segmenter): out of scope.
+FID: ``losses/fid/inception.py`` ``InceptionV3`` (the FID variant of torchvision's Inception-v3 up to pool3) and ``base_loss.FIDScore`` /
+``calculate_frechet_distance``.  Pred and target go through the network as ONE batch of 2N images: ``lama_fid_input_fwd`` resizes both to 299 x 299
+and applies 2x - 1 into one tensor, the 94 convolutions (BatchNorm folded, ReLU in the epilogue) are ``lama_conv2d_rect_fwd`` launches that store
+straight into their block's concatenation buffer, the poolings ``lama_pool3x3_fwd`` and ``lama_global_avgpool_fwd`` (csrc/inception.hip).  The
+architecture is restated below (torchvision is not a dependency); module tree and keys are the reference's ``blocks.K.J.*``, torchvision's keys
+(the format of ``pt_inception-2015-12-05-6726825d.pth``) load as well.  Nothing is downloaded: ``weights`` is a state dict or a path the caller
+supplies.  The Frechet distance is numpy only (two ``eigh`` in fp64 instead of scipy's ``sqrtm``).
+
+The segmentation-aware scores need a pretrained ADE20k segmenter: out of scope.
 """
 from __future__ import annotations
 
@@ -32,7 +40,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._lib import LamaError, LamaRangeError
-from .ffc import _Exec, _HipModule
+from .ffc import _Exec, _HipModule, _bn_fold
 from .pix2pixhd import Conv2dBN
 
 
@@ -473,6 +481,470 @@ class LPIPSScore(PairwiseScore):
 
 
 # ----------------------------------------------------------------------------------------------------
+# losses/fid/inception.py: InceptionV3 (use_fid_inception=True), restated from the published architecture (Szegedy et al. 2015, as
+# torchvision lays it out; the FID variant's three differences: average pools that leave the padding out of the divisor, a max pool in
+# Mixed_7c's pool branch, 1008 classes -- the classifier is not part of the feature extractor)
+# ----------------------------------------------------------------------------------------------------
+
+def _pair2(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def _c(name, cout, k=1, s=1, p=0):
+    return ('conv', name, cout, _pair2(k), s, _pair2(p))
+
+
+def _fork(*branches):
+    return ('fork', branches)
+
+
+_AVG = ('pool', L.POOL_AVG_EXCLUDE_PAD, 1, 1)
+_MAX1 = ('pool', L.POOL_MAX, 1, 1)
+_MAX2 = ('pool', L.POOL_MAX, 2, 0)
+_GAP = ('gap',)
+
+
+def _inc_a(pf):
+    return [[_c('branch1x1', 64)], [_c('branch5x5_1', 48), _c('branch5x5_2', 64, 5, 1, 2)],
+            [_c('branch3x3dbl_1', 64), _c('branch3x3dbl_2', 96, 3, 1, 1), _c('branch3x3dbl_3', 96, 3, 1, 1)], [_AVG, _c('branch_pool', pf)]]
+
+
+def _inc_b():
+    return [[_c('branch3x3', 384, 3, 2)], [_c('branch3x3dbl_1', 64), _c('branch3x3dbl_2', 96, 3, 1, 1), _c('branch3x3dbl_3', 96, 3, 2)], [_MAX2]]
+
+
+def _inc_c(c7):
+    return [[_c('branch1x1', 192)],
+            [_c('branch7x7_1', c7), _c('branch7x7_2', c7, (1, 7), 1, (0, 3)), _c('branch7x7_3', 192, (7, 1), 1, (3, 0))],
+            [_c('branch7x7dbl_1', c7), _c('branch7x7dbl_2', c7, (7, 1), 1, (3, 0)), _c('branch7x7dbl_3', c7, (1, 7), 1, (0, 3)),
+             _c('branch7x7dbl_4', c7, (7, 1), 1, (3, 0)), _c('branch7x7dbl_5', 192, (1, 7), 1, (0, 3))],
+            [_AVG, _c('branch_pool', 192)]]
+
+
+def _inc_d():
+    return [[_c('branch3x3_1', 192), _c('branch3x3_2', 320, 3, 2)],
+            [_c('branch7x7x3_1', 192), _c('branch7x7x3_2', 192, (1, 7), 1, (0, 3)), _c('branch7x7x3_3', 192, (7, 1), 1, (3, 0)),
+             _c('branch7x7x3_4', 192, 3, 2)], [_MAX2]]
+
+
+def _inc_e(pool):
+    return [[_c('branch1x1', 320)],
+            [_c('branch3x3_1', 384), _fork([_c('branch3x3_2a', 384, (1, 3), 1, (0, 1))], [_c('branch3x3_2b', 384, (3, 1), 1, (1, 0))])],
+            [_c('branch3x3dbl_1', 448), _c('branch3x3dbl_2', 384, 3, 1, 1),
+             _fork([_c('branch3x3dbl_3a', 384, (1, 3), 1, (0, 1))], [_c('branch3x3dbl_3b', 384, (3, 1), 1, (1, 0))])],
+            [pool, _c('branch_pool', 192)]]
+
+
+# the four blocks of inception.py:89-129: (torchvision name or None, op | list of branches)
+_INCEPTION = (
+    (('Conv2d_1a_3x3', _c(None, 32, 3, 2)), ('Conv2d_2a_3x3', _c(None, 32, 3)), ('Conv2d_2b_3x3', _c(None, 64, 3, 1, 1)), (None, _MAX2)),
+    (('Conv2d_3b_1x1', _c(None, 80)), ('Conv2d_4a_3x3', _c(None, 192, 3)), (None, _MAX2)),
+    (('Mixed_5b', _inc_a(32)), ('Mixed_5c', _inc_a(64)), ('Mixed_5d', _inc_a(64)), ('Mixed_6a', _inc_b()), ('Mixed_6b', _inc_c(128)),
+     ('Mixed_6c', _inc_c(160)), ('Mixed_6d', _inc_c(160)), ('Mixed_6e', _inc_c(192))),
+    (('Mixed_7a', _inc_d()), ('Mixed_7b', _inc_e(_AVG)), ('Mixed_7c', _inc_e(_MAX1)), (None, _GAP)),
+)
+
+
+def _out_hw(h, w, k, s, p):
+    return (h + 2 * p[0] - k[0]) // s + 1, (w + 2 * p[1] - k[1]) // s + 1
+
+
+class _BasicConv2d(_HipModule):
+    """torchvision's BasicConv2d: conv without bias, BatchNorm(eps=0.001), ReLU -- one ``lama_conv2d_rect_fwd`` launch (scale folded into the
+    packed weights, shift = the epilogue's bias)."""
+
+    def __init__(self, cin, cout, k, s, p):
+        super().__init__()
+        self.conv = nn.Conv2d(cin, cout, kernel_size=k, stride=s, padding=p, bias=False)
+        self.bn = nn.BatchNorm2d(cout, eps=0.001)
+
+    def pack(self):
+        if self._packed is None or self._packed['key'] != self.precision:
+            scale, shift = _bn_fold(self.bn)
+            self._packed = dict(key=self.precision, b=shift.contiguous(),
+                                w=self._exec.lib.pack_conv_rect_weight(self.conv.weight.detach(), scale, self.precision))
+        return self._packed
+
+    def run(self, x: L.Tensor4, y: L.Tensor4, batch: int, stream: int):
+        pk, ex = self.pack(), self._exec
+        flag = ex._cur_flag if self.precision == L.PREC_F16X3 else None
+        k, p = self.conv.kernel_size, self.conv.padding
+        ex.lib.conv2d_rect(x, pk['w'], y, batch, k[0], k[1], self.conv.stride[0], p[0], p[1], bias=pk['b'], act=L.ACT_RELU,
+                           precision=self.precision, stream=stream, range_flag=flag)
+
+
+class _Mixed(nn.Module):
+    """Parameter container of one Inception block: its BasicConv2d children under torchvision's names."""
+
+
+def _mixed_module(spec, cin):
+    """(module, output channels) of a block spec fed ``cin`` channels."""
+    m, total = _Mixed(), 0
+
+    def walk(ops, c):
+        nonlocal total
+        for op in ops:
+            if op[0] == 'fork':
+                for br in op[1]:
+                    walk(br, c)
+                return
+            if op[0] == 'conv':
+                m.add_module(op[1], _BasicConv2d(c, op[2], op[3], op[4], op[5]))
+                c = op[2]
+        total += c
+
+    for br in spec:
+        walk(br, cin)
+    return m, total
+
+
+class InceptionV3(_HipModule):
+    """inception.py:21-168.  ``forward(inp) -> [features]`` for images [N,3,H,W] in [0, 1]; ``pair(pred, target)`` runs both as one batch and
+    returns the two halves of the last requested block's output (what ``FIDScore`` calls).  ``weights``: the FID Inception state dict or a path to
+    it (torchvision keys -- ``pt_inception-2015-12-05-6726825d.pth`` -- or this module's own ``blocks.K.J.*``); nothing is downloaded.  Only
+    ``use_fid_inception=True`` and ``normalize_input=True`` are served."""
+
+    DEFAULT_BLOCK_INDEX = 3
+    BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}
+
+    def __init__(self, output_blocks=(DEFAULT_BLOCK_INDEX,), resize_input=True, normalize_input=True, requires_grad=False, use_fid_inception=True,
+                 weights=None):
+        super().__init__()
+        if not use_fid_inception:
+            raise NotImplementedError("InceptionV3 on the HIP path serves use_fid_inception=True only (torchvision's own Inception-v3 differs in "
+                                      'its pools and weights and is not what FID is defined on)')
+        if not normalize_input:
+            raise NotImplementedError('InceptionV3 on the HIP path: normalize_input=False is not served (the 2x - 1 runs inside the input launch)')
+        if requires_grad:
+            raise NotImplementedError('InceptionV3 on the HIP path is inference-only')
+        self.resize_input, self.normalize_input = resize_input, normalize_input
+        self.output_blocks = sorted(output_blocks)
+        self.last_needed_block = max(output_blocks)
+        assert self.last_needed_block <= 3, 'Last possible output block index is 3'
+        self.blocks = nn.ModuleList()
+        self._names = {}                                     # torchvision name -> 'blocks.K.J'
+        cin = 3
+        for bi, block in enumerate(_INCEPTION[:self.last_needed_block + 1]):
+            mods = []
+            for j, (name, spec) in enumerate(block):
+                if isinstance(spec, list):
+                    m, cin = _mixed_module(spec, cin)
+                elif spec[0] == 'conv':
+                    m, cin = _BasicConv2d(cin, spec[2], spec[3], spec[4], spec[5]), spec[2]
+                elif spec[0] == 'pool':
+                    m = nn.MaxPool2d(kernel_size=3, stride=2)
+                else:
+                    m = nn.AdaptiveAvgPool2d(output_size=(1, 1))
+                if name is not None:
+                    self._names[name] = f'blocks.{bi}.{j}'
+                mods.append(m)
+            self.blocks.append(nn.Sequential(*mods))
+        for p in self.parameters():
+            p.requires_grad = False
+        self.use_graph = False            # capture the launch sequence of a shape into a hipGraph and replay it (inputs are then copied into static buffers)
+        self.auto_fallback = True         # an activation beyond the fp16 split's range: repeat with the 3-term bf16 split and stay on it
+        self.max_plans = 4
+        self._plans = collections.OrderedDict()
+        self._load(weights)
+        nn.Module.train(self, False)
+
+    # -- weights ---------------------------------------------------------------------------------
+    def _load(self, weights):
+        if weights is None:
+            raise LamaError("FID: no Inception weights: pass weights= the FID Inception state dict or a path to it (torchvision keys, the format of "
+                            "'pt_inception-2015-12-05-6726825d.pth', or 'blocks.K.J.*'); nothing is downloaded")
+        if not isinstance(weights, dict):
+            path = os.fspath(weights)
+            if not os.path.exists(path):
+                raise LamaError(f'FID: weights file {path!r} not found (lama_amd downloads nothing)')
+            weights = torch.load(path, map_location='cpu', weights_only=True)
+            if not isinstance(weights, dict):
+                raise LamaError(f'FID: {path!r} does not hold a state dict')
+        own = {}
+        for k, v in weights.items():
+            head, _, rest = k.partition('.')
+            if head == 'blocks':
+                own[k] = v
+            elif head in self._names:
+                own[f'{self._names[head]}.{rest}'] = v
+            # fc.*, AuxLogits.* and blocks past the last needed one: not part of the feature extractor
+        mine = nn.Module.state_dict(self)
+        want = {k for k in mine if not k.endswith('num_batches_tracked')}
+        own = {k: v for k, v in own.items() if k in mine}
+        missing = sorted(want - set(own))
+        bad = sorted(k for k, v in own.items() if tuple(v.shape) != tuple(mine[k].shape))
+        if missing or bad:
+            raise LamaError(f'FID: the Inception state dict lacks {missing[:4]}{" ..." if len(missing) > 4 else ""} ({len(missing)} tensors) / has '
+                            f'wrongly shaped {[(k, tuple(own[k].shape), tuple(mine[k].shape)) for k in bad[:4]]} ({len(bad)}): expected '
+                            "torchvision's Inception3 keys ('Conv2d_1a_3x3.conv.weight', 'Mixed_6c.branch7x7dbl_3.bn.running_var', ...) or 'blocks.K.J.*'")
+        nn.Module.load_state_dict(self, own, strict=False)
+        self._invalidate()
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise NotImplementedError('lama_amd.evaluation InceptionV3 is inference-only')
+        return nn.Module.train(self, False)
+
+    def _invalidate(self):
+        super()._invalidate()
+        self._plans = collections.OrderedDict()
+
+    # -- execution -------------------------------------------------------------------------------
+    def _build_plan(self, shape, device) -> dict:
+        """``shape``: (B, 3, H, W) of ONE of the two inputs; every buffer holds 2B images."""
+        B, _, H, W = shape
+        n = 2 * B
+        h, w = (299, 299) if self.resize_input else (H, W)
+        bufs, steps, outs = {}, [], {}
+
+        def new(name, C, hh, ww):
+            if hh < 1 or ww < 1:
+                raise LamaError(f'InceptionV3: a {H} x {W} input is too small for the network (layer {name} would be {hh} x {ww})')
+            bufs[name] = torch.empty((n, C, hh, ww), device=device, dtype=torch.float32)
+            return name
+
+        new('x', 3, h, w)
+        cur = ('x', 0, 3)                                                # (buffer, first channel, channels)
+
+        def op_out(op, C, hh, ww):
+            if op[0] == 'conv':
+                return (op[2],) + _out_hw(hh, ww, op[3], op[4], op[5])
+            return (C,) + _out_hw(hh, ww, (3, 3), op[2], (op[3], op[3]))
+
+        def emit(op, mod, src, dst):
+            steps.append(('conv', mod, src, dst) if op[0] == 'conv' else ('pool', op[1], op[2], op[3], src, dst))
+
+        for bi, block in enumerate(_INCEPTION[:self.last_needed_block + 1]):
+            for j, (name, spec) in enumerate(block):
+                mod, tag = self.blocks[bi][j], f'{bi}.{j}'
+                if not isinstance(spec, list):
+                    if spec[0] == 'gap':
+                        bufs[tag] = torch.empty((n, cur[2]), device=device, dtype=torch.float32)
+                        steps.append(('gap', cur, tag))
+                        cur, h, w = (tag, 0, cur[2]), 1, 1
+                        continue
+                    C, ho, wo = op_out(spec, cur[2], h, w)
+                    dst = (new(tag, C, ho, wo), 0, C)
+                    emit(spec, mod, cur, dst)
+                    cur, h, w = dst, ho, wo
+                    continue
+                # a Mixed block: every branch ends in a channel slice of the block's concatenation buffer
+                leaves = []
+
+                def shape_walk(ops, C, hh, ww):
+                    for op in ops:
+                        if op[0] == 'fork':
+                            for br in op[1]:
+                                shape_walk(br, C, hh, ww)
+                            return
+                        C, hh, ww = op_out(op, C, hh, ww)
+                    leaves.append((C, hh, ww))
+
+                for br in spec:
+                    shape_walk(br, cur[2], h, w)
+                ho, wo = leaves[0][1:]
+                assert all(l[1:] == (ho, wo) for l in leaves)
+                cat = new(tag, sum(l[0] for l in leaves), ho, wo)
+                c_off, tmp = [0], [0]
+
+                def walk(ops, src, hh, ww):
+                    for i, op in enumerate(ops):
+                        if op[0] == 'fork':
+                            for br in op[1]:
+                                walk(br, src, hh, ww)
+                            return
+                        C, h2, w2 = op_out(op, src[2], hh, ww)
+                        if i == len(ops) - 1:
+                            dst = (cat, c_off[0], C)
+                            c_off[0] += C
+                        else:
+                            tmp[0] += 1
+                            dst = (new(f'{tag}.t{tmp[0]}', C, h2, w2), 0, C)
+                        emit(op, getattr(mod, op[1]) if op[0] == 'conv' else None, src, dst)
+                        src, hh, ww = dst, h2, w2
+
+                for br in spec:
+                    walk(br, cur, h, w)
+                cur, h, w = (cat, 0, bufs[cat].shape[1]), ho, wo
+            outs[bi] = cur[0]
+        return dict(bufs=bufs, steps=steps, outs=outs, B=B, graph=None, static=None)
+
+    def conv_paths(self, shape, device):
+        """The entry every conv of the plan of this input shape takes (tests, tools): all 94 run on ``lama_conv2d_rect_fwd``."""
+        return ['rect' for st in self._plan_for(shape, torch.device(device))['steps'] if st[0] == 'conv']
+
+    def _plan_for(self, shape, device) -> dict:
+        key = (tuple(int(v) for v in shape), _Exec._dev_key(device), self.precision)
+        plan = self._plans.get(key)
+        if plan is None:
+            while len(self._plans) >= max(1, self.max_plans):
+                self._plans.popitem(last=False)
+            plan = self._plans[key] = self._build_plan(shape, device)
+        else:
+            self._plans.move_to_end(key)
+        return plan
+
+    def _run_plan(self, plan, a: torch.Tensor, b: torch.Tensor):
+        ex, lib, bufs, n = self._exec, self._exec.lib, plan['bufs'], 2 * plan['B']
+        st = ex.stream(a)
+        lib.fid_input(L.view(a), L.view(b), L.view(bufs['x']), plan['B'], resize=self.resize_input, stream=st)
+
+        def v(ref):
+            return L.view(bufs[ref[0]], ref[1], ref[2])
+
+        for step in plan['steps']:
+            if step[0] == 'conv':
+                step[1].run(v(step[2]), v(step[3]), n, st)
+            elif step[0] == 'pool':
+                lib.pool3x3(v(step[4]), v(step[5]), n, step[1], step[2], step[3], stream=st)
+            else:
+                lib.global_avgpool(v(step[1]), bufs[step[2]], n, stream=st)
+
+    def _launch(self, a: torch.Tensor, b: torch.Tensor) -> dict:
+        plan = self._plan_for(a.shape, a.device)
+        if not (self.use_graph and a.is_cuda):
+            self._run_plan(plan, a, b)
+            return plan
+        if plan['graph'] is None:
+            s0, s1 = torch.empty_like(a), torch.empty_like(b)
+            s0.copy_(a)
+            s1.copy_(b)
+            side = torch.cuda.Stream(device=a.device)
+            side.wait_stream(torch.cuda.current_stream(a.device))
+            with torch.cuda.stream(side):                # warm-up outside capture: packs the weights
+                self._run_plan(plan, s0, s1)
+            torch.cuda.current_stream(a.device).wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._run_plan(plan, s0, s1)
+            plan['graph'], plan['static'] = g, (s0, s1)
+        plan['static'][0].copy_(a)
+        plan['static'][1].copy_(b)
+        plan['graph'].replay()
+        return plan
+
+    def _check(self, a: torch.Tensor, b: torch.Tensor):
+        for t in (a, b):
+            if not self._exec.injected and not t.is_cuda:
+                raise LamaError('InceptionV3 runs on the GPU: move the images to the device (there is no CPU path)')
+        if a.dim() != 4 or a.shape != b.shape or a.shape[1] != 3 or a.shape[0] < 1:
+            raise LamaError(f'InceptionV3: [N,3,H,W] batches of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}')
+        dev = next(self.parameters()).device
+        if dev != a.device and not self._exec.injected:
+            raise LamaError(f'InceptionV3: the weights are on {dev}, the images on {a.device}: move the module (.to(device))')
+
+    def _blocks_of(self, a: torch.Tensor, b: torch.Tensor) -> list:
+        """The requested blocks' outputs for the 2B images (a, then b), cloned out of the plan's buffers."""
+        self._check(a, b)
+        a, b = a.contiguous().float(), b.contiguous().float()
+        try:
+            with self._exec.range_scope(a, self.precision):
+                plan = self._launch(a, b)
+                outs = [plan['bufs'][plan['outs'][i]].clone() for i in self.output_blocks]
+        except LamaRangeError as e:
+            if not (self.auto_fallback and self.precision == L.PREC_F16X3):
+                raise
+            warnings.warn(f'lama_amd: {e}; switching the FID Inception to the 3-term bf16 split (PREC_BF16X3)')
+            self.set_precision(L.PREC_BF16X3)
+            return self._blocks_of(a, b)
+        return [o.view(o.shape[0], o.shape[1], 1, 1) if o.dim() == 2 else o for o in outs]
+
+    def pair(self, pred: torch.Tensor, target: torch.Tensor):
+        """(features of pred, features of target) of the LAST requested block, both from one pass over 2N images."""
+        out = self._blocks_of(pred, target)[-1]
+        n = pred.shape[0]
+        return out[:n], out[n:]
+
+    def forward(self, inp: torch.Tensor):
+        n = inp.shape[0]
+        if n % 2 == 0 and n > 0:                           # the plan's two inputs: the two halves of the batch
+            outs = self._blocks_of(inp[:n // 2], inp[n // 2:])
+        else:
+            outs = [o[:n] for o in self._blocks_of(inp, inp)]
+        return outs
+
+
+# ----------------------------------------------------------------------------------------------------
+# losses/base_loss.py: fid_calculate_activation_statistics, calculate_frechet_distance, FIDScore
+# ----------------------------------------------------------------------------------------------------
+
+def fid_calculate_activation_statistics(act):
+    """base_loss.py:121-124, in the dtypes numpy gives the reference: the mean of fp32 activations is fp32, their covariance fp64."""
+    return np.mean(act, axis=0), np.cov(act, rowvar=False)
+
+
+def _psd_eigenvalues(lam: np.ndarray) -> np.ndarray:
+    """Eigenvalues of a positive semi-definite matrix as ``eigh`` returns them, with its noise cut: ``eigh`` is accurate to eps x lambda_max
+    ABSOLUTELY, so everything below D eps lambda_max (numpy's ``matrix_rank`` threshold) is indistinguishable from 0.  Without the cut the
+    D - N null eigenvalues of a rank-deficient covariance (N images, D = 2048) each add sqrt(noise) to the trace below: 1e-6 relative for an
+    identical pair, whose FID is 0."""
+    top = lam.max(initial=0.0)
+    return np.where(lam > lam.size * np.finfo(np.float64).eps * top, lam, 0.0)
+
+
+def _psd_sqrt(sigma: np.ndarray) -> np.ndarray:
+    lam, vec = np.linalg.eigh(sigma)
+    return (vec * np.sqrt(_psd_eigenvalues(lam))) @ vec.T
+
+
+def calculate_frechet_distance(activations_pred, activations_target, eps=1e-6):
+    """base_loss.py:127-153: |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2).  The reference takes scipy's ``sqrtm`` of the (non-symmetric)
+    product; S1 S2 is similar to the symmetric positive semi-definite S1^1/2 S2 S1^1/2, so tr sqrt(S1 S2) = sum_i sqrt(max(lambda_i, 0)) over
+    that matrix's eigenvalues: two ``eigh`` in fp64, numpy only.  Nothing can come out non-finite or complex, so ``eps`` (the reference's
+    diagonal offset for a singular product) is accepted and not needed."""
+    mu1, sigma1 = fid_calculate_activation_statistics(activations_pred)
+    mu2, sigma2 = fid_calculate_activation_statistics(activations_target)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    diff = mu1 - mu2
+    root1 = _psd_sqrt(sigma1)
+    mid = root1 @ sigma2 @ root1
+    lam = _psd_eigenvalues(np.linalg.eigvalsh((mid + mid.T) * 0.5))
+    tr_covmean = np.sqrt(lam).sum()
+    return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * tr_covmean
+
+
+class FIDScore(nn.Module):
+    """The reference's FIDScore: ``forward`` appends the two [N, dims] activation batches (on the CPU) to ``activations_pred`` /
+    ``activations_target`` and returns them; ``get_value(groups, states)`` -> ({'mean': FID}, {label: {'mean': FID of the group}} or None) and
+    resets.  A group of one element has no covariance: nan.  ``weights``: see ``InceptionV3`` (one network per score; nothing is downloaded)."""
+
+    def __init__(self, dims=2048, eps=1e-6, weights=None):
+        super().__init__()
+        self.model = InceptionV3([InceptionV3.BLOCK_INDEX_BY_DIM[dims]], weights=weights).eval()
+        self.eps = eps
+        self.reset()
+
+    def activations(self, pred_batch, target_batch):
+        """The two [N, dims] activation batches on the device (the device loop keeps them there until a bucket is done)."""
+        ap, at = self.model.pair(pred_batch, target_batch)
+        if ap.shape[2] != 1 or ap.shape[3] != 1:
+            ap, at = ap.mean(dim=(2, 3), keepdim=True), at.mean(dim=(2, 3), keepdim=True)
+        return ap.flatten(1), at.flatten(1)
+
+    def forward(self, pred_batch, target_batch, mask=None):
+        ap, at = self.activations(pred_batch, target_batch)
+        self.activations_pred.append(ap.detach().cpu())
+        self.activations_target.append(at.detach().cpu())
+        return ap, at
+
+    def get_value(self, groups=None, states=None):
+        ap, at = zip(*states) if states is not None else (self.activations_pred, self.activations_target)
+        ap, at = torch.cat(list(ap)).cpu().numpy(), torch.cat(list(at)).cpu().numpy()
+        total = dict(mean=calculate_frechet_distance(ap, at, eps=self.eps))
+        per_group = None
+        if groups is not None:
+            per_group = {}
+            for label, index in get_groupings(groups).items():
+                per_group[label] = dict(mean=calculate_frechet_distance(ap[index], at[index], eps=self.eps) if len(index) > 1 else float('nan'))
+        self.reset()
+        return total, per_group
+
+    def reset(self):
+        self.activations_pred = []
+        self.activations_target = []
+
+
+# ----------------------------------------------------------------------------------------------------
 # evaluation/evaluator.py, evaluation/__init__.py, evaluation/data.py: the bookkeeping around the scores
 # ----------------------------------------------------------------------------------------------------
 
@@ -580,16 +1052,22 @@ class InpaintingEvaluator:
 
 
 def _fid_absent(what: str):
-    return NotImplementedError(f'{what}: FID is not served on the HIP path (it needs a pretrained Inception-v3, whose definition and weights '
-                               'lama_amd neither ships nor downloads); use ssim / lpips, or the reference evaluator for the FID column')
+    return NotImplementedError(f'{what}: FID needs the pretrained FID Inception-v3 weights, which lama_amd neither ships nor downloads: pass '
+                               "fid_kwargs=dict(weights=<state dict or path to pt_inception-2015-12-05-6726825d.pth>), or score ssim / lpips only")
+
+
+def _fid_rel(metrics, fid_scale):
+    return max(0, fid_scale - metrics[('fid', 'total')]['mean']) / fid_scale
 
 
 def ssim_fid100_f1(metrics, fid_scale=100):          # evaluator.py:112-117
-    raise _fid_absent('ssim_fid100_f1')
+    ssim, fid_rel = metrics[('ssim', 'total')]['mean'], _fid_rel(metrics, fid_scale)
+    return 2 * ssim * fid_rel / (ssim + fid_rel + 1e-3)
 
 
 def lpips_fid100_f1(metrics, fid_scale=100):         # evaluator.py:120-125
-    raise _fid_absent('lpips_fid100_f1')
+    neg_lpips, fid_rel = 1 - metrics[('lpips', 'total')]['mean'], _fid_rel(metrics, fid_scale)       # inverted, so bigger is better
+    return 2 * neg_lpips * fid_rel / (neg_lpips + fid_rel + 1e-3)
 
 
 class InpaintingEvaluatorOnline(nn.Module):
@@ -643,22 +1121,29 @@ class InpaintingEvaluatorOnline(nn.Module):
 
 
 def make_evaluator(kind='default', ssim=True, lpips=True, fid=False, integral_kind=None, **kwargs):
-    """evaluation/__init__.py:9-33 without FID (``fid`` defaults to False here; True raises, as does an integral kind built on FID).
-    ``lpips_kwargs`` = dict(model_path=..., backbone=...) reaches ``LPIPSScore`` (nothing is downloaded)."""
+    """evaluation/__init__.py:9-33.  ``fid`` defaults to False here, because FID needs weights the caller must supply:
+    ``fid_kwargs`` = dict(weights=...) reaches ``FIDScore``, ``lpips_kwargs`` = dict(model_path=..., backbone=...) ``LPIPSScore`` (nothing is
+    downloaded).  ``fid=True`` without weights, or an integral kind (both are built on FID) while ``fid`` is off, raises NotImplementedError."""
     lpips_kwargs = kwargs.pop('lpips_kwargs', None) or {}
-    if fid:
+    fid_kwargs = kwargs.pop('fid_kwargs', None) or {}
+    if fid and fid_kwargs.get('weights') is None:
         raise _fid_absent('make_evaluator(fid=True)')
+    integral_func = None
     if integral_kind is not None:
         if integral_kind not in ('ssim_fid100_f1', 'lpips_fid100_f1'):
             raise ValueError(f'Unexpected integral_kind={integral_kind}')
-        raise _fid_absent(f'make_evaluator(integral_kind={integral_kind!r})')
+        if not fid:
+            raise _fid_absent(f'make_evaluator(integral_kind={integral_kind!r}) with fid off')
+        integral_func = ssim_fid100_f1 if integral_kind == 'ssim_fid100_f1' else lpips_fid100_f1
     metrics = {}
     if ssim:
         metrics['ssim'] = SSIMScore()
     if lpips:
         metrics['lpips'] = LPIPSScore(**lpips_kwargs)
+    if fid:
+        metrics['fid'] = FIDScore(**fid_kwargs)
     if kind == 'default':
-        return InpaintingEvaluatorOnline(scores=metrics, integral_func=None, integral_title=integral_kind, **kwargs)
+        return InpaintingEvaluatorOnline(scores=metrics, integral_func=integral_func, integral_title=integral_kind, **kwargs)
 
 
 class PrecomputedInpaintingResultsDataset:
