@@ -306,6 +306,43 @@ int lama_eval_ingest_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_
                             int32_t Ws, int32_t pad_mod, int32_t clamp, float clamp_lo, float clamp_hi, const lama_tensor* out_image,
                             const lama_tensor* out_pred, int64_t* mask_sum, int32_t batch);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) the sparse tail of the predict step ------------------------
+ * The predict step keeps inpainted = mask * pred + (1 - mask) * image (trainers/default.py:71; bin/predict.py writes nothing else): wherever the mask
+ * is 0 the generator's output is multiplied by zero.  The bottleneck sees every pixel through its FFTs; the ConvTranspose2d upsamplings and the 7x7
+ * head behind it (ffc.py:348-363) have receptive fields of 1 and 3 pixels, so their persistent kernels can walk only the work units the output needs.
+ *
+ * lama_tail_lists_build: two launches, no host synchronisation, hipGraph-capturable.  mask = the [batch, 1, H, W] fp32 view of channel 3 of the
+ *   generator's input (what lama_mask_compose_fwd / lama_mask_compose_u8_fwd wrote there); a pixel is needed where it is not 0.  Units:
+ *     head   segment g = part * (batch * ceil(W / 26)) + b * ceil(W / 26) + column: rows part * head_rs .., 26 columns (head_rs: a multiple of 8);
+ *     up[i]  (i = 0 feeds the head, i = 1 feeds up[0], ...; input plane H / 2^(i+1) x W / 2^(i+1), H and W divisible by 2^n_up): tile
+ *            t = ((b * ceil(h / 4) + ty) * ceil(w / 32) + tx) * up_mg[i] + mg: 4 x 32 input pixels (8 x 64 output pixels) x 64 output channels.
+ *   A head segment is listed iff a needed pixel lies in its rectangle; an up[0] tile iff its output rectangle meets the rectangle of a listed head
+ *   segment grown by 3 and clamped to the plane; an up[i] tile iff its output rectangle meets the 5 x 33 input patch (clamped to the plane) of a
+ *   listed up[i - 1] tile -- closure at the granularity of what is COMPUTED.  The list variants keep every load inside those rectangles, the lanes
+ *   and rows of ragged last segments / parts / tiles that feed no stored pixel included (the head clamps them into its grown rectangle; the
+ *   transposed conv reads zeros beyond the plane), so no listed unit reads -- or range-watches -- a pixel that this step did not write.  Every list
+ *   is in ascending order (a prefix sum, no atomic append) and bit-identical run to run; *_count is one int32; *_list has room for every unit of its
+ *   launch.  workspace: lama_tail_lists_workspace_bytes() bytes (0: bad geometry), 4-byte aligned.
+ * lama_conv2d_list_fwd: lama_conv2d_fwd of a ConvTranspose2d(k3,s2,p1,op1) or of the 7x7 reflect head over such a list: the same grid, every
+ *   workgroup walks list[0 .. *count) instead of every unit; units that are not listed are NOT written.  Only where the dedicated persistent kernels
+ *   run (LAMA_PREC_F16X3 / BF16X3, fp32 tensors, the shapes they take); anything else returns LAMA_ERR_UNSUPPORTED with nothing launched and the caller
+ *   runs lama_conv2d_fwd -- a superset.  head_rs: rows per head segment (as given to lama_tail_lists_build; ignored by the transposed conv).
+ * lama_conv2d_list_supported: 1 when lama_conv2d_list_fwd takes these arguments (every check, no launch).
+ * lama_blend_quantize_u8_fwd does not read pred where the mask is 0. */
+typedef struct lama_tail_lists {
+    int32_t n_up;    /* ConvTranspose2d launches listed, 0 .. 4 */
+    int32_t head_rs; /* rows per head segment, a multiple of 8 */
+    int32_t up_mg[4]; /* Cout / 64 of up[i] */
+    int32_t* head_list;
+    int32_t* head_count;
+    int32_t* up_list[4];
+    int32_t* up_count[4];
+} lama_tail_lists;
+size_t lama_tail_lists_workspace_bytes(int32_t batch, int32_t H, int32_t W, const lama_tail_lists* lists);
+int lama_tail_lists_build(void* stream, const lama_tensor* mask, int32_t batch, const lama_tail_lists* lists, void* workspace, size_t workspace_bytes);
+int lama_conv2d_list_fwd(void* stream, const lama_conv2d_args* args, const int32_t* list, const int32_t* count, int32_t head_rs);
+int32_t lama_conv2d_list_supported(const lama_conv2d_args* args, int32_t head_rs);
+
 /* Stand-alone per-channel affine + activation: y = act(x*scale[c] + shift[c]) (scale/shift NULL = identity).
  * Used when a caller runs generator.model layer by layer and hits a bare nn.BatchNorm2d (eval) /
  * nn.ReLU / nn.Sigmoid (ffc.py:352-354,362-363); the fused forward never launches it. */

@@ -65,6 +65,12 @@ class Conv2dRectArgs(C.Structure):
                 ('precision', C.c_int32), ('range_flag', C.c_void_p)]
 
 
+class TailLists(C.Structure):
+    """struct lama_tail_lists"""
+    _fields_ = [('n_up', C.c_int32), ('head_rs', C.c_int32), ('up_mg', C.c_int32 * 4), ('head_list', C.c_void_p), ('head_count', C.c_void_p),
+                ('up_list', C.c_void_p * 4), ('up_count', C.c_void_p * 4)]
+
+
 def view(t: Optional[torch.Tensor], c0: int = 0, c: Optional[int] = None) -> Tensor4:
     """lama_tensor view of channels [c0, c0+c) of a contiguous fp32 / fp16 NCHW tensor (None -> absent)."""
     if t is None:
@@ -100,6 +106,10 @@ class LamaLib:
         L.lama_conv2d_pack_weight.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
         L.lama_conv2d_fwd.restype = C.c_int
         L.lama_conv2d_fwd.argtypes = [vp, C.POINTER(Conv2dArgs)]
+        L.lama_conv2d_list_fwd.restype, L.lama_conv2d_list_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dArgs), vp, vp, i32]
+        L.lama_conv2d_list_supported.restype, L.lama_conv2d_list_supported.argtypes = i32, [C.POINTER(Conv2dArgs), i32]
+        L.lama_tail_lists_workspace_bytes.restype, L.lama_tail_lists_workspace_bytes.argtypes = sz, [i32, i32, i32, C.POINTER(TailLists)]
+        L.lama_tail_lists_build.restype, L.lama_tail_lists_build.argtypes = C.c_int, [vp, T, i32, C.POINTER(TailLists), vp, sz]
         L.lama_rfft2_fwd.restype = C.c_int
         L.lama_rfft2_fwd.argtypes = [vp, T, T, i32, vp, sz]
         L.lama_irfft2_fwd.restype = C.c_int
@@ -224,10 +234,14 @@ class LamaLib:
                pad_mode: int = PAD_REFLECT, transposed: bool = False, bias: Optional[torch.Tensor] = None,
                act: int = ACT_NONE, resid: Optional[Tensor4] = None, x2: Optional[Tensor4] = None,
                w2_packed: Optional[torch.Tensor] = None, precision: int = PREC_F32, stream: int = 0,
-               range_flag: Optional[torch.Tensor] = None, fuse1: Optional[tuple] = None, cooperative: bool = False, siblings_log2: int = 0):
+               range_flag: Optional[torch.Tensor] = None, fuse1: Optional[tuple] = None, cooperative: bool = False, siblings_log2: int = 0,
+               tile_list: Optional[tuple] = None, query: bool = False):
         """``fuse1`` = (packed conv1 weights with the channel order of fuse1_channel_order(), BatchNorm shift [192], x1 view): the NEXT
         layer's SpectralTransform.conv1 in the epilogue of this (global-branch) launch -- lama_conv2d_args.fuse1_*.  ``siblings_log2`` (v109):
-        this launch covers 1 / 2^n of a batch whose other parts run beside it (LAMA_CONV_SIBLINGS_*)."""
+        this launch covers 1 / 2^n of a batch whose other parts run beside it (LAMA_CONV_SIBLINGS_*).  ``tile_list`` = (list, count, head_rs), the
+        int32 tensors of ``tail_lists_alloc``: lama_conv2d_list_fwd, the launch over the listed work units only (LamaError with code ERR_UNSUPPORTED
+        where the dedicated kernels do not take the shape); with ``query`` nothing is launched and the verdict is returned
+        (lama_conv2d_list_supported)."""
         a = Conv2dArgs()
         a.x, a.w_packed = x, w_packed.data_ptr()
         a.kh = a.kw = k
@@ -243,7 +257,46 @@ class LamaLib:
         if fuse1 is not None:
             a.fuse1_w, a.fuse1_bias, a.fuse1_y = fuse1[0].data_ptr(), fuse1[1].data_ptr(), fuse1[2]
         a.flags = (CONV_COOPERATIVE if cooperative else 0) | (int(siblings_log2) << CONV_SIBLINGS_SHIFT)   # lama_conv2d_args.flags
+        if tile_list is not None:
+            lst, cnt, head_rs = tile_list
+            if query:
+                return self._l.lama_conv2d_list_supported(C.byref(a), int(head_rs)) == 1
+            self.check(self._l.lama_conv2d_list_fwd(stream, C.byref(a), lst.data_ptr(), cnt.data_ptr(), int(head_rs)), 'lama_conv2d_list_fwd')
+            return None
         self.check(self._l.lama_conv2d_fwd(stream, C.byref(a)), 'lama_conv2d_fwd')
+
+    # -- work lists of the sparse tail (lama_tail_lists_*) ------------------------------------------------
+    def tail_lists_alloc(self, batch: int, H: int, W: int, head_rs: int, up_mg, device) -> dict:
+        """The plan-owned buffers of lama_tail_lists_build for a [batch, ., H, W] head plane behind len(up_mg) upsamplings (up_mg[0] = Cout / 64 of
+        the one that feeds the head): ``head`` and ``up[i]`` = (int32 list with room for every unit, int32 count [1]), the flag workspace and the
+        argument block.  Zero-filled: an entry is a valid unit index before the first build."""
+        n_up = len(up_mg)
+        if n_up > 4 or H % (1 << n_up) or W % (1 << n_up) or head_rs < 8 or head_rs % 8:
+            raise LamaError(f'tail lists: {n_up} upsamplings of a {H} x {W} plane, head_rs {head_rs}')
+
+        def pair(n):
+            return torch.zeros(n, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+
+        cd = lambda a, b: (a + b - 1) // b
+        head = pair(batch * cd(W, 26) * cd(H, head_rs))
+        up = [pair(batch * cd(H >> (i + 1), 4) * cd(W >> (i + 1), 32) * int(up_mg[i])) for i in range(n_up)]
+        a = TailLists()
+        a.n_up, a.head_rs = n_up, head_rs
+        a.head_list, a.head_count = head[0].data_ptr(), head[1].data_ptr()
+        for i in range(n_up):
+            a.up_mg[i] = int(up_mg[i])
+            a.up_list[i], a.up_count[i] = up[i][0].data_ptr(), up[i][1].data_ptr()
+        nbytes = self._l.lama_tail_lists_workspace_bytes(batch, H, W, C.byref(a))
+        if nbytes <= 0:
+            raise LamaError(f'tail lists: unsupported geometry {batch} x {H} x {W}')
+        ws = torch.zeros(nbytes // 4, dtype=torch.int32, device=device)
+        return dict(head=head, up=up, ws=ws, args=a, head_rs=head_rs, batch=batch, H=H, W=W)
+
+    def tail_lists_build(self, mask: Tensor4, lists: dict, stream: int = 0):
+        """lama_tail_lists_build: ``mask`` = the [batch, 1, H, W] view of channel 3 of the generator's input; fills ``lists`` (tail_lists_alloc)."""
+        ws = lists['ws']
+        self.check(self._l.lama_tail_lists_build(stream, C.byref(mask), lists['batch'], C.byref(lists['args']), ws.data_ptr(), ws.numel() * 4),
+                   'lama_tail_lists_build')
 
     # -- Winograd F(2x2, 3x3) form of the stride-1 3x3 reflect conv (lama_winograd_*) -----------------
     def winograd_supported(self, cout: int, cin: int, H: int, W: int, precision: int) -> bool:

@@ -31,6 +31,8 @@ struct HeadParams {
     int ns, rs;          // vertical parts per column of segments, rows per part (a multiple of HEAD_R = 8)
     int nseg;            // B * tx * ns
     unsigned* range_flag;   // lama_conv2d_args.range_flag (f16 split only; may be null)
+    const int* list;        // LIST instantiation (lama_conv2d_list_fwd): the dense segment indices to walk, in ascending order ...
+    const int* count;       // ... and how many of them (device int, written by lama_tail_lists_build earlier in the same stream)
 };
 
 #define HEAD_ZP 33                                  // floats per z row in LDS (32 columns, padded)
@@ -50,7 +52,9 @@ struct HeadParams {
 
 // HI (f16 back end, LAMA_PREC_F16): the input is fp16 (half of this kernel's HBM traffic, which is all loads): a requested row is 8
 // 16-bit patterns that pack into the four hi dwords without any conversion; one product per MAC.  The output image stays fp32.
-template <bool HI = false>
+// LIST: the workgroups walk the p.count[0] segment indices of p.list (segments that hold a needed output pixel: sparse tail, DESIGN.md 4.17) instead
+// of 0 .. nseg - 1; list order = dense order with holes, so neighbouring entries are still neighbouring columns wherever both are listed.
+template <bool HI = false, bool LIST = false>
 __global__ __launch_bounds__(256, 3) void CB_NAME(head7_ws_kernel)(HeadParams p) {
     constexpr int ESI = HI ? 2 : 4;
     const int tid = threadIdx.x, lane = tid & 63, q = LAMA_WAVE_UNIFORM(tid >> 6);
@@ -80,8 +84,12 @@ __global__ __launch_bounds__(256, 3) void CB_NAME(head7_ws_kernel)(HeadParams p)
     // segment: walked at the same time behind the same L2 it is fetched from HBM once (column-major order put the two on
     // different XCDs: 2.09x the algorithmic traffic, profiles/r02_pmc.json).
     const int ncols = p.B * p.tx;
+    int nseg = p.nseg;
+    if constexpr (LIST) { const int n = p.count[0]; nseg = n < nseg ? (n > 0 ? n : 0) : nseg; }   // (never more entries than the list holds)
 #pragma unroll 1
-    for (int g = lama_xcd_remap(blockIdx.x, gridDim.x); g < p.nseg; g += gridDim.x) {
+    for (int gi = lama_xcd_remap(blockIdx.x, gridDim.x); gi < nseg; gi += gridDim.x) {
+        int g = gi;
+        if constexpr (LIST) { g = p.list[gi]; g = g < 0 ? 0 : (g >= p.nseg ? p.nseg - 1 : g); }   // (an entry is a segment of this plane whatever the buffer holds)
         const int part = g / ncols, col = g - part * ncols;
         const int b = col / p.tx, x0 = (col - b * p.tx) * 26;
         const int y0 = part * p.rs, y1 = (y0 + p.rs < H) ? y0 + p.rs : H;
@@ -92,11 +100,19 @@ __global__ __launch_bounds__(256, 3) void CB_NAME(head7_ws_kernel)(HeadParams p)
         ix = ix < 0 ? -ix : ix;
         ix = ix >= W ? 2 * (W - 1) - ix : ix;
         ix = ix < 0 ? 0 : (ix >= W ? W - 1 : ix);               // columns of a ragged last segment that no stored pixel uses
+        // LIST: what this segment may read is its output rectangle grown by 3 and clamped to the plane -- all the list build closes over.  The
+        // columns / rows that stored pixels use lie inside it (reflection included); the lanes of a ragged last segment and the rows of a ragged
+        // last part that feed no stored pixel would reflect out of it (W % 26 in 1..13: columns left of x0 - 3), into tiles nobody wrote, and
+        // what they load passes the range watch: keep them inside.
+        const int rx0 = x0 - 3 < 0 ? 0 : x0 - 3, rx1 = (x0 + 26 < W ? x0 + 26 : W) + 2 < W ? (x0 + 26 < W ? x0 + 26 : W) + 2 : W - 1;
+        const int ry0 = y0 - 3 < 0 ? 0 : y0 - 3, ry1 = y1 + 2 < H ? y1 + 2 : H - 1;
+        if constexpr (LIST) ix = ix < rx0 ? rx0 : (ix > rx1 ? rx1 : ix);
         const int coloff = ((16 * q + 8 * khalf) * HW + ix) * ESI;
         auto row_off = [&](int u) {                             // virtual row u (may be outside the image) -> byte offset of the input row
             int iy = u < 0 ? -u : u;
             iy = iy >= H ? 2 * (H - 1) - iy : iy;
             iy = iy < 0 ? 0 : (iy >= H ? H - 1 : iy);
+            if constexpr (LIST) iy = iy < ry0 ? ry0 : (iy > ry1 ? ry1 : iy);
             return iy * W * ESI;
         };
         // register ring: slot (u - (y0 - 3)) % HEAD_R holds virtual row u of this lane's 8 channels, first as the 8 requested

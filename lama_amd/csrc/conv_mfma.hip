@@ -643,7 +643,7 @@ extern "C" void lama_fuse1_channel_order(int32_t* order) {
             for (int i = 0; i < 8; ++i) order[16 * kq + 8 * kh + i] = 32 * (kq / 2) + 16 * (kq & 1) + 8 * (i / 4) + 4 * kh + (i % 4);
 }
 
-extern "C" int lama_conv2d_fwd(void* stream, const lama_conv2d_args* a) {
+static int conv2d_impl(void* stream, const lama_conv2d_args* a, const LamaTileList* tl) {
     if (!a || !tensor_ok(a->x) || !tensor_ok(a->y) || !a->w_packed || a->batch <= 0) return LAMA_ERR_BAD_ARG;
     if (a->precision != LAMA_PREC_F32 && a->precision != LAMA_PREC_BF16X3 && a->precision != LAMA_PREC_F16X3 && a->precision != LAMA_PREC_F16)
         return LAMA_ERR_UNSUPPORTED;
@@ -677,9 +677,10 @@ extern "C" int lama_conv2d_fwd(void* stream, const lama_conv2d_args* a) {
             (a->precision != LAMA_PREC_BF16X3 && a->precision != LAMA_PREC_F16X3))
             return LAMA_ERR_UNSUPPORTED;
     }
-    if (a->precision == LAMA_PREC_BF16X3) return lama_cb_conv2d_fwd_bf16x3((hipStream_t)stream, a, Ho, Wo);
-    if (a->precision == LAMA_PREC_F16X3) return lama_cb_conv2d_fwd_f16x3((hipStream_t)stream, a, Ho, Wo);
-    if (a->precision == LAMA_PREC_F16) return lama_cb_conv2d_fwd_f16((hipStream_t)stream, a, Ho, Wo);
+    if (a->precision == LAMA_PREC_BF16X3) return lama_cb_conv2d_fwd_bf16x3((hipStream_t)stream, a, Ho, Wo, tl);
+    if (a->precision == LAMA_PREC_F16X3) return lama_cb_conv2d_fwd_f16x3((hipStream_t)stream, a, Ho, Wo, tl);
+    if (a->precision == LAMA_PREC_F16) return lama_cb_conv2d_fwd_f16((hipStream_t)stream, a, Ho, Wo, tl);
+    if (tl) return LAMA_ERR_UNSUPPORTED;   // the work lists are walked by the split-precision tail kernels only
 
     ConvPlan pl2;
     if (has2 && !make_plan(cout, a->x2.C, 1, 1, 1, 0, 0, &pl2)) return LAMA_ERR_UNSUPPORTED;
@@ -732,4 +733,17 @@ extern "C" int lama_conv2d_fwd(void* stream, const lama_conv2d_args* a) {
         if (rc != LAMA_OK) return rc;
     }
     return LAMA_OK;
+}
+
+extern "C" int lama_conv2d_fwd(void* stream, const lama_conv2d_args* a) { return conv2d_impl(stream, a, nullptr); }
+
+// The same convolution over a compacted list of its work units (sparse tail): the dedicated ConvTranspose2d / 7x7 head kernels only
+extern "C" int lama_conv2d_list_fwd(void* stream, const lama_conv2d_args* a, const int32_t* list, const int32_t* count, int32_t head_rs) {
+    if (!list || !count) return LAMA_ERR_BAD_ARG;
+    const LamaTileList tl = {list, count, head_rs, false};
+    return conv2d_impl(stream, a, &tl);
+}
+extern "C" int32_t lama_conv2d_list_supported(const lama_conv2d_args* a, int32_t head_rs) {
+    const LamaTileList tl = {nullptr, nullptr, head_rs, true};
+    return conv2d_impl(nullptr, a, &tl) == LAMA_OK ? 1 : 0;
 }

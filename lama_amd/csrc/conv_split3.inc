@@ -1075,11 +1075,18 @@ int CB_NAME(lama_cb_pack_weight)(hipStream_t stream, const float* w, const float
 }
 
 // arguments were validated by lama_conv2d_fwd (conv_mfma.hip)
-int CB_NAME(lama_cb_conv2d_fwd)(hipStream_t stream, const lama_conv2d_args* a, int Ho, int Wo) {
+// ``tl`` (lama_conv2d_list_fwd): only the two persistent tail kernels walk a work list -- everything else is LAMA_ERR_UNSUPPORTED, nothing launched
+int CB_NAME(lama_cb_conv2d_fwd)(hipStream_t stream, const lama_conv2d_args* a, int Ho, int Wo, const LamaTileList* tl) {
     const int cout = a->y.C, cin = a->x.C;
     CbPlan pl;
     if (!cb_make_plan(cout, cin, a->kh, a->kw, a->stride, a->pad, a->transposed, &pl)) return LAMA_ERR_UNSUPPORTED;
     const bool has2 = a->x2.ptr != nullptr;
+    if (tl) {
+        if (has2 || a->fuse1_w) return LAMA_ERR_UNSUPPORTED;
+        const int io_l = (a->x.dtype == LAMA_DT_F16 ? 1 : 0) | (a->y.dtype == LAMA_DT_F16 ? 2 : 0);
+        if ((io_l != CB_IO_F32) != (CB_HALF != 0)) return LAMA_ERR_UNSUPPORTED;
+        return a->transposed ? ct_try_launch(stream, a, pl, Ho, Wo, io_l, tl) : head_try_launch(stream, a, pl, Ho, Wo, io_l, tl);
+    }
     CbPlan pl2;
     if (has2 && !cb_make_plan(cout, a->x2.C, 1, 1, 1, 0, 0, &pl2)) return LAMA_ERR_UNSUPPORTED;
     if (has2 && pl.mode) return LAMA_ERR_UNSUPPORTED;

@@ -530,9 +530,10 @@ int cw_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& p
 
 // ConvTranspose2d(k3, s2, p1, op1) as ONE launch, all four output-parity classes in one wave (convt2_kernel, convt_dev.inc).  LAMA_CT (profiling
 // build): 0 = off (A/B runs against the fused LDS-staged launch); read per launch.
-int ct_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& pl, int Ho, int Wo, int io) {
+// ``tl`` (lama_conv2d_list_fwd): the LIST instantiation over the caller's tile list, same grid; tl->dry: every check, no launch.
+int ct_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& pl, int Ho, int Wo, int io, const LamaTileList* tl = nullptr) {
 #if CB_HALF
-    (void)stream; (void)a; (void)pl; (void)Ho; (void)Wo; (void)io;
+    (void)stream; (void)a; (void)pl; (void)Ho; (void)Wo; (void)io; (void)tl;
     return LAMA_ERR_UNSUPPORTED;
 #else
     const int mode = lama_env_int("LAMA_CT", 1);
@@ -571,10 +572,15 @@ int ct_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& p
     const long long tiles = (long long)a->batch * p.tiles_x * p.tiles_y * p.MG;
     if (tiles <= 0) return LAMA_OK;
     if (tiles >= (1ll << 30)) return LAMA_ERR_UNSUPPORTED;
+    if (tl && tl->dry) return LAMA_OK;
     { static const int abl = lama_env_int("LAMA_CT_ABLATE", 0); p.abl = abl; }      // profiling tools only
     long long grid = tiles < 512 ? tiles : 512;                                      // persistent: two workgroups per CU walk tiles w, w + grid, ...
     { const int cap = lama_env_int("LAMA_CT_GRID", 0); if (cap > 0 && grid > cap) grid = cap; }   // emulator tests: several tiles per workgroup
-    hipLaunchKernelGGL(CB_NAME(convt2_kernel), dim3((int)grid), dim3(C2_THREADS), C2_LDS_BYTES, stream, p);
+    if (tl) {
+        p.list = tl->list; p.count = tl->count;
+        hipLaunchKernelGGL(CB_NAME(convt2_kernel)<true>, dim3((int)grid), dim3(C2_THREADS), C2_LDS_BYTES, stream, p);
+    } else
+        hipLaunchKernelGGL(CB_NAME(convt2_kernel)<false>, dim3((int)grid), dim3(C2_THREADS), C2_LDS_BYTES, stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 #endif
@@ -631,8 +637,11 @@ int stem_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan&
 
 // Head (7x7, 64 input channels, <= 4 output channels, reflect pad 3): conv_head_dev.inc.  LAMA_HEAD_WS: 0 disables it (A/B runs of
 // the profiling tools), 2 takes it whatever the launch size (emulator tests); read once.
-int head_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& pl, int Ho, int Wo, int io) {
+// ``tl`` (lama_conv2d_list_fwd): the LIST instantiation over the caller's segment list, cut into parts of tl->head_rs rows (the host cannot know
+// the count, so the parts are small and the grid is the resident 768); fp32 tensors only; tl->dry: every check, no launch.
+int head_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& pl, int Ho, int Wo, int io, const LamaTileList* tl = nullptr) {
     if (io != CB_IO_F32 && io != CB_IO_F16_F32) return LAMA_ERR_UNSUPPORTED;
+    if (tl && (io != CB_IO_F32 || tl->head_rs < HEAD_R || tl->head_rs % HEAD_R != 0)) return LAMA_ERR_UNSUPPORTED;
     static const int mode = lama_env_int("LAMA_HEAD_WS", 1);
     if (mode == 0 || pl.mode != 2 || pl.mft != 1 || a->x.C != 64 || a->y.C > 4 || a->transposed || a->stride != 1 || a->pad != 3 ||
         a->pad_mode != LAMA_PAD_REFLECT || a->resid.ptr || a->x.H < 4 || a->x.W < 4)
@@ -668,11 +677,20 @@ int head_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan&
         const double eff = (per <= 1.0 ? per : per / rounds) * rs / (rs + 6.0 + HEAD_D);
         if (eff > best) { best = eff; best_rs = rs; }
     }
-    p.rs = best_rs;
+    p.rs = tl ? tl->head_rs : best_rs;
     p.ns = lama_ceil_div(Ho, p.rs);
     if (cols * p.ns >= (1ll << 31)) return LAMA_ERR_UNSUPPORTED;
     p.nseg = (int)(cols * p.ns);
     const int grid = p.nseg < wgs ? p.nseg : wgs;
+    if (tl && tl->dry) return LAMA_OK;
+#if !CB_HALF
+    if (tl) {
+        p.list = tl->list; p.count = tl->count;
+        hipLaunchKernelGGL((CB_NAME(head7_ws_kernel)<false, true>), dim3(grid), dim3(256), HEAD_LDS_BYTES, stream, p);
+        LAMA_CHECK_LAUNCH();
+        return LAMA_OK;
+    }
+#endif
 #if CB_HALF
     if (io != CB_IO_F16_F32) return LAMA_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(CB_NAME(head7_ws_kernel)<true>, dim3(grid), dim3(256), HEAD_LDS_BYTES, stream, p);

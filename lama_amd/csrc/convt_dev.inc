@@ -27,6 +27,8 @@ struct CtParams {
     int tiles_x, tiles_y, MG;
     unsigned* range_flag;
     int abl;                 // profiling tools only (LAMA_CT_ABLATE, results WRONG): bit 0 = no global stores, bit 1 = no epilogue at all
+    const int* list;         // LIST instantiation (lama_conv2d_list_fwd): the dense tile indices to walk, in ascending order ...
+    const int* count;        // ... and how many of them (device int, written by lama_tail_lists_build earlier in the same stream)
 };
 
 #define CT_PWS 34                                   // LDS row pitch of the 5 x 33 patch (pixels)
@@ -81,6 +83,10 @@ constexpr int c2_tap(int q) { constexpr int t[9] = {3, 1, 1, 0, 1, 0, 2, 0, 0}; 
 constexpr int c2_dy(int q) { constexpr int t[9] = {0, 0, 0, 0, 1, 1, 0, 0, 1}; return t[q]; }
 constexpr int c2_dx(int q) { constexpr int t[9] = {0, 0, 0, 0, 0, 0, 1, 1, 1}; return t[q]; }
 
+// LIST: the workgroup walks entries L0, L0 + G, ... of p.list (p.count[0] of them) instead of every tile of the plane -- the tiles whose output
+// something downstream reads (sparse tail, DESIGN.md 4.17); the grid stays what the dense launch takes and workgroups beyond the count leave at once.
+// A template parameter: the kernel sits at the register limit and the dense instantiation must stay what it was.
+template <bool LIST = false>
 __global__ __launch_bounds__(C2_THREADS, 2) void CB_NAME(convt2_kernel)(CtParams p) {
     static_assert((C2_AR == 3 || C2_AR == 6) && (C2_KG == 1 || C2_KG == 2), "ring slot = compile-time function of (k-group parity, position)");
     constexpr int KG = C2_KG, AR = C2_AR, NU = C2_NU;
@@ -90,11 +96,14 @@ __global__ __launch_bounds__(C2_THREADS, 2) void CB_NAME(convt2_kernel)(CtParams
     const int HW = p.H * p.W;
     char* const smem = lama_smem;
     const int L0 = lama_xcd_remap(blockIdx.x, gridDim.x), G = gridDim.x;
-    const int ntiles = p.B * p.tiles_y * p.tiles_x * p.MG;
+    const int ndense = p.B * p.tiles_y * p.tiles_x * p.MG;
+    int ntiles = ndense;
+    if constexpr (LIST) { const int n = p.count[0]; ntiles = n < ntiles ? (n > 0 ? n : 0) : ntiles; }   // (never more entries than the list holds)
     const int ntl = L0 < ntiles ? (ntiles - L0 + G - 1) / G : 0;     // tiles of this workgroup
     const int ngr = p.C / 16, nch = ngr / KG, nseq = ntl * nch;      // k-groups / staged chunks per tile (Cin % 32 == 0), chunks of this workgroup
     auto tile_of = [&](int tl, int& mg, int& b, int& gy0, int& gx0) {
         int t0 = L0 + tl * G;
+        if constexpr (LIST) { t0 = p.list[t0]; t0 = t0 < 0 ? 0 : (t0 >= ndense ? ndense - 1 : t0); }   // (an entry is a tile of this plane whatever the buffer holds)
         mg = t0 % p.MG;
         t0 /= p.MG;
         const int tx = t0 % p.tiles_x;

@@ -148,10 +148,116 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void blend_quantize_u8_kernel(U8Para
         uint8_t* d = p.out_u8 + i * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float v = ew_blend(m, k, p.pred[b * p.pred_bs + c * hw + px], im[c]) * 255.0f;
+            // pred is not read where the mask is 0 (the sparse tail leaves those pixels of the generator's output unwritten: DESIGN.md 4.17):
+            // fmaf(0, pred, 1 * img) = img for every finite pred -- the same bytes
+            const float pr = m != 0.0f ? p.pred[b * p.pred_bs + c * hw + px] : 0.0f;
+            float v = ew_blend(m, k, pr, im[c]) * 255.0f;
             v = fminf(fmaxf(v, 0.0f), 255.0f);
             d[c] = (uint8_t)v;
         }
+    }
+}
+
+// ---- work lists of the sparse tail (lama_tail_lists_build) --------------------------------------------------------------------
+// The predict step keeps mask * pred + (1 - mask) * image: where the mask is 0 the generator's output is never read, and the last launches of the
+// generator -- the ConvTranspose2d upsamplings (convt2_kernel: tiles of 4 x 32 input pixels x 64 output channels) and the 7x7 head (head7_ws_kernel:
+// segments of rs rows x 26 columns) -- have receptive fields of 1 and 3 pixels.  Two launches list the work units the output needs:
+//   tail_flags_kernel  one 64-thread workgroup per head segment: is any mask pixel of its output rectangle not 0?
+//   tail_lists_kernel  ONE workgroup: the closures -- an up tile is needed when its output rectangle meets what a LISTED unit downstream reads (the
+//     head segment's rectangle grown by 3 and clamped to the plane; the 5 x 33 input patch of an up tile clamped to the plane), i.e. at the
+//     granularity of what is computed: a listed unit never reads a pixel that was not written in this step -- and the ordered compactions (a
+//     prefix sum, no atomic append: the list is the dense order with holes, the same from run to run).
+#define TAIL_MAX_UP 4
+struct TailParams {
+    const float* mask;            // [B][H][W] plane of the generator's input (channel 3), batch stride in elements
+    long long mask_bs;
+    int B, H, W;                  // the head's plane
+    int txh, ns, rs;              // head: 26-column segments per row, parts per column, rows per part
+    int n_up;
+    int uh[TAIL_MAX_UP], uw[TAIL_MAX_UP], mg[TAIL_MAX_UP];   // level i (0 = feeds the head): its INPUT plane, Cout / 64
+    int* head_flags;              // workspace: [ns][B * txh]
+    int* up_flags[TAIL_MAX_UP];   // workspace: [B][tiles_y][tiles_x]
+    int* head_list; int* head_count;
+    int* up_list[TAIL_MAX_UP]; int* up_count[TAIL_MAX_UP];
+};
+
+__global__ __launch_bounds__(64) void tail_flags_kernel(TailParams p) {
+    const int ncols = p.B * p.txh, g = blockIdx.x;
+    const int part = g / ncols, col = g - part * ncols, b = col / p.txh, x0 = (col - b * p.txh) * 26;
+    const int y0 = part * p.rs, y1 = y0 + p.rs < p.H ? y0 + p.rs : p.H, x1 = x0 + 26 < p.W ? x0 + 26 : p.W;
+    const int w = x1 - x0, n = (y1 - y0) * w;
+    const float* m = p.mask + (long long)b * p.mask_bs;
+    bool any = false;
+    for (int i = threadIdx.x; i < n; i += 64) {
+        const int r = i / w, c = i - r * w;
+        any = any || m[(long long)(y0 + r) * p.W + x0 + c] != 0.0f;
+    }
+    if (threadIdx.x == 0) p.head_flags[g] = 0;
+    __syncthreads();
+    if (any) p.head_flags[g] = 1;           // (every writer stores the same value)
+}
+
+// ordered compaction by the whole workgroup: item i of n with flags[i] != 0 becomes the list entries i * mg .. i * mg + mg - 1
+__device__ void tail_compact(const int* flags, int n, int mg, int* list, int* count, int* lds) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int per = (n + nt - 1) / nt;
+    const int i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
+    int c = 0;
+    for (int i = i0; i < i1; ++i) c += flags[i] != 0;
+    lds[tid] = c;
+    __syncthreads();
+    for (int d = 1; d < nt; d <<= 1) {
+        const int v = tid >= d ? lds[tid - d] : 0;
+        __syncthreads();
+        lds[tid] += v;
+        __syncthreads();
+    }
+    int pos = lds[tid] - c;
+    for (int i = i0; i < i1; ++i)
+        if (flags[i] != 0) {
+            for (int m = 0; m < mg; ++m) list[pos * mg + m] = i * mg + m;
+            ++pos;
+        }
+    if (tid == nt - 1) count[0] = lds[tid] * mg;
+    __syncthreads();
+}
+
+#define TAIL_NT 1024   // one workgroup: its time is a chain of memory round trips per thread, so the widest workgroup is the shortest chain
+__global__ __launch_bounds__(TAIL_NT) void tail_lists_kernel(TailParams p) {
+    int* lds = reinterpret_cast<int*>(lama_smem);
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int ncols = p.B * p.txh;
+    tail_compact(p.head_flags, ncols * p.ns, 1, p.head_list, p.head_count, lds);
+    for (int lv = 0; lv < p.n_up; ++lv) {
+        const int ty_n = (p.uh[lv] + 3) / 4, tx_n = (p.uw[lv] + 31) / 32, nsp = p.B * ty_n * tx_n;
+        const int Ho = 2 * p.uh[lv], Wo = 2 * p.uw[lv];
+        for (int t = tid; t < nsp; t += nt) {
+            const int tx = t % tx_n, ty = (t / tx_n) % ty_n, b = t / (tx_n * ty_n);
+            const int y0 = 8 * ty, y1 = y0 + 8 < Ho ? y0 + 8 : Ho, x0 = 64 * tx, x1 = x0 + 64 < Wo ? x0 + 64 : Wo;   // this tile's output rectangle
+            int need = 0;
+            if (lv == 0) {       // read by: the rectangle of a listed head segment grown by the 3-pixel reflection pad, clamped to the plane
+                int pa0 = (y0 - 3) / p.rs - 1, pa1 = (y1 + 3) / p.rs + 1, c0 = (x0 - 3) / 26 - 1, c1 = (x1 + 3) / 26 + 1;
+                pa0 = pa0 < 0 ? 0 : pa0; pa1 = pa1 >= p.ns ? p.ns - 1 : pa1; c0 = c0 < 0 ? 0 : c0; c1 = c1 >= p.txh ? p.txh - 1 : c1;
+                for (int pa = pa0; pa <= pa1; ++pa)
+                    for (int c = c0; c <= c1; ++c) {
+                        int ry0 = pa * p.rs, ry1 = ry0 + p.rs < p.H ? ry0 + p.rs : p.H, rx0 = c * 26, rx1 = rx0 + 26 < p.W ? rx0 + 26 : p.W;
+                        ry0 = ry0 - 3 < 0 ? 0 : ry0 - 3; ry1 = ry1 + 3 > p.H ? p.H : ry1 + 3; rx0 = rx0 - 3 < 0 ? 0 : rx0 - 3; rx1 = rx1 + 3 > p.W ? p.W : rx1 + 3;
+                        if (ry0 < y1 && y0 < ry1 && rx0 < x1 && x0 < rx1 && p.head_flags[pa * ncols + b * p.txh + c] != 0) need = 1;
+                    }
+            } else {             // read by: the 4 x 32 input pixels of a listed tile of the level downstream plus one row below and one column right
+                const int Hd = p.uh[lv - 1], Wd = p.uw[lv - 1], tyd_n = (Hd + 3) / 4, txd_n = (Wd + 31) / 32;
+                int a0 = y0 / 4 - 1, a1 = y1 / 4 + 1, c0 = x0 / 32 - 1, c1 = x1 / 32 + 1;
+                a0 = a0 < 0 ? 0 : a0; a1 = a1 >= tyd_n ? tyd_n - 1 : a1; c0 = c0 < 0 ? 0 : c0; c1 = c1 >= txd_n ? txd_n - 1 : c1;
+                for (int a = a0; a <= a1; ++a)
+                    for (int c = c0; c <= c1; ++c) {
+                        const int ry0 = 4 * a, ry1 = ry0 + 5 < Hd ? ry0 + 5 : Hd, rx0 = 32 * c, rx1 = rx0 + 33 < Wd ? rx0 + 33 : Wd;
+                        if (ry0 < y1 && y0 < ry1 && rx0 < x1 && x0 < rx1 && p.up_flags[lv - 1][(b * tyd_n + a) * txd_n + c] != 0) need = 1;
+                    }
+            }
+            p.up_flags[lv][t] = need;
+        }
+        __syncthreads();
+        tail_compact(p.up_flags[lv], nsp, p.mg[lv], p.up_list[lv], p.up_count[lv], lds);
     }
 }
 
@@ -631,6 +737,59 @@ extern "C" int lama_blend_quantize_u8_fwd(void* stream, const uint8_t* image_hwc
     p.out_u8 = dst_hwc;
     p.B = batch; p.Hp = pred->H; p.Wp = pred->W; p.binarize = binarize;
     hipLaunchKernelGGL(blend_quantize_u8_kernel, dim3(ew_grid((long long)batch * pred->H * pred->W)), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// work lists of the sparse tail: see tail_flags_kernel / tail_lists_kernel
+static bool tail_geometry(const lama_tensor* mask, int32_t batch, const lama_tail_lists* l, TailParams* p) {
+    if (!mask || !l || batch <= 0 || mask->H <= 0 || mask->W <= 0 || l->n_up < 0 || l->n_up > TAIL_MAX_UP || l->head_rs < 8 || l->head_rs % 8 != 0) return false;
+    memset(p, 0, sizeof(*p));
+    p->B = batch; p->H = mask->H; p->W = mask->W;
+    p->txh = lama_ceil_div(mask->W, 26); p->rs = l->head_rs; p->ns = lama_ceil_div(mask->H, l->head_rs);
+    p->n_up = l->n_up;
+    int H = mask->H, W = mask->W;
+    for (int i = 0; i < l->n_up; ++i) {          // level i writes the plane level i - 1 (the head for i = 0) reads: twice its own input plane
+        if (H % 2 != 0 || W % 2 != 0 || l->up_mg[i] < 1) return false;
+        H /= 2; W /= 2;
+        p->uh[i] = H; p->uw[i] = W; p->mg[i] = l->up_mg[i];
+    }
+    long long total = (long long)batch * p->txh * p->ns;
+    for (int i = 0; i < l->n_up; ++i) total += (long long)batch * lama_ceil_div(p->uh[i], 4) * lama_ceil_div(p->uw[i], 32) * p->mg[i];
+    return total < (1ll << 24);                  // one workgroup closes and compacts every list
+}
+extern "C" size_t lama_tail_lists_workspace_bytes(int32_t batch, int32_t H, int32_t W, const lama_tail_lists* lists) {
+    lama_tensor m;
+    memset(&m, 0, sizeof(m));
+    m.H = H; m.W = W;
+    TailParams p;
+    if (!tail_geometry(&m, batch, lists, &p)) return 0;
+    size_t n = (size_t)batch * p.txh * p.ns;
+    for (int i = 0; i < p.n_up; ++i) n += (size_t)batch * lama_ceil_div(p.uh[i], 4) * lama_ceil_div(p.uw[i], 32);
+    return n * sizeof(int32_t);
+}
+extern "C" int lama_tail_lists_build(void* stream, const lama_tensor* mask, int32_t batch, const lama_tail_lists* lists, void* workspace,
+                                     size_t workspace_bytes) {
+    TailParams p;
+    if (!mask || !mask->ptr || mask->C != 1 || !tail_geometry(mask, batch, lists, &p)) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({mask})) return LAMA_ERR_UNSUPPORTED;
+    if (!lists->head_list || !lists->head_count) return LAMA_ERR_BAD_ARG;
+    for (int i = 0; i < p.n_up; ++i)
+        if (!lists->up_list[i] || !lists->up_count[i]) return LAMA_ERR_BAD_ARG;
+    if (!workspace || ((uintptr_t)workspace & 3) != 0 || workspace_bytes < lama_tail_lists_workspace_bytes(batch, mask->H, mask->W, lists)) return LAMA_ERR_WORKSPACE;
+    p.mask = (const float*)mask->ptr; p.mask_bs = mask->batch_stride;
+    int* ws = (int*)workspace;
+    p.head_flags = ws;
+    ws += (size_t)batch * p.txh * p.ns;
+    p.head_list = lists->head_list; p.head_count = lists->head_count;
+    for (int i = 0; i < p.n_up; ++i) {
+        p.up_flags[i] = ws;
+        ws += (size_t)batch * lama_ceil_div(p.uh[i], 4) * lama_ceil_div(p.uw[i], 32);
+        p.up_list[i] = lists->up_list[i]; p.up_count[i] = lists->up_count[i];
+    }
+    hipLaunchKernelGGL(tail_flags_kernel, dim3(batch * p.txh * p.ns), dim3(64), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(tail_lists_kernel, dim3(1), dim3(TAIL_NT), TAIL_NT * sizeof(int), (hipStream_t)stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }

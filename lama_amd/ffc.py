@@ -228,7 +228,7 @@ class _Exec:
         flag = self._cur_flag if kw.get('precision') in (L.PREC_F16X3, L.PREC_F16) else None
         if self.siblings_log2:
             kw['siblings_log2'] = self.siblings_log2
-        self.lib.conv2d(*a, range_flag=flag, **kw)
+        return self.lib.conv2d(*a, range_flag=flag, **kw)
 
     def fourier_unit(self, *a, precision: int = L.PREC_F32, stream: int = 0, wino_out=None):
         flag = self._cur_flag if precision in (L.PREC_F16X3, L.PREC_F16) else None
@@ -326,6 +326,11 @@ class _PlanGenerator(_HipModule):
         # activation-buffer sets (+ captured hipGraphs) per input shape: 2.2 GB at 8 x 512^2, so only the most recently used
         # ``max_plans`` shapes are kept (a directory of many image sizes would otherwise fill HBM)
         self.max_plans = 4
+        # The sparse tail: a caller that keeps only mask * pred + (1 - mask) * image (forward_u8 with out_key 'inpainted') sets this
+        # around its forward; a generator whose plan builder knows the tail (``has_sparse_tail``) then serves the shape from plans of their own
+        # -- cached under their own key -- whose last launches walk only the work units a non-zero mask pixel needs.  The output buffer of such
+        # a plan is UNDEFINED where the mask (channel 3 of the input) is 0.  Everything else -- ``generator(x)``, forward(batch), refinement -- is dense.
+        self.sparse_tail = False
         self._assume_graph = False        # set by a caller that captures this generator's plain launches into a graph of its own (HostFedStep)
         self.split_decisions = {}         # (shape, device) -> what tune_split measured and kept (bench.py prints it)
         self._plans = collections.OrderedDict()
@@ -340,6 +345,16 @@ class _PlanGenerator(_HipModule):
         torch.device('cuda'), every forward sees x.device = 'cuda:0' -- two keys meant a verdict and a tuned plan no forward ever found)."""
         return (tuple(int(v) for v in shape), _Exec._dev_key(device))
 
+    has_sparse_tail = False               # the subclass's plan builder reads ``sparse_tail``
+
+    def _sparse(self) -> bool:
+        return bool(self.sparse_tail and self.has_sparse_tail)
+
+    def _cache_key(self, shape, device):
+        """Key of the plan cache: dense and sparse-tail plans of one shape live side by side."""
+        key = self._plan_key(shape, device)
+        return key + ('sparse_tail',) if self._sparse() else key
+
     def _split_parts(self, shape, device) -> int:
         """How many parallel parts the plan of this input shape has: one, unless the generator builds split plans."""
         return 1
@@ -353,7 +368,7 @@ class _PlanGenerator(_HipModule):
             self._plans.popitem(last=False)
 
     def _plan_for(self, shape, device) -> dict:
-        key = self._plan_key(shape, device)
+        key = self._cache_key(shape, device)
         n = self._split_parts(shape, device)                 # on every call, cached plan or not: a bad ``split_batch`` raises here
         plan = self._plans.get(key)
         if plan is not None and plan.get('nsplit', 1) != n:
@@ -368,7 +383,9 @@ class _PlanGenerator(_HipModule):
 
     def drop_plan(self, shape, device) -> None:
         """Free the activation buffers / captured graph of one input shape (predict.py drops a bucket's plan when it is done)."""
-        self._plans.pop(self._plan_key(shape, device), None)
+        key = self._plan_key(shape, device)
+        self._plans.pop(key, None)
+        self._plans.pop(key + ('sparse_tail',), None)
 
     def input_buffer(self, shape, device) -> torch.Tensor:
         """The tensor this shape's plan READS its input from (the captured hipGraph's static input when ``use_graph``): a caller that produces
@@ -472,11 +489,11 @@ def _plan_out(layers, i, src, dst, src_shape, pad, bufs, steps, device):
     return shp, 2 if act else 1
 
 
-def _run_step(st, buf):
+def _run_step(st, buf, **kw):
     """Run a plan step of the form (kind, layer, source name, destination name, *what the layer's ``run`` takes behind the two tensors):
     the 'up' and 'out' steps above, and the regular generator's 'conv'."""
     lay, src, dst = st[1:4]
-    lay.run(buf(src), buf(dst), *st[4:])
+    return lay.run(buf(src), buf(dst), *st[4:], **kw)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -977,7 +994,8 @@ class ConvTranspose2dUp(nn.ConvTranspose2d, _HipModule):
         self._packed = None
         self._exec = _DEFAULT_EXEC
 
-    def run(self, src, dst, bn: Optional[nn.BatchNorm2d] = None, act: int = L.ACT_NONE):
+    def run(self, src, dst, bn: Optional[nn.BatchNorm2d] = None, act: int = L.ACT_NONE, tile_list=None, query: bool = False):
+        """``tile_list`` (sparse tail): the launch over the listed tiles only; with ``query`` nothing runs and the answer is whether it can."""
         key = id(bn)
         if self._packed is None or self._packed[0] != key:
             if bn is not None:
@@ -988,8 +1006,8 @@ class ConvTranspose2dUp(nn.ConvTranspose2d, _HipModule):
             self._packed = (key, self._exec.lib.pack_conv_weight(self.weight.detach(), scale, stride=2, transposed=True,
                                                                   precision=self.precision), bias.contiguous())
         _, wp, bias = self._packed
-        self._exec.conv2d(L.view(src), wp, L.view(dst), src.shape[0], 3, 2, 1, L.PAD_ZERO, True, bias, act,
-                              precision=self.precision, stream=self._exec.stream(src))
+        return self._exec.conv2d(L.view(src), wp, L.view(dst), src.shape[0], 3, 2, 1, L.PAD_ZERO, True, bias, act,
+                                 precision=self.precision, stream=self._exec.stream(src), tile_list=tile_list, query=query)
 
     def forward(self, x, bn=None, act=L.ACT_NONE):
         self._exec.check(x)
@@ -1010,13 +1028,15 @@ class Conv2dOut(nn.Conv2d, _HipModule):
         self._packed = None
         self._exec = _DEFAULT_EXEC
 
-    def run(self, src, dst, extra_pad=0, act=L.ACT_NONE):
+    def run(self, src, dst, extra_pad=0, act=L.ACT_NONE, tile_list=None, query: bool = False):
+        """``tile_list`` (sparse tail): the launch over the listed segments only; with ``query`` nothing runs and the answer is whether it can."""
         if self._packed is None:
             self._packed = (self._exec.lib.pack_conv_weight(self.weight.detach(), None, precision=self.precision),
                             self.bias.detach().float().contiguous())
         wp, bias = self._packed
-        self._exec.conv2d(L.view(src), wp, L.view(dst), src.shape[0], self.kernel_size[0], 1, self.padding[0] + extra_pad,
-                              L.PAD_REFLECT, False, bias, act, precision=self.precision, stream=self._exec.stream(src))
+        return self._exec.conv2d(L.view(src), wp, L.view(dst), src.shape[0], self.kernel_size[0], 1, self.padding[0] + extra_pad,
+                                 L.PAD_REFLECT, False, bias, act, precision=self.precision, stream=self._exec.stream(src),
+                                 tile_list=tile_list, query=query)
 
     def forward(self, x, extra_pad=0, act=L.ACT_NONE):
         self._exec.check(x)
@@ -1170,6 +1190,9 @@ class FFCResNetGenerator(_PlanGenerator):
         self._split_ok = {}               # (shape, device) -> False where the check rejected the split plan
         self.split_margin = 0.02          # the split plan must be this much faster (median) to be kept
         self.split_replays = 9            # timed replays of each graph in tune_split
+        # sparse-tail plans (``sparse_tail``): rows per head segment.  The host cannot know how many segments a mask lists, so the parts are small:
+        # 16 rows pay 7 window rows each, and a listed segment covers little that nobody needs
+        self.tail_head_rs = 16
         super().train(False)
 
     # ------------------------------------------------------------------------------------------------
@@ -1288,7 +1311,38 @@ class FFCResNetGenerator(_PlanGenerator):
                 scratch['ws'] = wn[:ws.numel()]
         side = torch.cuda.Stream(device=device) if (self.overlap_streams and not serial and not one_stream and torch.device(device).type == 'cuda') else None
         return dict(steps=steps, bufs=bufs, scratch=scratch, out=cur, graph=None, static_in=None, side=side,
+                    tail=self._plan_tail(steps, bufs, tuple(shape), device) if self._sparse() else None,
                     fuse=self.fuse_conv1 or (serial and self.fuse_conv1 is not False and self.fuse_conv1_serial))
+
+    has_sparse_tail = True
+
+    def _plan_tail(self, steps, bufs, shape, device) -> Optional[dict]:
+        """The sparse tail of a plan: the head and the run of upsamplings in front of it, with the work lists their launches walk.
+        None where the plan has no such tail (the input carries no mask channel, the head does not write the input's plane)."""
+        _, C, H, W = shape
+        if C != 4 or not steps or steps[-1][0] != 'out' or tuple(bufs[steps[-1][3]].shape[2:]) != (H, W):
+            return None
+        ups, i = [], len(steps) - 2
+        while (i >= 0 and steps[i][0] == 'up' and len(ups) < 4 and steps[i][1].out_channels % 64 == 0
+               and H % (2 << len(ups)) == 0 and W % (2 << len(ups)) == 0):
+            ups.append(i)
+            i -= 1
+        lists = self._exec.lib.tail_lists_alloc(shape[0], H, W, self.tail_head_rs, [steps[j][1].out_channels // 64 for j in ups], device)
+        return dict(lists=lists, out=len(steps) - 1, ups=ups, taken=None)
+
+    def _tail_taken(self, plan, B) -> dict:
+        """Which launches of the tail walk their list: step index -> (list, count, head_rs).  From the head backwards, and only as far as the
+        dedicated kernels take the shapes: a launch that runs dense reads every pixel of its input, so everything upstream of it is dense too."""
+        tail, steps = plan['tail'], plan['steps']
+        ls, rs = tail['lists'], tail['lists']['head_rs']
+        taken = {}
+        if _run_step(steps[tail['out']], B, tile_list=ls['head'] + (rs,), query=True):
+            taken[tail['out']] = ls['head'] + (rs,)
+            for lv, j in enumerate(tail['ups']):
+                if not _run_step(steps[j], B, tile_list=ls['up'][lv] + (rs,), query=True):
+                    break
+                taken[j] = ls['up'][lv] + (rs,)
+        return taken
 
     def _run_plan(self, plan, x):
         if 'parts' in plan:
@@ -1299,6 +1353,13 @@ class FFCResNetGenerator(_PlanGenerator):
             return x if name == 'in' else bufs[name]
 
         steps = plan['steps']
+        sparse = {}
+        if plan.get('tail') is not None:
+            if plan['tail']['taken'] is None:
+                plan['tail']['taken'] = self._tail_taken(plan, B)
+            sparse = plan['tail']['taken']
+            if sparse:              # two small launches at the head of the plan: the lists of this step's mask (channel 3 of the input)
+                self._exec.lib.tail_lists_build(L.view(x, 3, 1), plan['tail']['lists'], self._exec.stream(x))
         x1_ready = False
         if plan['scratch']:
             plan['scratch'].pop('pending_out', None)        # (left behind by a run that raised)
@@ -1322,6 +1383,8 @@ class FFCResNetGenerator(_PlanGenerator):
                         self._exec.lib.winograd_out(pend[0], pend[1], self._exec.stream(x))
                     if pipe is not None:
                         pipe.join()                 # the last local conv: everything downstream reads its x_l
+            elif i in sparse:                       # 'up', 'out' over the listed work units
+                _run_step(st, B, tile_list=sparse[i])
             else:                                   # 'up', 'out'
                 _run_step(st, B)
         return bufs[plan['out']]
@@ -1429,7 +1492,7 @@ class FFCResNetGenerator(_PlanGenerator):
         cand.clear()                              #  input_buffer hands it to a caller that writes its input in place); the loser is released now
         del x
         self._make_room()
-        self._plans[key] = plan
+        self._plans[self._cache_key(shape, device)] = plan
         torch.cuda.empty_cache()
         return n if ok else 1
 

@@ -108,16 +108,26 @@ class DefaultInpaintingTrainingModule(nn.Module):
             raise NotImplementedError('concat_mask=False is not used by big-lama')
         st = ex.stream(image_hwc)
         gen = self.generator
-        masked = gen.input_buffer((B, 4, H, W), image_hwc.device) if hasattr(gen, 'input_buffer') else torch.empty(B, 4, H, W, device=image_hwc.device)
-        ex.lib.mask_compose_u8(image_hwc, mask, sizes, L.view(masked), B, binarize, st)
-        if hasattr(gen, 'clone_output'):
-            keep, gen.clone_output = gen.clone_output, False                       # the blend below consumes the plan's own output buffer at once
-            try:
+        # 'inpainted' keeps mask * pred + (1 - mask) * image: the blend below never reads pred where the mask is 0, so the generator may leave those
+        # pixels unwritten -- the sparse-tail plans of this shape (generator.sparse_tail; cached apart from the dense ones that 'predicted_image',
+        # forward(batch) and a bare generator(x) take)
+        keep_sparse = getattr(gen, 'sparse_tail', None)
+        if keep_sparse is not None:
+            gen.sparse_tail = out_key == 'inpainted'
+        try:
+            masked = gen.input_buffer((B, 4, H, W), image_hwc.device) if hasattr(gen, 'input_buffer') else torch.empty(B, 4, H, W, device=image_hwc.device)
+            ex.lib.mask_compose_u8(image_hwc, mask, sizes, L.view(masked), B, binarize, st)
+            if hasattr(gen, 'clone_output'):
+                keep, gen.clone_output = gen.clone_output, False                   # the blend below consumes the plan's own output buffer at once
+                try:
+                    pred = gen(masked)
+                finally:
+                    gen.clone_output = keep
+            else:
                 pred = gen(masked)
-            finally:
-                gen.clone_output = keep
-        else:
-            pred = gen(masked)
+        finally:
+            if keep_sparse is not None:
+                gen.sparse_tail = keep_sparse
         if out_key == 'predicted_image':
             ex.lib.quantize_u8_hwc(L.view(pred), out_u8, B, H, W, st)              # predict.py:92 on batch['predicted_image']
         else:
