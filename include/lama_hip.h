@@ -484,6 +484,28 @@ int lama_global_avgpool_fwd(void* stream, const lama_tensor* x, float* y, int32_
  * (inception.py:196-203).  resize = 0: 2 x - 1 only, y.H = H, y.W = W. */
 int lama_fid_input_fwd(void* stream, const lama_tensor* pred, const lama_tensor* target, const lama_tensor* y, int32_t batch, int32_t resize);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) activation ranges: WHERE a tensor leaves the fp16 split's range ----
+ * The range watch (lama_conv2d_args.range_flag) is one bit per device.  lama_range_stats_fwd reduces any view to per-channel statistics in one read:
+ * for channel c of x [batch, C, H, W] (fp32 or fp16, any batch_stride >= C H W, any element-aligned start, any plane size), over its batch H W elements,
+ *   n_nan = NaNs, n_inf = +-inf, n_over = FINITE elements with |e| > limit, abs_max = the largest |e| over the finite elements (+0.0f if none).
+ * Elements are classified on their bit patterns (fp16 ones widen exactly): exactly `limit` is not over, the next float is; -0.0 and denormals count as
+ * what they are (nothing is flushed).  out: device [x->C], OVERWRITTEN (no zeroing launch).  Two launches (per-piece partials into `workspace`, then one
+ * fold per channel), no atomics: bit-identical run to run; asynchronous and hipGraph-capturable.  workspace: lama_range_stats_workspace_bytes() device
+ * bytes, 4-byte aligned.
+ * LAMA_ERR_BAD_ARG: a null pointer, batch <= 0, an empty view, limit that is not a positive finite number, batch_stride < C H W, a misaligned pointer;
+ * LAMA_ERR_WORKSPACE: workspace too small; LAMA_ERR_UNSUPPORTED: an unknown dtype, batch H W >= 2^32 (the counters are 32-bit) or more than 2^31 - 1
+ * 32 KiB pieces in all.  Nothing is launched and out is untouched on an error. */
+typedef struct lama_range_stats { float abs_max; uint32_t n_nan, n_inf, n_over; } lama_range_stats;   /* 16 bytes, one per channel */
+size_t lama_range_stats_workspace_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
+int    lama_range_stats_fwd(void* stream, const lama_tensor* x, int32_t batch, float limit,
+                            lama_range_stats* out /* device, [x->C] */, void* workspace, size_t workspace_bytes);
+/* The two spectra inside a lama_fourier_unit_fwd workspace for x [batch, C, h, w] of element type dtype, as that call leaves them: spec_in = the
+ * interleaved rfft2 of x (the operand the spectral 1x1 splits, ffc.py:86-100), spec_out = relu(bn(conv(spec_in))) (ffc.py:100-101), both
+ * [batch, 2C, h, w/2+1].  The library's own statement of the layout (lama_fourier_unit_fwd goes through it); nothing is launched.
+ * LAMA_ERR_BAD_ARG / LAMA_ERR_UNSUPPORTED (dtype) / LAMA_ERR_WORKSPACE (smaller than lama_fourier_unit_workspace_bytes). */
+int lama_fourier_unit_workspace_views(int32_t batch, int32_t C, int32_t h, int32_t w, int32_t dtype, void* workspace, size_t workspace_bytes,
+                                      lama_tensor* spec_in, lama_tensor* spec_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,9 @@ class LamaLib:
         L.lama_pool3x3_fwd.restype, L.lama_pool3x3_fwd.argtypes = C.c_int, [vp, T, T, i32, i32, i32, i32]
         L.lama_global_avgpool_fwd.restype, L.lama_global_avgpool_fwd.argtypes = C.c_int, [vp, T, vp, i32]
         L.lama_fid_input_fwd.restype, L.lama_fid_input_fwd.argtypes = C.c_int, [vp, T, T, T, i32, i32]
+        L.lama_range_stats_workspace_bytes.restype, L.lama_range_stats_workspace_bytes.argtypes = sz, [i32] * 4
+        L.lama_range_stats_fwd.restype, L.lama_range_stats_fwd.argtypes = C.c_int, [vp, T, i32, C.c_float, vp, vp, sz]
+        L.lama_fourier_unit_workspace_views.restype, L.lama_fourier_unit_workspace_views.argtypes = C.c_int, [i32, i32, i32, i32, i32, vp, sz, T, T]
         del dp
         if L.lama_version() != ABI_VERSION:
             raise LamaError(f'{path}: ABI version {L.lama_version()} != {ABI_VERSION}')
@@ -442,6 +445,37 @@ class LamaLib:
                                                  None if range_flag is None else range_flag.data_ptr()),
                    'lama_fourier_unit_fwd')
 
+    def fourier_unit_views(self, ws: torch.Tensor, b: int, c: int, h: int, w: int, dtype: int = DT_F32):
+        """(spec_in, spec_out): the two [b, 2c, h, w/2+1] spectra a ``fourier_unit`` call on x [b, c, h, w] leaves inside its workspace ``ws`` --
+        the operand of the spectral 1x1 and its BN + ReLU output (lama_fourier_unit_workspace_views: the library states the layout)."""
+        si, so = Tensor4(), Tensor4()
+        self.check(self._l.lama_fourier_unit_workspace_views(b, c, h, w, dtype, ws.data_ptr(), ws.numel() * ws.element_size(), C.byref(si),
+                                                             C.byref(so)), 'lama_fourier_unit_workspace_views')
+        return si, so
+
+    # -- activation ranges (lama_range_stats_fwd) ------------------------------------------------------
+    def range_stats_workspace_bytes(self, batch: int, c: int, h: int, w: int) -> int:
+        return int(self._l.lama_range_stats_workspace_bytes(batch, c, h, w))
+
+    def range_stats(self, x: Tensor4, batch: int, limit: float = F16_MAX, stream: int = 0, out: Optional[torch.Tensor] = None,
+                    ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-channel range statistics of the view ``x`` over ``batch`` images: an int32 [C, 4] device tensor of lama_range_stats records --
+        column 0 holds the BITS of abs_max (fp32), columns 1..3 n_nan, n_inf, n_over (uint32 bits); ``unpack_range_stats`` reads it on the
+        host.  ``out`` (int32, at least 4 C elements, overwritten) and ``ws`` (the workspace) are allocated when absent -- a view carries no
+        device, so on the other's device, or on the current GPU when neither is given."""
+        if out is None:
+            dev = ws.device if ws is not None else (torch.device('cpu') if self.host_emulated else torch.device('cuda', torch.cuda.current_device()))
+            out = torch.empty(x.C, 4, dtype=torch.int32, device=dev)
+        if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < 4 * x.C or (not self.host_emulated and not out.is_cuda):
+            raise LamaError(f'range_stats: out is a contiguous device int32 tensor of at least 4 * C elements, got {tuple(out.shape)} {out.dtype}')
+        if ws is None:
+            ws = torch.empty(max(1, self.range_stats_workspace_bytes(batch, x.C, x.H, x.W) // 4), dtype=torch.int32, device=out.device)
+        elif not self.host_emulated and not ws.is_cuda:
+            raise LamaError('range_stats: the workspace must be a device tensor')
+        self.check(self._l.lama_range_stats_fwd(stream, C.byref(x), batch, float(limit), out.data_ptr(), ws.data_ptr(),
+                                                ws.numel() * ws.element_size()), 'lama_range_stats_fwd')
+        return out
+
     # -- elementwise -------------------------------------------------------------------------------
     def mask_compose(self, image: Tensor4, mask: Tensor4, out: Tensor4, batch: int, stream: int = 0):
         self.check(self._l.lama_mask_compose_fwd(stream, C.byref(image), C.byref(mask), C.byref(out), batch), 'lama_mask_compose_fwd')
@@ -692,6 +726,16 @@ class LamaLib:
                 raise LamaError('adam_step: contiguous fp32 tensors of one size expected')
         self.check(self._l.lama_adam_step(stream, param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, lr,
                                           beta1, beta2, eps, step), 'lama_adam_step')
+
+
+def unpack_range_stats(stats: torch.Tensor):
+    """Host view of a ``LamaLib.range_stats`` result (int32 [..., 4], any device): (abs_max float32 [...], n_nan, n_inf, n_over uint32 [...])
+    as numpy arrays.  One D2H copy when the tensor is on the device."""
+    import numpy as np
+    a = np.ascontiguousarray(stats.detach().cpu().numpy()).reshape(-1, 4)
+    lead = tuple(stats.shape[:-1]) if stats.dim() > 1 else (a.shape[0],)
+    u = a.view(np.uint32)
+    return (a[:, 0].copy().view(np.float32).reshape(lead), u[:, 1].copy().reshape(lead), u[:, 2].copy().reshape(lead), u[:, 3].copy().reshape(lead))
 
 
 _LIB: Optional[LamaLib] = None

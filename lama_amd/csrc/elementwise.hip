@@ -900,11 +900,28 @@ extern "C" int lama_reflect_pad_fwd(void* stream, const lama_tensor* x, int32_t 
 }
 
 // ---- FourierUnit.forward (ffc.py:76-113) as three launches over caller workspace ------------------
+// bytes of one spectrum slot of the FourierUnit's workspace: [batch, 2C, h, w/2+1] fp32, rounded up to 256
+static size_t fu_spec_bytes(int32_t batch, int32_t C, int32_t h, int32_t w) {
+    return ((size_t)batch * 2 * C * h * (w / 2 + 1) * sizeof(float) + 255) & ~(size_t)255;
+}
+
 extern "C" size_t lama_fourier_unit_workspace_bytes(int32_t batch, int32_t C, int32_t h, int32_t w) {
     if (batch <= 0 || C <= 0 || h <= 0 || w <= 0) return 0;
-    size_t spec = (size_t)batch * 2 * C * h * (w / 2 + 1) * sizeof(float);
-    spec = (spec + 255) & ~(size_t)255;
-    return 2 * spec + lama_fft_workspace_bytes(batch, C, h, w);
+    return 2 * fu_spec_bytes(batch, C, h, w) + lama_fft_workspace_bytes(batch, C, h, w);
+}
+
+// The ONE statement of the FourierUnit's workspace layout: spec_in (the operand of the spectral 1x1) | spec_out (after BN + ReLU), each
+// [batch, 2C, h, w/2+1] in the activation dtype inside a 256-byte aligned slot sized for fp32, then the FFT workspace.
+extern "C" int lama_fourier_unit_workspace_views(int32_t batch, int32_t C, int32_t h, int32_t w, int32_t dtype, void* workspace, size_t workspace_bytes,
+                                                 lama_tensor* spec_in, lama_tensor* spec_out) {
+    if (batch <= 0 || C <= 0 || h <= 0 || w <= 0 || !spec_in || !spec_out) return LAMA_ERR_BAD_ARG;
+    if (dtype != LAMA_DT_F32 && dtype != LAMA_DT_F16) return LAMA_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < lama_fourier_unit_workspace_bytes(batch, C, h, w)) return LAMA_ERR_WORKSPACE;
+    const int wf = w / 2 + 1;
+    char* ws = (char*)workspace;
+    *spec_in = lama_tensor{ws, (int64_t)2 * C * h * wf, 2 * C, h, wf, dtype};
+    *spec_out = lama_tensor{ws + fu_spec_bytes(batch, C, h, w), (int64_t)2 * C * h * wf, 2 * C, h, wf, dtype};
+    return LAMA_OK;
 }
 
 static int fourier_unit_impl(void* stream, const lama_tensor* x, const void* w_packed, const float* bias,
@@ -913,16 +930,16 @@ static int fourier_unit_impl(void* stream, const lama_tensor* x, const void* w_p
                              const lama_conv2d_args* wino_args, void* wino_ws, size_t wino_ws_bytes, int32_t flags = 0) {
     if (!x || !y || !x->ptr || !y->ptr || !w_packed || batch <= 0) return LAMA_ERR_BAD_ARG;
     if (x->C != y->C || x->H != y->H || x->W != y->W) return LAMA_ERR_BAD_ARG;
-    const int C = x->C, h = x->H, w = x->W, wf = w / 2 + 1;
+    const int C = x->C, h = x->H, w = x->W;
     if (!workspace || workspace_bytes < lama_fourier_unit_workspace_bytes(batch, C, h, w)) return LAMA_ERR_WORKSPACE;
-    size_t spec_bytes = ((size_t)batch * 2 * C * h * wf * sizeof(float) + 255) & ~(size_t)255;
+    const size_t spec_bytes = fu_spec_bytes(batch, C, h, w);
     char* ws = (char*)workspace;
     if (x->dtype != y->dtype) return LAMA_ERR_UNSUPPORTED;
-    lama_tensor s1 = {ws, (int64_t)2 * C * h * wf, 2 * C, h, wf, x->dtype};
-    lama_tensor s2 = {ws + spec_bytes, (int64_t)2 * C * h * wf, 2 * C, h, wf, x->dtype};
+    lama_tensor s1, s2;
+    int rc = lama_fourier_unit_workspace_views(batch, C, h, w, x->dtype, workspace, workspace_bytes, &s1, &s2);
+    if (rc) return rc;
     void* fws = ws + 2 * spec_bytes;
     size_t fws_bytes = workspace_bytes - 2 * spec_bytes;
-    int rc;
     if (wino_args) {      // the deferred output transform of the Winograd conv of the layer before: inside the rfft2 launch where a kernel does that
         rc = lama_rfft2_winograd_out_fwd(stream, x, &s1, batch, fws, fws_bytes, wino_args, wino_ws, wino_ws_bytes);
         if (rc == LAMA_ERR_UNSUPPORTED) {
