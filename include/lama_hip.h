@@ -215,6 +215,23 @@ int lama_irfft2_masked_fwd(void* stream, const lama_tensor* spec, const lama_ten
                            int32_t batch, void* workspace, size_t workspace_bytes);
 /* scratch bytes lama_rfft2_fwd / lama_irfft2_fwd / lama_fourier_unit_fwd need for [B,C,h,w] */
 size_t lama_fft_workspace_bytes(int32_t batch, int32_t C, int32_t h, int32_t w);
+/* (added to v112 without a version bump: one new symbol, nothing else changes) Which kernels would serve a transform, asked on the host:
+ * returns exactly the code lama_rfft2_fwd (inverse == 0: `real` is x, `resid` is ignored) / lama_irfft2_fwd (inverse != 0: `real` is y, `resid` may
+ * be NULL) -- or, with mask != NULL, lama_rfft2_masked_fwd / lama_irfft2_masked_fwd -- return for the same views, batch and workspace.  Nothing is
+ * launched and no tensor or workspace pointer is dereferenced: only their addresses (alignment) are looked at.  On LAMA_OK *family is the kernel
+ * family, 1 .. 6 (1 plane in LDS, power of two; 2 one-launch mixed radix; 3 compile-time 256 x 256 pair; 4 two-pass power of two; 5 two-launch
+ * mixed radix; 6 separable DFT), and *kind the kernel inside family 1 (LAMA_FFT_KIND_*), the threads per workgroup (256 / 1024) for family 2, and
+ * 0 otherwise.  A plane is served only where BOTH directions have a kernel for it: the two directions of one set of views report the same code and
+ * family.  LAMA_ERR_BAD_ARG also for family == NULL or kind == NULL.  lama_rfft2_winograd_out_fwd is not covered. */
+#define LAMA_FFT_KIND_WINO64 0  /* one-buffer 64 x 64 with the Winograd output transform (lama_rfft2_winograd_out_fwd only: never reported) */
+#define LAMA_FFT_KIND_IP64 1    /* one-buffer 64 x 64 */
+#define LAMA_FFT_KIND_IP128 2   /* one-buffer 128 x 128 */
+#define LAMA_FFT_KIND_TRACE64 3 /* profiling build only */
+#define LAMA_FFT_KIND_SEQ 4     /* profiling build only */
+#define LAMA_FFT_KIND_SIZED 5   /* two-buffer, compile-time 32 / 64 / 128 squares */
+#define LAMA_FFT_KIND_GENERIC 6 /* two-buffer, any power-of-two plane of 16 .. 128 */
+int lama_fft_route_query(const lama_tensor* real, const lama_tensor* resid, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
+                         int32_t inverse, const void* workspace, size_t workspace_bytes, int32_t* family, int32_t* kind);
 
 /* FourierUnit.forward (ffc.py:76-113) in one call: y = [x +] irfft2( relu( W' rfft2(x) + b ) ).
  * w_packed = lama_conv2d_pack_weight(conv_layer.weight [2C,2C,1,1], bn scale); bias = bn shift.

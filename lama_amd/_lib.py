@@ -39,6 +39,7 @@ class LamaRangeError(LamaError):
 
 F16_MAX = 65504.0
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -2, -3      # include/lama_hip.h LAMA_ERR_*
+FFT_KIND_WINO64, FFT_KIND_IP64, FFT_KIND_IP128, FFT_KIND_TRACE64, FFT_KIND_SEQ, FFT_KIND_SIZED, FFT_KIND_GENERIC = range(7)   # LAMA_FFT_KIND_*
 
 
 class Tensor4(C.Structure):
@@ -124,6 +125,8 @@ class LamaLib:
         L.lama_irfft2_masked_fwd.argtypes = [vp, T, T, T, T, i32, vp, sz]
         L.lama_fft_workspace_bytes.restype = sz
         L.lama_fft_workspace_bytes.argtypes = [i32] * 4
+        L.lama_fft_route_query.restype = C.c_int
+        L.lama_fft_route_query.argtypes = [T, T, T, T, i32, i32, vp, sz, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.lama_fourier_unit_workspace_bytes.restype = sz
         L.lama_fourier_unit_workspace_bytes.argtypes = [i32] * 4
         L.lama_fourier_unit_fwd.restype = C.c_int
@@ -392,6 +395,16 @@ class LamaLib:
     # -- fft -------------------------------------------------------------------------------------
     def fft_workspace_bytes(self, b, c, h, w) -> int:
         return int(self._l.lama_fft_workspace_bytes(b, c, h, w))
+
+    def fft_route_query(self, real: Tensor4, resid: Optional[Tensor4], spec: Tensor4, batch: int, inverse: bool, ws_addr: Optional[int] = None,
+                        ws_bytes: int = 0, mask: Optional[Tensor4] = None):
+        """(code, family, kind) of lama_fft_route_query: the return code ``rfft2`` / ``irfft2`` (``inverse``; with ``mask`` the masked entries) give
+        for these views and this workspace ADDRESS, and on 0 the kernel family 1 .. 6 and FFT_KIND_* / threads per workgroup / 0.  Host only:
+        nothing is launched, no pointer is dereferenced, so the addresses need not be real."""
+        fam, kind = C.c_int32(-1), C.c_int32(-1)
+        rc = self._l.lama_fft_route_query(C.byref(real), None if resid is None else C.byref(resid), C.byref(spec), None if mask is None else C.byref(mask),
+                                          batch, int(bool(inverse)), ws_addr, ws_bytes, C.byref(fam), C.byref(kind))
+        return (int(rc), None, None) if rc else (0, fam.value, kind.value)
 
     def rfft2(self, x: Tensor4, spec: Tensor4, batch: int, ws: Optional[torch.Tensor] = None, stream: int = 0, mask: Optional[Tensor4] = None):
         """``mask``: spec *= [mask > 0] in the same launch (lama_rfft2_masked_fwd; LamaError ERR_UNSUPPORTED where no kernel does it)."""

@@ -18,7 +18,7 @@
 //   3. fq                         : fp32 256 x 256, aligned views and workspace: compile-time rows + columns pair; the only kernels that apply a mask
 //   4. two-pass power of two      : h, w powers of two in 16..1024 that row 1 cannot hold: rows + columns pair
 //   5. two-launch mixed radix     : mr2_* rows + columns pair (fft_mr_dev.inc), lengths whose factors its passes take
-//   6. separable DFT              : the last resort, rows + columns pair, O(n) more flops; LAMA_ERR_UNSUPPORTED beyond 160 KB of LDS
+//   6. separable DFT              : the last resort, rows + columns pair, O(n) more flops; LAMA_ERR_UNSUPPORTED where either direction needs more than 160 KB of LDS
 // A masked entry is served by row 3 only, the Winograd-output entry by the 64 x 64 one-buffer kernel of row 1 only (LAMA_ERR_UNSUPPORTED otherwise).
 //
 // The plane-in-LDS power-of-two kernels:
@@ -1888,10 +1888,13 @@ int fft_route(FftParams& p, bool inv, bool hf, bool real_al, bool spec_al, bool 
     if (mr2_fill(r.q, p, &r.lds, &r.lds_cols)) return is(FFT_MR2);
     fft_split1(w, p.w1, p.w2);
     fft_split1(h, p.h1, p.h2);
-    r.lds = inv ? ((size_t)w * (1 + 2 * DFT_ROWS_PER_WG) + (size_t)DFT_ROWS_PER_WG * p.w1) * sizeof(float2)
-                : (size_t)w * sizeof(float2) + (size_t)DFT_ROWS_PER_WG * ((size_t)(w + p.w1) * sizeof(float2) + w * sizeof(float));
+    // a plane is served only where BOTH directions fit their LDS (the inverse rows need more: the Hermitian whole Z beside T), so that rfft2
+    // and irfft2 refuse the same planes and a caller of both (lama_fourier_unit_fwd) is refused before its first launch
+    const size_t rows_fwd = (size_t)w * sizeof(float2) + (size_t)DFT_ROWS_PER_WG * ((size_t)(w + p.w1) * sizeof(float2) + w * sizeof(float));
+    const size_t rows_inv = ((size_t)w * (1 + 2 * DFT_ROWS_PER_WG) + (size_t)DFT_ROWS_PER_WG * p.w1) * sizeof(float2);
+    r.lds = inv ? rows_inv : rows_fwd;
     r.lds_cols = (size_t)h * sizeof(float2) * (1 + 2 * DFT_COLS_PER_WG);
-    return r.lds > 160 * 1024 || r.lds_cols > 160 * 1024 ? (int)LAMA_ERR_UNSUPPORTED : is(FFT_DFT);
+    return rows_fwd > 160 * 1024 || rows_inv > 160 * 1024 || r.lds_cols > 160 * 1024 ? (int)LAMA_ERR_UNSUPPORTED : is(FFT_DFT);
 }
 
 }  // namespace
@@ -1989,39 +1992,68 @@ static int fft_launch(hipStream_t st, FftRoute& r, const FftParams& p, bool hf, 
     return LAMA_OK;
 }
 
-// rfft2 (INV = false: `real` is the input x, no resid) and irfft2 (INV = true: `real` is the output y, `resid` may be absent).  `mask` is laid
-// out like the output: spec forward, y inverse.
-template <bool INV>
-static int fft2_impl(void* stream, const lama_tensor* real, const lama_tensor* resid, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
-                     void* workspace, size_t workspace_bytes, const WoParams* wo = nullptr) {
+// One validated call: the kernel parameters, the element type and the route.
+struct FftCall {
+    FftParams p;
+    FftRoute r;
+    bool hf;
+};
+
+// The host half of a call, shared by the launching entries and lama_fft_route_query: validates the views, fills the FftParams and asks
+// fft_route().  rfft2 (inv = false: `real` is the input x, no resid) and irfft2 (inv = true: `real` is the output y, `resid` may be absent).
+// `mask` is laid out like the output: spec forward, y inverse.  Only the ADDRESSES of the views are looked at, nothing is launched.
+static int fft_prepare(bool inv, const lama_tensor* real, const lama_tensor* resid, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
+                       const void* workspace, size_t workspace_bytes, bool wo, FftCall& c) {
     if (!fft_args_ok(real, spec, batch)) return LAMA_ERR_BAD_ARG;
-    const bool has_r = resid && resid->ptr;
+    const bool has_r = inv && resid && resid->ptr;
     if (has_r && (resid->C != real->C || resid->H != real->H || resid->W != real->W)) return LAMA_ERR_BAD_ARG;
     if (real->dtype != spec->dtype || (has_r && resid->dtype != real->dtype) || (real->dtype != LAMA_DT_F32 && real->dtype != LAMA_DT_F16))
         return LAMA_ERR_UNSUPPORTED;
-    const lama_tensor *out = INV ? real : spec, *x = INV ? (has_r ? resid : nullptr) : real;
+    const lama_tensor *out = inv ? real : spec, *x = inv ? (has_r ? resid : nullptr) : real;
     if (mask && (!mask->ptr || mask->dtype != LAMA_DT_F32 || mask->C != out->C || mask->H != out->H || mask->W != out->W)) return LAMA_ERR_BAD_ARG;
-    FftParams p;
+    FftParams& p = c.p;
     memset(&p, 0, sizeof(p));
     if (x) { p.x = x->ptr; p.x_bstride = x->batch_stride; }
     p.spec = spec->ptr;
     p.spec_bstride = spec->batch_stride;
-    if (INV) { p.y = real->ptr; p.y_bstride = real->batch_stride; }
+    if (inv) { p.y = real->ptr; p.y_bstride = real->batch_stride; }
     if (mask) { p.mask = (const float*)mask->ptr; p.mask_bstride = mask->batch_stride; }
     p.C = real->C; p.h = real->H; p.w = real->W; p.wf = real->W / 2 + 1;
     p.nplanes = batch * real->C;
     p.scale = (float)(1.0 / sqrt((double)p.h * (double)p.w));
     // vector accesses are 4 elements: 16-byte (fp32) / 8-byte (fp16) alignment of every view they touch (the forward mask is read by element)
-    const bool hf = real->dtype == LAMA_DT_F16;
+    const bool hf = c.hf = real->dtype == LAMA_DT_F16;
     const int es = hf ? 2 : 4;
     const uintptr_t amask = hf ? 7 : 15;
     uintptr_t al = (uintptr_t)real->ptr | (uintptr_t)(real->batch_stride * es);
     if (has_r) al |= (uintptr_t)resid->ptr | (uintptr_t)(resid->batch_stride * es);
-    if (INV && mask) al |= (uintptr_t)mask->ptr | (uintptr_t)(mask->batch_stride * 4);
+    if (inv && mask) al |= (uintptr_t)mask->ptr | (uintptr_t)(mask->batch_stride * 4);
     const bool spec_al = (((uintptr_t)spec->ptr | (uintptr_t)(spec->batch_stride * es)) & amask) == 0;
-    FftRoute r;
-    const int rc = fft_route(p, INV, hf, (al & amask) == 0, spec_al, mask != nullptr, wo != nullptr, workspace, workspace_bytes, r);
-    return rc ? rc : fft_launch<INV>((hipStream_t)stream, r, p, hf, (float2*)workspace, wo);
+    return fft_route(p, inv, hf, (al & amask) == 0, spec_al, mask != nullptr, wo, workspace, workspace_bytes, c.r);
+}
+
+template <bool INV>
+static int fft2_impl(void* stream, const lama_tensor* real, const lama_tensor* resid, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
+                     void* workspace, size_t workspace_bytes, const WoParams* wo = nullptr) {
+    FftCall c;
+    const int rc = fft_prepare(INV, real, resid, spec, mask, batch, workspace, workspace_bytes, wo != nullptr, c);
+    return rc ? rc : fft_launch<INV>((hipStream_t)stream, c.r, c.p, c.hf, (float2*)workspace, wo);
+}
+
+// The route lama_rfft2_fwd / lama_irfft2_fwd (with `mask`: the masked entries) take for these arguments, and their return code, without a launch:
+// fft_prepare() is all of it.  family: the row of the table at the top of this file; kind: LAMA_FFT_KIND_* (row 1), threads (row 2), else 0.
+static_assert(LDS_WINO64 == LAMA_FFT_KIND_WINO64 && LDS_IP64 == LAMA_FFT_KIND_IP64 && LDS_IP128 == LAMA_FFT_KIND_IP128 &&
+              LDS_TRACE64 == LAMA_FFT_KIND_TRACE64 && LDS_SEQ == LAMA_FFT_KIND_SEQ && LDS_SIZED == LAMA_FFT_KIND_SIZED &&
+              LDS_GENERIC == LAMA_FFT_KIND_GENERIC, "include/lama_hip.h publishes FftLdsKind");
+extern "C" int lama_fft_route_query(const lama_tensor* real, const lama_tensor* resid, const lama_tensor* spec, const lama_tensor* mask, int32_t batch,
+                                    int32_t inverse, const void* workspace, size_t workspace_bytes, int32_t* family, int32_t* kind) {
+    if (!family || !kind) return LAMA_ERR_BAD_ARG;
+    FftCall c;
+    const int rc = fft_prepare(inverse != 0, real, resid, spec, mask, batch, workspace, workspace_bytes, false, c);
+    if (rc) return rc;
+    *family = (int32_t)c.r.family + 1;
+    *kind = c.r.family == FFT_LDS ? (int32_t)c.r.kind : c.r.family == FFT_MR1 ? c.r.nt : 0;
+    return LAMA_OK;
 }
 
 extern "C" int lama_rfft2_fwd(void* stream, const lama_tensor* x, const lama_tensor* spec, int32_t batch, void* workspace, size_t workspace_bytes) {

@@ -12,7 +12,7 @@ from oracle import refine_oracle as R
 from tests.emu import emu_lib
 
 
-@pytest.mark.parametrize('hw', [(32, 32), (40, 24)], ids=['pow2_planes', 'generic_dft_planes'])
+@pytest.mark.parametrize('hw', [(32, 32), (40, 24)], ids=['pow2_planes', 'mixed_radix_planes'])      # 40 x 24: every FFT plane takes the one-launch mixed-radix kernels (family 2 of lama_fft_route_query)
 @pytest.mark.parametrize('bprec', [L.PREC_F32, L.PREC_BF16X3], ids=['bwd_f32', 'bwd_bf16x3'])
 def test_rear_gradients_match_autograd(hw, bprec):
     cfg = O.small_config(ngf=8, n_blocks=2)

@@ -290,7 +290,8 @@ def test_biglama_fp16_activation_path(shape):
 
 
 def test_odd_sized_input_generic_fft(big):
-    """H, W multiples of 8 only -> bottleneck 21x27 (odd, non power-of-two): generic DFT kernels."""
+    """H, W multiples of 8 only -> bottleneck 21x27 (odd, non power-of-two): the one-launch mixed-radix kernels, 256 threads
+    (family 2 of lama_fft_route_query; the separable DFT serves no plane of this size any more)."""
     cfg, sd, gen, TOL = big
     batch = O.make_synthetic_batch(1, 168, 216, seed=5)
     x = torch.cat([batch['image'] * (1 - batch['mask']), batch['mask']], 1)
@@ -324,7 +325,7 @@ def test_biglama_shape_sweep(big):
 
 
 def test_photo_sized_input(big):
-    """1080 x 1920 (a photo; bottleneck planes 135 x 240: the generic DFT kernels with their one Cooley-Tukey split per length, and 254
+    """1080 x 1920 (a photo; bottleneck planes 135 x 240: the one-launch mixed-radix kernels with 1024 threads, family 2 of lama_fft_route_query, and 254
     pixel tiles per launch, i.e. conv1 riding in the global-branch epilogues) against the oracle, at 1.5x the 512^2 tolerance like
     the other high-resolution cases."""
     cfg, sd, gen, TOL = big

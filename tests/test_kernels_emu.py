@@ -202,7 +202,7 @@ FFT_SIZES = [(16, 16), (32, 32), (64, 64), (32, 64), (64, 16), (128, 32), (128, 
              (9, 14), (35, 30), (22, 26), (1, 16), (3, 2), (49, 56), (67, 40),  # ... 7x2, 5x7 / 2x3x5, primes 11 / 13, degenerate planes, 7x7 / 8x7, a prime height
              (90, 160),                                                       # ... the bottleneck plane of a 720 x 1280 frame (512 threads)
              (53, 24), (20, 59), (61, 67), (106, 12), (9, 118),               # ... large prime factors (the 2 x 2-blocked pair-symmetric first pass, mr_pass_prime1): prime heights / widths, both, 2 x 53, 2 x 59
-             (256, 32), (16, 512), (256, 256)]                                # two-pass LDS path
+             (256, 32), (16, 512), (256, 256)]                                # one workgroup's LDS still holds 256 x 32 and 16 x 512 (one-launch mixed radix since round 6); 256 x 256: the compile-time two-pass pair.  Routes are pinned in tests/test_fft_routes_emu.py
 
 
 @pytest.mark.parametrize('hw', FFT_SIZES, ids=lambda s: f'{s[0]}x{s[1]}')
