@@ -54,12 +54,26 @@ extern "C" {
 /* element type of an activation tensor in HBM */
 #define LAMA_DT_F32 0
 #define LAMA_DT_F16 1 /* IEEE half: BASELINE configs[2] "fp16"; every tensor of a call is fp16 except where an entry says otherwise */
+/* LAMA_DT_SPLIT16 (no new symbol, no version bump): the (hi, lo) 16-bit parts of the call's precision, stored in the order the MFMA
+ * kernels stage them -- fp16 parts under LAMA_PREC_F16X3, bf16 parts under LAMA_PREC_BF16X3: hi = rne16(x), lo = rne16(x - hi), exactly
+ * the values the kernels form from an fp32 tensor while they stage it.  FOUR bytes per logical element (batch_stride keeps counting
+ * logical elements: a buffer sized for fp32 holds the tensor), C % 8 == 0, and per image
+ *     [C / 8][hi | lo][H][W][8 halves]:  part p (0 = hi, 1 = lo) of element (c, y, x) is the 16-bit word at byte
+ *     (((c / 8) * 2 + p) * H * W + y * W + x) * 16 + (c % 8) * 2  behind  (char*)ptr + b * batch_stride * 4.
+ * The lo part is exactly zero (0x0000) for every element whose hi part is a zero or whose x - hi is zero.
+ * Range contract: a CONSUMER of such a tensor does not watch the fp16 range (it never sees the fp32 value) -- whoever WRITES one does:
+ * a kernel that stores a hi part >= 0x7c00 in magnitude (inf, or a NaN that came through) under LAMA_PREC_F16X3 ORs 1 into
+ * *range_flag in the same launch; it watches what it stores and nothing else.
+ * Accepted by lama_conv2d_fwd only, under the two split precisions: as y of the 7x7 stem kernel (cin <= 4, 40 .. 64 output channels,
+ * reflect pad 3) and as x and / or y of the 3x3 stride-2 convolutions (pad 1), without resid; x2, resid and fuse1_y never have this
+ * type.  Every other combination, and every other entry point, returns LAMA_ERR_UNSUPPORTED with nothing launched. */
+#define LAMA_DT_SPLIT16 2
 
 typedef struct lama_tensor {
     void* ptr;            /* device pointer to element (0,0,0,0) of the view; NULL = absent          */
     int64_t batch_stride; /* ELEMENTS between consecutive images                                     */
     int32_t C, H, W;
-    int32_t dtype;        /* LAMA_DT_F32 (0) or LAMA_DT_F16                                          */
+    int32_t dtype;        /* LAMA_DT_F32 (0), LAMA_DT_F16 or LAMA_DT_SPLIT16 (its own layout, above) */
 } lama_tensor;
 
 /* One fused convolution launch:

@@ -18,7 +18,7 @@ PREC_F32, PREC_BF16X3, PREC_F16X3, PREC_F16 = 0, 1, 2, 3
 CONV_COOPERATIVE = 1
 CONV_DEFER_OUT = 2          # lama_winograd_conv3x3_fwd: the GEMM launch only (include/lama_hip.h)
 CONV_SIBLINGS_SHIFT = 8     # (v109) bits 8..10: log2 of the number of sibling launches that share the chip with this one
-DT_F32, DT_F16 = 0, 1
+DT_F32, DT_F16, DT_SPLIT16 = 0, 1, 2      # LAMA_DT_*
 POOL_MAX, POOL_AVG_EXCLUDE_PAD = 0, 1      # lama_pool3x3_fwd mode
 ABI_VERSION = 112      # LAMA_HIP_VERSION of include/lama_hip.h
 PREC_NAMES = {'f32': PREC_F32, 'bf16x3': PREC_BF16X3, 'f16x3': PREC_F16X3, 'f16': PREC_F16}
@@ -83,6 +83,43 @@ def view(t: Optional[torch.Tensor], c0: int = 0, c: Optional[int] = None) -> Ten
     if c0 < 0 or c <= 0 or c0 + c > Ct:
         raise LamaError('channel slice out of range')
     return Tensor4(t.data_ptr() + t.element_size() * c0 * H * W, Ct * H * W, c, H, W, DT_F16 if t.dtype == torch.float16 else DT_F32)
+
+
+def view_split(t: torch.Tensor) -> Tensor4:
+    """lama_tensor view of a whole contiguous fp32 [B, C, H, W] buffer that holds LAMA_DT_SPLIT16 parts (include/lama_hip.h: four bytes per
+    logical element, per image [C / 8][hi | lo][H][W][8 halves]; no channel slices)."""
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or t.shape[1] % 8 != 0:
+        raise LamaError(f'expected a contiguous fp32-sized NCHW buffer with C % 8 == 0, got {t.dtype} {tuple(t.shape)}')
+    B, Ct, H, W = t.shape
+    return Tensor4(t.data_ptr(), Ct * H * W, Ct, H, W, DT_SPLIT16)
+
+
+def _split16_part_dtype(precision: int) -> torch.dtype:
+    if precision not in (PREC_F16X3, PREC_BF16X3):
+        raise LamaError('LAMA_DT_SPLIT16 exists for PREC_F16X3 / PREC_BF16X3 only')
+    return torch.float16 if precision == PREC_F16X3 else torch.bfloat16
+
+
+def split16_pack(x: torch.Tensor, precision: int) -> torch.Tensor:
+    """fp32 [B, C, H, W] -> the LAMA_DT_SPLIT16 image of it (an fp32-typed buffer of the same shape for view_split): hi = rne16(x),
+    lo = rne16(x - hi) in the part type of ``precision``.  Host-side helper for tests and tools (torch ops on x's device)."""
+    dt = _split16_part_dtype(precision)
+    B, Ct, H, W = x.shape
+    if Ct % 8 != 0:
+        raise LamaError('LAMA_DT_SPLIT16 needs C % 8 == 0')
+    x = x.float()
+    hi = x.to(dt)
+    lo = (x - hi.float()).to(dt)
+    parts = torch.stack((hi, lo), 0).view(torch.int16).view(2, B, Ct // 8, 8, H, W)
+    return parts.permute(1, 2, 0, 4, 5, 3).contiguous().view(torch.float32).view(B, Ct, H, W)
+
+
+def split16_unpack(buf: torch.Tensor, precision: int):
+    """The (hi, lo) parts of a LAMA_DT_SPLIT16 buffer (as view_split takes it), each [B, C, H, W] in the part type of ``precision``."""
+    dt = _split16_part_dtype(precision)
+    B, Ct, H, W = buf.shape
+    parts = buf.contiguous().view(torch.int16).view(B, Ct // 8, 2, H, W, 8).permute(2, 0, 1, 5, 3, 4).contiguous().view(2, B, Ct, H, W)
+    return parts[0].view(dt), parts[1].view(dt)
 
 
 class LamaLib:

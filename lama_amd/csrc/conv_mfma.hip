@@ -647,7 +647,16 @@ static int conv2d_impl(void* stream, const lama_conv2d_args* a, const LamaTileLi
     if (!a || !tensor_ok(a->x) || !tensor_ok(a->y) || !a->w_packed || a->batch <= 0) return LAMA_ERR_BAD_ARG;
     if (a->precision != LAMA_PREC_F32 && a->precision != LAMA_PREC_BF16X3 && a->precision != LAMA_PREC_F16X3 && a->precision != LAMA_PREC_F16)
         return LAMA_ERR_UNSUPPORTED;
-    {   // element types: fp16 tensors only with LAMA_PREC_F16 (and LAMA_PREC_F16 only with them: at least x or y is fp16)
+    const bool xs = a->x.dtype == LAMA_DT_SPLIT16, ys = a->y.dtype == LAMA_DT_SPLIT16;
+    if ((a->x2.ptr && a->x2.dtype == LAMA_DT_SPLIT16) || (a->resid.ptr && a->resid.dtype == LAMA_DT_SPLIT16) ||
+        (a->fuse1_w && a->fuse1_y.dtype == LAMA_DT_SPLIT16))
+        return LAMA_ERR_UNSUPPORTED;
+    if (xs || ys) {   // pre-split tensors: the stem and the stride-2 convs of the split precisions only (lama_hip.h), decided by the back end
+        if (a->precision != LAMA_PREC_BF16X3 && a->precision != LAMA_PREC_F16X3) return LAMA_ERR_UNSUPPORTED;
+        if (tl || a->transposed || a->x2.ptr || a->resid.ptr || a->fuse1_w) return LAMA_ERR_UNSUPPORTED;
+        if ((xs && a->x.C % 8 != 0) || (ys && a->y.C % 8 != 0)) return LAMA_ERR_UNSUPPORTED;
+        if ((!xs && a->x.dtype != LAMA_DT_F32) || (!ys && a->y.dtype != LAMA_DT_F32)) return LAMA_ERR_UNSUPPORTED;
+    } else {   // element types: fp16 tensors only with LAMA_PREC_F16 (and LAMA_PREC_F16 only with them: at least x or y is fp16)
         const bool xh = a->x.dtype == LAMA_DT_F16, yh = a->y.dtype == LAMA_DT_F16;
         if ((a->x.dtype != LAMA_DT_F32 && !xh) || (a->y.dtype != LAMA_DT_F32 && !yh)) return LAMA_ERR_BAD_ARG;
         if (a->x2.ptr && a->x2.dtype != LAMA_DT_F32 && a->x2.dtype != LAMA_DT_F16) return LAMA_ERR_BAD_ARG;

@@ -62,6 +62,7 @@ typedef __bf16 cb_half_t;
 typedef cb_half_t bf16x2 __attribute__((ext_vector_type(2)));   // (historic names: 2 / 8 x the 16-bit operand type)
 typedef cb_half_t bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace CB_NAME(cbns) {   // the two instantiations of this body must not share type / template names
 
@@ -71,7 +72,9 @@ namespace CB_NAME(cbns) {   // the two instantiations of this body must not shar
 // element types of a launch (lama_tensor.dtype of x / x2 and of y / resid): LAMA_PREC_F16 runs on the f16 back end only
 // bit 0: x is fp16, bit 1: y / resid are fp16, bit 2: x2 is fp16 (the resnet blocks keep their residual stream fp32, everything
 // else of the fp16 path is fp16 -- so the two big convs of a block read or write one fp32 tensor)
-enum { CB_IO_F32 = 0, CB_IO_F16_F32 = 1, CB_IO_F32_F16 = 2, CB_IO_F16 = 3, CB_IO_X2H = 4 };
+// bits 3 / 4 (3-term split precisions only): x / y is LAMA_DT_SPLIT16 -- pre-split (hi, lo) parts in staging order (lama_hip.h); only the
+// stem kernel (y) and the 4 x 1 stride-2 launch (x, y) know them, nothing else is ever launched with them
+enum { CB_IO_F32 = 0, CB_IO_F16_F32 = 1, CB_IO_F32_F16 = 2, CB_IO_F16 = 3, CB_IO_X2H = 4, CB_IO_XS = 8, CB_IO_YS = 16 };
 
 struct CbSeg {
     const float* x;
@@ -1092,6 +1095,17 @@ int CB_NAME(lama_cb_conv2d_fwd)(hipStream_t stream, const lama_conv2d_args* a, i
     if (has2 && pl.mode) return LAMA_ERR_UNSUPPORTED;
     const int io = (a->x.dtype == LAMA_DT_F16 ? 1 : 0) | (a->y.dtype == LAMA_DT_F16 ? 2 : 0) | ((has2 && a->x2.dtype == LAMA_DT_F16) ? CB_IO_X2H : 0);   // CB_IO_*
     if ((io != CB_IO_F32) != (CB_HALF != 0)) return LAMA_ERR_UNSUPPORTED;   // fp16 tensors <-> the LAMA_PREC_F16 translation unit
+    {   // LAMA_DT_SPLIT16 (validated by lama_conv2d_fwd: split precisions, no x2 / resid / fuse1): the two dedicated kernels or nothing
+        const int ios = (a->x.dtype == LAMA_DT_SPLIT16 ? CB_IO_XS : 0) | (a->y.dtype == LAMA_DT_SPLIT16 ? CB_IO_YS : 0);
+        if (ios) {
+            if (CB_HALF || has2 || a->transposed) return LAMA_ERR_UNSUPPORTED;
+            if (ios == CB_IO_YS) {
+                const int rc = stem_try_launch(stream, a, pl, Ho, Wo, ios);
+                if (rc != LAMA_ERR_UNSUPPORTED) return rc;
+            }
+            return cw_try_launch(stream, a, pl, nullptr, Ho, Wo, ios);
+        }
+    }
     {   // bottleneck shapes: weights-in-registers kernel (conv_wreg_dev.inc)
         int rc = cw_try_launch(stream, a, pl, has2 ? &pl2 : nullptr, Ho, Wo, io);
         if (rc != LAMA_ERR_UNSUPPORTED) return rc;

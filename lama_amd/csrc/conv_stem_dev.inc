@@ -48,8 +48,12 @@ __device__ __forceinline__ void stem_pack2(float a, float b, unsigned& pa, unsig
 
 // HO (f16 back end, LAMA_PREC_F16): the output is fp16 (half of this kernel's HBM traffic, which is all stores) and the contraction is
 // one product per MAC (hi parts only).
-template <bool HO = false>
+// YS (3-term split only): the output is LAMA_DT_SPLIT16 -- the (hi, lo) parts the next stride-2 conv would form while it stages, stored in
+// its staging order, [channel octet][hi | lo][H][W][8 halves] (four bytes per element, as fp32); this kernel then watches the range of what
+// it stores (lama_hip.h).  M % 8 == 0 (the host checks).
+template <bool HO = false, bool YS = false>
 __global__ __launch_bounds__(256, 2) void CB_NAME(stem7_ws_kernel)(StemParams p) {
+    static_assert(!(HO && YS), "pre-split output: the 3-term split precisions only");
     constexpr int ESO = HO ? 2 : 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = LAMA_WAVE_UNIFORM(tid >> 6);
     const int F = wave & 1, half = wave >> 1;
@@ -205,10 +209,31 @@ __global__ __launch_bounds__(256, 2) void CB_NAME(stem7_ws_kernel)(StemParams p)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) ov[r] = tanhf(ov[r]);
             }
+            if constexpr (YS) {
+                // registers 4 g .. 4 g + 3 = channels 4 khalf .. 4 khalf + 3 of octet 4 F + g: 8 bytes of the pixel's hi slot, 8 of its lo slot
+                // (a wave stores 512 contiguous bytes per plane).  Split, then the watch of what IS stored (a ragged last segment's lanes past W and
+                // octets past M are not), then the stores.
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if constexpr (HO) LAMA_BUF_STORE_B16(yres, __builtin_bit_cast(unsigned short, (_Float16)ov[r]), eoff, ((r & 3) + 8 * (r >> 2)) * HW * ESO);
-                else LAMA_BUF_STORE_B32(yres, __builtin_bit_cast(unsigned, ov[r]), eoff, ((r & 3) + 8 * (r >> 2)) * HW * ESO);
+                for (int g = 0; g < 4; ++g) {
+                    unsigned h0, h1, l0, l1;
+                    cb_split2(ov[4 * g], ov[4 * g + 1], h0, l0);
+                    cb_split2(ov[4 * g + 2], ov[4 * g + 3], h1, l1);
+                    const int oct = F * 4 + g;
+                    const bool stored = px < W && oct * 8 < p.M;
+                    if (stored) {
+                        cb_range_watch(h0, rw);
+                        cb_range_watch(h1, rw);
+                    }
+                    const int voff = stored ? (y * W + px) * 16 + 8 * khalf : 0x7ffffff0;   // (not stored: past the buffer's range, dropped)
+                    LAMA_BUF_STORE_B64(yres, (u32x2{h0, h1}), voff, oct * 2 * HW * 16);
+                    LAMA_BUF_STORE_B64(yres, (u32x2{l0, l1}), voff, (oct * 2 + 1) * HW * 16);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (HO) LAMA_BUF_STORE_B16(yres, __builtin_bit_cast(unsigned short, (_Float16)ov[r]), eoff, ((r & 3) + 8 * (r >> 2)) * HW * ESO);
+                    else LAMA_BUF_STORE_B32(yres, __builtin_bit_cast(unsigned, ov[r]), eoff, ((r & 3) + 8 * (r >> 2)) * HW * ESO);
+                }
             }
         }
         LAMA_WAVE_SYNC();   // the next part refills the window

@@ -68,7 +68,11 @@ struct CwFrag {
 // next, so that the next set's rows 0..3 are requested while the current set's ky = 1, 2 taps still run on rows 1..5.
 // NU: staging units (8 channels of one patch pixel) per thread and chunk -- 2 for the stride-1 tiles, 5 for the (2 TH + 1) x (2 TW + 1)
 // patch of a stride-2 3x3 (columns parity-split in LDS, so that the B fragments of every tap stay 32 consecutive 16-byte slots)
-template <int T, int KSC, int WMV, int KG, int ABL = 0, int SCH = 2, bool HF = false, bool HI = HF, bool ROLL = false, int NU = 2>
+// XS: this segment's input tensor is LAMA_DT_SPLIT16 (3-term split only): the producer stored the (hi, lo) parts in staging order, per image
+// [channel octet][hi | lo][H][W][8 halves], so a unit is two 16-byte buffer loads and two 16-byte LDS writes -- no conversion, no split, no range
+// watch (the producer watched what it stored); padding, the parity split of the columns and the dump slot are untouched, and the LDS image is
+// the one the fp32 form gives bit for bit.
+template <int T, int KSC, int WMV, int KG, int ABL = 0, int SCH = 2, bool HF = false, bool HI = HF, bool ROLL = false, int NU = 2, bool XS = false>
 __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0, int gx0, int TWlog, char* pbuf0, int pbytes,
                                            f32x16 (&acc)[4], unsigned& rw, long long* trace = nullptr) {
     using S = CwShape<T, KSC, WMV, KG>;
@@ -78,6 +82,8 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
     constexpr bool BDB = S::BDB;
     constexpr int BKC = 16 * KSC;
     constexpr int ES = HI ? 2 : 4;   // bytes per activation element
+    static_assert(!XS || (!HF && !HI), "pre-split input: the 3-term split precisions only");
+    constexpr int NLD = XS ? 2 * NU : 8 * NU;   // patch requests per thread and chunk
     const int tid = threadIdx.x, lane = tid & 63, wave = LAMA_WAVE_UNIFORM(tid >> 6);
     const int kg = KG == 1 ? 0 : wave / WMV;
     const int khalf = lane >> 5, l31 = lane & 31;
@@ -104,7 +110,8 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
             if (iy >= 0 && ix >= 0) { so = iy * s.W + ix; ok = 1; }
             lo = (q * s.npix + py * s.PWs + (s.PWh ? (px & 1) * s.PWh + (px >> 1) : px)) * 16;
         }
-        ubase[i] = (q * 8 * HW + so) * ES;   // byte offset inside a chunk; always in bounds (zero padding is applied at write time)
+        // byte offset inside a chunk; always in bounds (zero padding is applied at write time).  XS: the hi plane of octet q, the lo plane HW * 16 behind
+        ubase[i] = XS ? (q * 2 * HW + so) * 16 : (q * 8 * HW + so) * ES;
         lds_off[i] = lo;
         uvalid[i] = ok;
     }
@@ -113,6 +120,20 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
     float preg[PFD][NU][8];   // HF: the raw 16-bit patterns (zero-extended)
     auto load_units = [&](int ch, auto slot_tag) {
         constexpr int SL = decltype(slot_tag)::value;
+        if constexpr (XS) {   // a chunk is BKC channels = BKC / 8 octets of 2 * HW * 16 bytes = the same BKC * HW * 4 bytes as in fp32
+#pragma unroll
+            for (int hl = 0; hl < 2; ++hl)
+#pragma unroll
+                for (int i = 0; i < NU; ++i) {
+                    const u32x4 v = __builtin_bit_cast(u32x4, LAMA_BUF_LOAD_B128(xres, ubase[i], ch * BKC * HW * 4 + hl * HW * 16));
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const unsigned ve = v[e];   // (a named scalar: __builtin_bit_cast of the vector ELEMENT expression reads element 0 for every e)
+                        preg[SL][i][4 * hl + e] = __builtin_bit_cast(float, ve);
+                    }
+                }
+            return;
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int so = (ch * BKC + e) * HW * ES;
@@ -130,7 +151,10 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
             unsigned hh[4], ll[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if constexpr (HI) {
+                if constexpr (XS) {
+                    hh[e] = __builtin_bit_cast(unsigned, preg[SL][i][e]);
+                    ll[e] = __builtin_bit_cast(unsigned, preg[SL][i][4 + e]);
+                } else if constexpr (HI) {
                     hh[e] = __builtin_bit_cast(unsigned, preg[SL][i][2 * e]) | (__builtin_bit_cast(unsigned, preg[SL][i][2 * e + 1]) << 16);
                     cb_range_watch(hh[e], rw);
                     ll[e] = 0u;
@@ -270,7 +294,7 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
             }
             if constexpr (SCH == 1) __builtin_amdgcn_sched_barrier(0);
             if constexpr (SCH == 2 && !(ABL & 8) && !HF) {
-                constexpr int NVM = ((ABL & 1) ? 0 : 2) + (LDU ? 8 * NU : 0);                 // VMEM reads of this region
+                constexpr int NVM = ((ABL & 1) ? 0 : 2) + (LDU ? NLD : 0);                    // VMEM reads of this region
                 auto grp = [&](auto i_tag) {
                     constexpr int i = decltype(i_tag)::value;
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                     // MFMA
@@ -374,7 +398,7 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
                 for (int j = 0; j < 4; ++j) acc[j] = CB_MFMA(a_lo, rows[slot(ky + j)].h, acc[j], 0, 0, 0);
             }
             if constexpr (SCH == 2 && !HF && !(ABL & 8)) {
-                constexpr int NVM = ((ABL & 1) ? 0 : 2) + (LDU ? 8 * NU : 0);
+                constexpr int NVM = ((ABL & 1) ? 0 : 2) + (LDU ? NLD : 0);
                 auto grp = [&](auto i_tag) {
                     constexpr int i = decltype(i_tag)::value;
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                     // MFMA
@@ -420,8 +444,11 @@ __device__ __forceinline__ void cw_segment(const CbSeg& s, int F, int b, int gy0
 // HF: LAMA_PREC_F16 (one product per MAC); HI1 / HI2 / HO: x, x2 and y / resid are fp16 (any mix: the resnet blocks keep their
 // residual stream fp32 and everything else fp16)
 template <int T1, int KSC1, int T2, int KSC2, int WMV = 4, int KG = 2, int ABL = 0, int SCH = 2, bool HF = false, bool HI1 = HF, bool HI2 = HF,
-          bool HO = HF, bool ROLL = false, int NU = 2, bool FUSE1 = false>
+          bool HO = HF, bool ROLL = false, int NU = 2, bool FUSE1 = false, bool XS = false, bool YS = false>
 __global__ __launch_bounds__(64 * WMV * KG, (WMV * KG == 4) ? 2 : 1) void CB_NAME(conv_wr_kernel)(CbParams p) {
+    // XS / YS (the 4 x 1 stride-2 launch of the 3-term split): x / y is LAMA_DT_SPLIT16 -- cw_segment stages pre-split units, the epilogue
+    // splits, watches and stores what the next stride-2 conv would otherwise split while it stages
+    static_assert(!(XS || YS) || (KG == 1 && T2 == 0 && !HF && !HO && !FUSE1), "pre-split tensors: plain one-segment launches without K-groups");
     using AT = typename LamaAct<HO>::T;   // element type of resid / y
     const int L = lama_xcd_remap(blockIdx.x, gridDim.x);
     const int mt = L % p.MT;
@@ -452,7 +479,7 @@ __global__ __launch_bounds__(64 * WMV * KG, (WMV * KG == 4) ? 2 : 1) void CB_NAM
     // ABL bit 8 (profiling tools, timing only, results WRONG): waves F >= 6 stream the weight fragments of wave F - 6 -- the SAME number of
     // requests per CU, half the distinct bytes from L2: what a 256-pixel tile shared by two half-row workgroups could gain at best (DESIGN.md 9.2)
     const int Fw = (ABL & 256) ? Fc % 6 : Fc;
-    cw_segment<T1, KSC1, WMV, KG, (ABL & 255), SCH, HF, HI1, ROLL && T1 == 9, NU>(p.s1, Fw, b, gy0, gx0, p.TWlog, lama_smem, p.pbytes, acc, rw, trace);
+    cw_segment<T1, KSC1, WMV, KG, (ABL & 255), SCH, HF, HI1, ROLL && T1 == 9, NU, XS>(p.s1, Fw, b, gy0, gx0, p.TWlog, lama_smem, p.pbytes, acc, rw, trace);
     if constexpr (T2 > 0) cw_segment<T2, KSC2, WMV, KG, (ABL & 65), SCH, HF, HI2>(p.s2, Fw, b, gy0, gx0, p.TWlog, lama_smem, p.pbytes, acc, rw, (ABL & 64) ? trace + 7 : nullptr);
     cb_range_report(rw, p.range_flag);
 
@@ -486,7 +513,9 @@ __global__ __launch_bounds__(64 * WMV * KG, (WMV * KG == 4) ? 2 : 1) void CB_NAM
     };
     auto store_frag = [&](int j, const f32x16& v16, int slot) {   // bias, activation, residual, store
         bool pv;
-        const unsigned lo = (unsigned)(frag_off(j, pv) + kplane);
+        const int po = frag_off(j, pv);
+        const unsigned lo = (unsigned)(po + kplane);
+        [[maybe_unused]] float vs[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int mu = row_u(r);
@@ -495,7 +524,28 @@ __global__ __launch_bounds__(64 * WMV * KG, (WMV * KG == 4) ? 2 : 1) void CB_NAM
             else if (p.act == LAMA_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
             else if (p.act == LAMA_ACT_TANH) v = tanhf(v);
             v += rv[slot][r];
-            if (pv && mu + khalf4 < p.M) (reinterpret_cast<AT*>(p.y) + (long long)b * p.y_bstride + (long long)mu * plane)[lo] = (AT)v;
+            if constexpr (YS) vs[r] = v;
+            else if (pv && mu + khalf4 < p.M) (reinterpret_cast<AT*>(p.y) + (long long)b * p.y_bstride + (long long)mu * plane)[lo] = (AT)v;
+        }
+        if constexpr (YS) {
+            // LAMA_DT_SPLIT16: registers 4 g .. 4 g + 3 are channels 4 khalf .. 4 khalf + 3 of octet 4 F + g -> 8 bytes of the pixel's hi slot and
+            // 8 of its lo slot; the two half-waves fill the 16 bytes, 32 pixels of a tile row are 512 contiguous bytes per plane.  Split, THEN the
+            // watch -- of what is stored and nothing else (lanes of a ragged tile outside the plane hold garbage) --, then plain vector stores.
+            char* const yb = reinterpret_cast<char*>(p.y) + (long long)b * p.y_bstride * 4;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                unsigned h0, h1, l0, l1;
+                cb_split2(vs[4 * g], vs[4 * g + 1], h0, l0);
+                cb_split2(vs[4 * g + 2], vs[4 * g + 3], h1, l1);
+                const int oct = F * 4 + g;
+                if (pv && oct * 8 < p.M) {
+                    cb_range_watch(h0, rw);
+                    cb_range_watch(h1, rw);
+                    char* const d = yb + ((long long)oct * 2 * plane + po) * 16 + 2 * khalf4;
+                    *reinterpret_cast<u32x2*>(d) = u32x2{h0, h1};
+                    *reinterpret_cast<u32x2*>(d + plane * 16) = u32x2{l0, l1};
+                }
+            }
         }
     };
     if constexpr (FUSE1) {
@@ -632,6 +682,7 @@ __global__ __launch_bounds__(64 * WMV * KG, (WMV * KG == 4) ? 2 : 1) void CB_NAM
             else if (j + 1 < 4) load_resid(j + 1, (j + 1) & 1);
             store_frag(j, acc[j], NRV == 1 ? 0 : (j & 1));
         }
+        if constexpr (YS) cb_range_report(rw, p.range_flag);   // the producer-side watch of what this workgroup stored
     } else {
         // K-group exchange (the patch buffers are free after the last barrier): group 0 finishes pixel fragments 0-1, group 1
         // fragments 2-3; each wave hands the other two to its partner (same fragment, other group) as [fragment][r / 4][lane][4 floats]

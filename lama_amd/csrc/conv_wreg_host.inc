@@ -302,8 +302,27 @@ int cw_launch_s2(hipStream_t st, const CbParams& p, int grid, size_t shmem, int 
     if (io == CB_IO_F16) hipLaunchKernelGGL((CB_NAME(conv_wr_kernel)<9, 1, 0, 0, 4, 1, 0, 0, true, true, true, true, false, 5>), dim3(grid), dim3(256), shmem, st, p);
     else hipLaunchKernelGGL((CB_NAME(conv_wr_kernel)<9, 1, 0, 0, 4, 1, 0, 0, true, true, true, false, false, 5>), dim3(grid), dim3(256), shmem, st, p);
 #else
+    if (io & (CB_IO_XS | CB_IO_YS)) {   // LAMA_DT_SPLIT16 on either side: the 4 x 1 geometry only
+        if (io & ~(CB_IO_XS | CB_IO_YS)) return LAMA_ERR_UNSUPPORTED;
+#define CW_S2_SPLIT(xs, ys) hipLaunchKernelGGL((CB_NAME(conv_wr_kernel)<9, 1, 0, 0, 4, 1, 0, 2, false, false, false, false, false, 5, false, xs, ys>), dim3(grid), dim3(256), shmem, st, p)
+        if (io == (CB_IO_XS | CB_IO_YS)) CW_S2_SPLIT(true, true);
+        else if (io == CB_IO_XS) CW_S2_SPLIT(true, false);
+        else CW_S2_SPLIT(false, true);
+#undef CW_S2_SPLIT
+        LAMA_CHECK_LAUNCH();
+        return LAMA_OK;
+    }
     if (io != CB_IO_F32) return LAMA_ERR_UNSUPPORTED;
     static const int geo = lama_env_int("LAMA_CW_S2", 1);   // 2 (profiling tools): one 8-wave workgroup per CU, K split between two wave groups
+#if defined(LAMA_PROFILING)
+    if (CB_F16 && geo != 2) {   // profiling tools only: timing ablations of the patch staging (results wrong; profiles/presplit_outer.txt)
+        static const int abl = lama_env_int("LAMA_CW_ABLATE", 0);
+#define CW_ABL_S2(v) \
+    if (abl == v) { hipLaunchKernelGGL((CB_NAME(conv_wr_kernel)<9, 1, 0, 0, 4, 1, v, 2, false, false, false, false, false, 5>), dim3(grid), dim3(256), shmem, st, p); LAMA_CHECK_LAUNCH(); return LAMA_OK; }
+        CW_ABL_S2(4) CW_ABL_S2(16) CW_ABL_S2(32)
+#undef CW_ABL_S2
+    }
+#endif
     if (geo == 2) hipLaunchKernelGGL((CB_NAME(conv_wr_kernel)<9, 2, 0, 0, 4, 2, 0, 2, false, false, false, false, false, 5>), dim3(grid), dim3(512), shmem, st, p);
     else hipLaunchKernelGGL((CB_NAME(conv_wr_kernel)<9, 1, 0, 0, 4, 1, 0, 2, false, false, false, false, false, 5>), dim3(grid), dim3(256), shmem, st, p);
 #endif
@@ -345,6 +364,9 @@ int cw_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& p
     if (!cw_enabled() || a->transposed || (a->stride != 1 && a->stride != 2) || pl.mode != 0 || pl.nseg != 1) return LAMA_ERR_UNSUPPORTED;
     const bool s2 = a->stride == 2;   // the three downsampling convs: same kernel, parity-split patch columns, five staging units per thread
     if (s2 && (pl.T[0] != 9 || pl2 || a->pad != 1)) return LAMA_ERR_UNSUPPORTED;
+    const bool split_io = (io & (CB_IO_XS | CB_IO_YS)) != 0;   // LAMA_DT_SPLIT16 tensors: the stride-2 launch only, whole octets, no residual
+    if (split_io && (!s2 || CB_HALF || a->resid.ptr || a->x.C % 8 != 0 || pl.rows % 8 != 0 || pl.rows != a->y.C)) return LAMA_ERR_UNSUPPORTED;
+    if (split_io && ((long long)a->x.C * a->x.H * a->x.W >= (1ll << 29) || (long long)a->y.C * Ho * Wo >= (1ll << 29))) return LAMA_ERR_UNSUPPORTED;   // 32-bit byte offsets
     const int T1 = pl.T[0];
     int twlog3 = 5;
     const long long tiles_img = (T1 == 9 && !s2) ? cw_pick_tile(Wo, Ho, a->batch, a->flags, &twlog3) : lama_ceil_div64((long long)Ho * Wo, 128);   // 128-pixel tiles of one image
@@ -358,7 +380,7 @@ int cw_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& p
 #else
     static const int s2geo = lama_env_int("LAMA_CW_S2", 1);
 #endif
-    if (s2 && s2geo != 2) KG = 1;
+    if (s2 && (s2geo != 2 || split_io)) KG = 1;
     // stride-1 3x3 without second operand (the local conv), geometry by launch size (workgroups of 128 pixels x 128 rows):
     //   >= 512: two 4-wave workgroups per CU (16-channel chunks) instead of one 8-wave K-split workgroup: the launch is one or more full
     //           rounds either way, but the two workgroups of a CU run out of phase.  Kernel alone 426 -> 413 us at 4 x 1024^2; with the
@@ -589,7 +611,8 @@ int ct_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& p
 // Stem (7x7, cin <= 4, 33..64 output channels, reflect pad 3): conv_stem_dev.inc.  LAMA_STEM_WS: 0 disables it (A/B runs of the
 // profiling tools), 2 takes it whatever the launch size (emulator tests); read once.
 int stem_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan& pl, int Ho, int Wo, int io) {
-    if (io != CB_IO_F32 && io != CB_IO_F32_F16) return LAMA_ERR_UNSUPPORTED;
+    if (io != CB_IO_F32 && io != CB_IO_F32_F16 && io != CB_IO_YS) return LAMA_ERR_UNSUPPORTED;
+    if (io == CB_IO_YS && pl.rows % 8 != 0) return LAMA_ERR_UNSUPPORTED;   // LAMA_DT_SPLIT16: whole channel octets
     static const int mode = lama_env_int("LAMA_STEM_WS", 1);
     if (mode == 0 || pl.mode != 1 || pl.mft != 2 || a->transposed || a->stride != 1 || a->pad != 3 || a->pad_mode != LAMA_PAD_REFLECT ||
         a->resid.ptr || a->x.H < 4 || a->x.W < 4)
@@ -628,8 +651,9 @@ int stem_try_launch(hipStream_t stream, const lama_conv2d_args* a, const CbPlan&
     if (io != CB_IO_F32_F16) return LAMA_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(CB_NAME(stem7_ws_kernel)<true>, dim3(grid), dim3(256), STEM_LDS_BYTES, stream, p);
 #else
-    if (io != CB_IO_F32) return LAMA_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(CB_NAME(stem7_ws_kernel)<false>, dim3(grid), dim3(256), STEM_LDS_BYTES, stream, p);
+    if (io == CB_IO_YS) hipLaunchKernelGGL((CB_NAME(stem7_ws_kernel)<false, true>), dim3(grid), dim3(256), STEM_LDS_BYTES, stream, p);
+    else if (io != CB_IO_F32) return LAMA_ERR_UNSUPPORTED;
+    else hipLaunchKernelGGL(CB_NAME(stem7_ws_kernel)<false>, dim3(grid), dim3(256), STEM_LDS_BYTES, stream, p);
 #endif
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;

@@ -134,6 +134,9 @@ class _Exec:
         self.winograd = True              # the local 3x3 conv of a two-branch FFC layer as Winograd F(2x2, 3x3) where the shape allows (wino_dev.inc)
         self.local_first = True           # capture order at the fork: the first successor of a hipGraph node stays on its queue
         self.cooperative_serial = False   # tests: the one-stream launch order with the overlapped order's kernel geometry (bit-equal results)
+        # the stem kernel that can write LAMA_DT_SPLIT16 takes launches from this many 32-pixel row segments on (stem_try_launch); 0 with a
+        # library that takes it whatever the size (emulator / forced-path tests) -- FFCResNetGenerator.presplit_outer
+        self.presplit_stem_min_tiles = 4096
 
     @property
     def lib(self) -> L.LamaLib:
@@ -384,8 +387,8 @@ class _PlanGenerator(_HipModule):
     def drop_plan(self, shape, device) -> None:
         """Free the activation buffers / captured graph of one input shape (predict.py drops a bucket's plan when it is done)."""
         key = self._plan_key(shape, device)
-        self._plans.pop(key, None)
-        self._plans.pop(key + ('sparse_tail',), None)
+        for k in [k for k in self._plans if k[:len(key)] == key]:      # the dense plan and its variants (sparse tail, fp32 outer buffers)
+            del self._plans[k]
 
     def input_buffer(self, shape, device) -> torch.Tensor:
         """The tensor this shape's plan READS its input from (the captured hipGraph's static input when ``use_graph``): a caller that produces
@@ -698,7 +701,7 @@ class FFC(_HipModule):
     # -- launch --------------------------------------------------------------------------------------
     def launch(self, pk: dict, act: int, src: torch.Tensor, dst: torch.Tensor, scratch: Optional[dict],
                resid: Optional[torch.Tensor] = None, extra_pad: int = 0, side: Optional['torch.cuda.Stream'] = None,
-               x1_ready: bool = False, fuse_next: Optional['SpectralTransform'] = None) -> bool:
+               x1_ready: bool = False, fuse_next: Optional['SpectralTransform'] = None, split=(False, False)) -> bool:
         """src [B, in_cl+in_cg, H, W] -> dst [B, out_cl+out_cg, Ho, Wo] (x_l | x_g channel-contiguous), as 1 launch (no global
         input) or 6 launches (conv1x1, rfft2, spectral conv1x1, irfft2+add, fused local conv, fused global conv).
 
@@ -709,15 +712,19 @@ class FFC(_HipModule):
 
         ``x1_ready``: scratch['x1'] already holds conv1 of this layer (written by the previous layer's global launch).
         ``fuse_next``: the SpectralTransform of the NEXT layer: its conv1 rides in the epilogue of this layer's global launch
-        (lama_conv2d_args.fuse1_*).  Returns True when it did (the next layer then passes x1_ready=True)."""
+        (lama_conv2d_args.fuse1_*).  Returns True when it did (the next layer then passes x1_ready=True).
+        ``split`` = (src, dst) hold LAMA_DT_SPLIT16 parts instead of fp32 (layers without a global input only; FFCResNetGenerator.presplit_outer)."""
         f, ex, prec = self, self._exec, self.precision
         B = src.shape[0]
         st = ex.stream(src)
         pad = f.padding + extra_pad
         if f.in_cg == 0:
-            ex.conv2d(L.view(src), pk['w_all'], L.view(dst), B, f.kernel_size, f.stride, pad, L.PAD_REFLECT, False, pk['b_all'],
+            ex.conv2d(L.view_split(src) if split[0] else L.view(src), pk['w_all'], L.view_split(dst) if split[1] else L.view(dst), B,
+                      f.kernel_size, f.stride, pad, L.PAD_REFLECT, False, pk['b_all'],
                       act, None if resid is None else L.view(resid), precision=prec, stream=st)
             return False
+        if split[0] or split[1]:
+            raise LamaError('LAMA_DT_SPLIT16 tensors: layers without a global input only')
         cl, cg, ocl, ocg = f.in_cl, f.in_cg, f.out_cl, f.out_cg
         spec = f.convg2g
         # (not with the join-free chain of local convs, SidePipe: consecutive layers' local convs may overlap and share scratch['wino'])
@@ -861,7 +868,7 @@ class FFC_BN_ACT(_HipModule):
     # -- launch --------------------------------------------------------------------------------------
     def run(self, src: torch.Tensor, dst: torch.Tensor, scratch: Optional[dict], resid: Optional[torch.Tensor] = None,
             extra_pad: int = 0, side: Optional['torch.cuda.Stream'] = None, x1_ready: bool = False,
-            fuse_next: Optional['FFC_BN_ACT'] = None) -> bool:
+            fuse_next: Optional['FFC_BN_ACT'] = None, split=(False, False)) -> bool:
         f = self.ffc
         if f.in_cg and self._packed is not None and (f.convg2g._packed or {}).get('fused_scale') != id(self._packed.get('_sg')):
             self._packed = None   # a stand-alone SpectralTransform.forward / FFC.forward re-packed conv2 without bn_g
@@ -869,7 +876,7 @@ class FFC_BN_ACT(_HipModule):
         if fuse_next is not None and fuse_next.ffc.in_cg:
             fuse_next._pack()                                  # its conv1 weights must exist before they can ride along
             nxt = fuse_next.ffc.convg2g
-        return f.launch(self._pack(), self._act, src, dst, scratch, resid, extra_pad, side, x1_ready, nxt)
+        return f.launch(self._pack(), self._act, src, dst, scratch, resid, extra_pad, side, x1_ready, nxt, split=split)
 
     def out_shape(self, src_shape, extra_pad: int = 0):
         return self.ffc.out_shape(src_shape, extra_pad)
@@ -1193,6 +1200,12 @@ class FFCResNetGenerator(_PlanGenerator):
         # sparse-tail plans (``sparse_tail``): rows per head segment.  The host cannot know how many segments a mask lists, so the parts are small:
         # 16 rows pay 7 window rows each, and a listed segment covers little that nobody needs
         self.tail_head_rs = 16
+        # Fused plans under the two 3-term split precisions: a stem / stride-2 output whose ONLY reader is the next stride-2 conv is stored as
+        # LAMA_DT_SPLIT16 -- the (hi, lo) parts that conv would form while it stages, in its staging order (big-lama: a0, a1, a2) -- where the
+        # dedicated kernels take both launches (_presplit_edges; the output that becomes the (x_l | x_g) state stays fp32).  Bit-identical
+        # results.  False keeps every buffer fp32; layer-by-layer ``model[i]`` calls, probe.py, the refinement path, PREC_F32 / PREC_F16 and the
+        # regular / dilated generators always do.  Part of the plan cache's key.
+        self.presplit_outer = True
         super().train(False)
 
     # ------------------------------------------------------------------------------------------------
@@ -1310,11 +1323,49 @@ class FFCResNetGenerator(_PlanGenerator):
             else:
                 scratch['ws'] = wn[:ws.numel()]
         side = torch.cuda.Stream(device=device) if (self.overlap_streams and not serial and not one_stream and torch.device(device).type == 'cuda') else None
-        return dict(steps=steps, bufs=bufs, scratch=scratch, out=cur, graph=None, static_in=None, side=side,
+        return dict(steps=steps, bufs=bufs, scratch=scratch, out=cur, graph=None, static_in=None, side=side, split=self._presplit_edges(steps, bufs, shape),
                     tail=self._plan_tail(steps, bufs, tuple(shape), device) if self._sparse() else None,
                     fuse=self.fuse_conv1 or (serial and self.fuse_conv1 is not False and self.fuse_conv1_serial))
 
     has_sparse_tail = True
+
+    def _cache_key(self, shape, device):
+        key = super()._cache_key(shape, device)
+        return key if self.presplit_outer else key + ('fp32_outer',)
+
+    def _presplit_edges(self, steps, bufs, shape) -> frozenset:
+        """``presplit_outer``: the names of the plan buffers that hold LAMA_DT_SPLIT16 parts instead of fp32.  An edge qualifies when its buffer
+        is written by an 'ffc' step without a global branch on either side and read by exactly one step, the NEXT one, a 3 x 3 stride-2 'ffc'
+        step without a global input -- and when the dedicated kernels take both launches: the conditions below are those of stem_try_launch /
+        cw_try_launch (conv_wreg_host.inc); a launch they refuse all the same raises (LAMA_ERR_UNSUPPORTED), it never falls back silently."""
+        if not self.presplit_outer or self.precision not in (L.PREC_F16X3, L.PREC_BF16X3):
+            return frozenset()
+        ex = self._exec
+
+        def s2_conv(st, src_shape):          # the 4 x 1 weights-in-registers launch of the stride-2 convs
+            f, (_, C, H, W) = st[1].ffc, src_shape
+            return (f.in_cg == 0 and f.kernel_size == 3 and f.stride == 2 and f.padding + st[4] == 1 and C % 32 == 0
+                    and f.out_cl + f.out_cg >= 96 and (f.out_cl + f.out_cg) % 8 == 0 and C * H * W < (1 << 29))
+
+        def stem(st, src_shape, dst_shape):  # stem7_ws_kernel
+            f, (B, C, _, _), (_, M, Ho, Wo) = st[1].ffc, src_shape, dst_shape
+            return (f.in_cg == 0 and f.kernel_size == 7 and f.stride == 1 and f.padding + st[4] == 3 and C <= 4 and 33 <= M <= 64 and M % 8 == 0
+                    and Ho >= 4 and Wo >= 4 and 64 * Ho * Wo < (1 << 29) and B * Ho * ((Wo + 31) // 32) >= ex.presplit_stem_min_tiles)
+
+        def shape_of(name):
+            return tuple(shape) if name == 'in' else tuple(bufs[name].shape)
+
+        split = set()
+        for i in range(len(steps) - 1):
+            p, c = steps[i], steps[i + 1]
+            if p[0] != 'ffc' or c[0] != 'ffc' or c[2] != p[3] or p[1].ffc.out_cg or sum(1 for st in steps if st[2] == p[3]) != 1:
+                continue
+            ps, ds = shape_of(p[2]), shape_of(p[3])
+            if ds[1] * ds[2] * ds[3] >= (1 << 29) or not s2_conv(c, ds):
+                continue
+            if stem(p, ps, ds) or s2_conv(p, ps):
+                split.add(p[3])
+        return frozenset(split)
 
     def _plan_tail(self, steps, bufs, shape, device) -> Optional[dict]:
         """The sparse tail of a plan: the head and the run of upsamplings in front of it, with the work lists their launches walk.
@@ -1368,7 +1419,8 @@ class FFCResNetGenerator(_PlanGenerator):
             kind = st[0]
             if kind == 'ffc':
                 _, lay, s, d, pad = st
-                lay.run(B(s), B(d), plan['scratch'] if lay.ffc.in_cg else None, None, pad, side=plan['side'])
+                sp = plan.get('split') or ()
+                lay.run(B(s), B(d), plan['scratch'] if lay.ffc.in_cg else None, None, pad, side=plan['side'], split=(s in sp, d in sp))
                 x1_ready = False
             elif kind == 'res':
                 _, lay, s, t, d = st

@@ -2,7 +2,9 @@
 """Timings of the eight OUTER layers of the generator at BASELINE configs[1] shapes (B = 8, 512 x 512): stem, down1-3, up1-3, head -- each launched through
 the C ABI on rotated operand sets (inputs / outputs do not sit in the Infinity Cache), medians of HIP-event pairs.  For same-box A/B runs of the
 profiling library's switches:   LAMA_TOOL_LIB=lama_amd/lib/liblama_hip_prof.so LAMA_CT=3 python tools/outer_ab.py [names...]
-Prints one line per layer: name, median us, min us, checksum of the output (so that two variants can be compared for equality)."""
+Prints one line per layer: name, median us, min us, checksum of the output (so that two variants can be compared for equality).
+--presplit: the head's edges as the fused plans run them (FFCResNetGenerator.presplit_outer): the stem writes LAMA_DT_SPLIT16, down1 / down2 read
+and write it, down3 reads it (inputs packed from the same random fp32 values, so down3's checksum equals the plain run's; a split output has none)."""
 import os
 import sys
 
@@ -26,7 +28,8 @@ LAYERS = {           # name: (cin, cout, k, H, W, stride, transposed, pad)
 
 
 def main():
-    names = sys.argv[1:] or list(LAYERS)
+    presplit = '--presplit' in sys.argv[1:]
+    names = [a for a in sys.argv[1:] if a != '--presplit'] or list(LAYERS)
     prec = L.PREC_NAMES[os.environ.get('LAMA_PRECISION', 'f16x3')]
     lib = L.get_lib()
     dev, B, nrot = 'cuda', 8, int(os.environ.get('KBENCH_ROT', '3'))
@@ -34,7 +37,11 @@ def main():
     tag = ' '.join(f'{k}={v}' for k, v in sorted(os.environ.items()) if k.startswith('LAMA_') and k != 'LAMA_TOOL_LIB')
     for name in names:
         cin, cout, k, H, W, stride, tr, pad = LAYERS[name]
+        xs, ys = presplit and name in ('down1', 'down2', 'down3'), presplit and name in ('stem', 'down1', 'down2')
         x = [torch.randn(B, cin, H, W, generator=g).to(dev) for _ in range(nrot)]
+        if xs:
+            x = [L.split16_pack(t, prec) for t in x]
+        vx, vy = (L.view_split if xs else L.view), (L.view_split if ys else L.view)
         wt = (torch.randn(cin, cout, k, k, generator=g) if tr else torch.randn(cout, cin, k, k, generator=g)).to(dev) * 0.05
         wp = lib.pack_conv_weight(wt, None, stride=stride, transposed=tr, precision=prec)
         Ho, Wo = (2 * H, 2 * W) if tr else ((H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1)
@@ -47,7 +54,7 @@ def main():
         def fn():
             i = it[0] % nrot
             it[0] += 1
-            lib.conv2d(L.view(x[i]), wp, L.view(y[i]), B, k, stride, pad, L.PAD_ZERO if tr else L.PAD_REFLECT, tr, bias, act, None, precision=prec, stream=st)
+            lib.conv2d(vx(x[i]), wp, vy(y[i]), B, k, stride, pad, L.PAD_ZERO if tr else L.PAD_REFLECT, tr, bias, act, None, precision=prec, stream=st)
         for _ in range(2 * nrot):
             fn()
         torch.cuda.synchronize()
@@ -61,8 +68,8 @@ def main():
         it[0] = 0
         fn()
         torch.cuda.synchronize()
-        cs = float(y[0].double().sum()), float(y[0].double().abs().sum())
-        print(f'{name:6s} [{tag}] median {ts[len(ts) // 2]:8.1f} us  min {ts[0]:8.1f} us  checksum {cs[0]:.6e} {cs[1]:.6e}', flush=True)
+        cs = (float('nan'),) * 2 if ys else (float(y[0].double().sum()), float(y[0].double().abs().sum()))
+        print(f'{name:6s}{" presplit" if (xs or ys) else ""} [{tag}] median {ts[len(ts) // 2]:8.1f} us  min {ts[0]:8.1f} us  checksum {cs[0]:.6e} {cs[1]:.6e}', flush=True)
         del x, y
 
 
