@@ -358,7 +358,7 @@ int lama_eval_ingest_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_
  *   workgroup walks list[0 .. *count) instead of every unit; units that are not listed are NOT written.  Only where the dedicated persistent kernels
  *   run (LAMA_PREC_F16X3 / BF16X3, fp32 tensors, the shapes they take); anything else returns LAMA_ERR_UNSUPPORTED with nothing launched and the caller
  *   runs lama_conv2d_fwd -- a superset.  head_rs: rows per head segment (as given to lama_tail_lists_build; ignored by the transposed conv).
- * lama_conv2d_list_supported: 1 when lama_conv2d_list_fwd takes these arguments (every check, no launch).
+ * lama_conv2d_list_supported: 1 when lama_conv2d_list_fwd takes these arguments (every check, no launch: lama_conv2d_route_query with a list).
  * lama_blend_quantize_u8_fwd does not read pred where the mask is 0. */
 typedef struct lama_tail_lists {
     int32_t n_up;    /* ConvTranspose2d launches listed, 0 .. 4 */
@@ -373,6 +373,35 @@ size_t lama_tail_lists_workspace_bytes(int32_t batch, int32_t H, int32_t W, cons
 int lama_tail_lists_build(void* stream, const lama_tensor* mask, int32_t batch, const lama_tail_lists* lists, void* workspace, size_t workspace_bytes);
 int lama_conv2d_list_fwd(void* stream, const lama_conv2d_args* args, const int32_t* list, const int32_t* count, int32_t head_rs);
 int32_t lama_conv2d_list_supported(const lama_conv2d_args* args, int32_t head_rs);
+
+/* (added to v112 without a version bump: one new symbol, nothing else changes) Which kernel family would serve a convolution, asked on the host:
+ * returns exactly the code lama_conv2d_fwd (head_rs < 0) or lama_conv2d_list_fwd with this head_rs (head_rs >= 0) returns for the same arguments,
+ * after the same validation.  Nothing is launched and no tensor, weight or list pointer is dereferenced: only the addresses of the views are
+ * looked at (alignment).  On LAMA_OK *family is LAMA_CONV_FAMILY_* and *geometry packs what distinguishes the instantiations inside the family:
+ *   F32        the exact fmaf-chain path of LAMA_PREC_F32: the M tile (32 / 64 / 128)
+ *   GEMM1X1_WK bit 0: left-over super-tiles go to the fifth waves
+ *   GEMM1X1_W4 bits 4-7: 64-channel chunks of K (3 / 6); bit 8: residual
+ *   GEMM1X1_WS bits 0-3: NH (1: 32-pixel tiles, 2: 64-pixel tiles); bits 4-7: 64-channel chunks of K; bit 8: residual
+ *   CONV_WR    bits 0-3: M-waves WMV; 4-7: K-groups KG; 8-11: 16-channel sub-chunks per chunk KSC1; 12-15: log2 of the tile width; bit 16: stride 2;
+ *              17: the cooperative one-workgroup-per-CU geometry; 18: row-rolling fragment reads; 19: fused conv1 (fuse1_w); 20 / 21: x / y is
+ *              LAMA_DT_SPLIT16 (LAMA_CONV_GEO_WR packs them)
+ *   CONVT2, HEAD7  bit 0: over a work list
+ *   STEM7      bit 21: y is LAMA_DT_SPLIT16
+ *   LDS        bits 0-7: M tile BM; 8-19: pixel tile BN; 20-21: folded 7x7 mode (1 stem, 2 head); bit 22: ConvTranspose2d's fused tap list
+ * lama_conv2d_list_supported is this query with a list (1 where it returns LAMA_OK).  LAMA_ERR_BAD_ARG also for family == NULL or geometry == NULL.
+ * The Winograd and multi-dilated entries are not covered. */
+#define LAMA_CONV_FAMILY_F32 0        /* conv_mfma_f32_kernel (LAMA_PREC_F32) */
+#define LAMA_CONV_FAMILY_GEMM1X1_WK 1 /* the spectral GEMM with all of K in one wave */
+#define LAMA_CONV_FAMILY_GEMM1X1_W4 2 /* pointwise GEMM over 64-pixel super-tiles */
+#define LAMA_CONV_FAMILY_GEMM1X1_WS 3 /* weights-stationary persistent pointwise GEMM */
+#define LAMA_CONV_FAMILY_CONV_WR 4    /* weights-in-registers 3x3 / 1x1 */
+#define LAMA_CONV_FAMILY_CONVT2 5     /* ConvTranspose2d as one launch */
+#define LAMA_CONV_FAMILY_STEM7 6      /* 7x7 stem */
+#define LAMA_CONV_FAMILY_HEAD7 7      /* 7x7 head */
+#define LAMA_CONV_FAMILY_LDS 8        /* the LDS-staged conv_kernel */
+#define LAMA_CONV_GEO_WR(wmv, kg, ksc1, twlog, s2, coop, roll, fuse1, xs, ys) \
+    ((wmv) | (kg) << 4 | (ksc1) << 8 | (twlog) << 12 | (s2) << 16 | (coop) << 17 | (roll) << 18 | (fuse1) << 19 | (xs) << 20 | (ys) << 21)
+int lama_conv2d_route_query(const lama_conv2d_args* args, int32_t head_rs, int32_t* family, int32_t* geometry);
 
 /* Stand-alone per-channel affine + activation: y = act(x*scale[c] + shift[c]) (scale/shift NULL = identity).
  * Used when a caller runs generator.model layer by layer and hits a bare nn.BatchNorm2d (eval) /

@@ -19,6 +19,19 @@ CONV_COOPERATIVE = 1
 CONV_DEFER_OUT = 2          # lama_winograd_conv3x3_fwd: the GEMM launch only (include/lama_hip.h)
 CONV_SIBLINGS_SHIFT = 8     # (v109) bits 8..10: log2 of the number of sibling launches that share the chip with this one
 DT_F32, DT_F16, DT_SPLIT16 = 0, 1, 2      # LAMA_DT_*
+# LAMA_CONV_FAMILY_* of lama_conv2d_route_query (include/lama_hip.h)
+(CONV_FAM_F32, CONV_FAM_GEMM1X1_WK, CONV_FAM_GEMM1X1_W4, CONV_FAM_GEMM1X1_WS, CONV_FAM_CONV_WR, CONV_FAM_CONVT2, CONV_FAM_STEM7, CONV_FAM_HEAD7,
+ CONV_FAM_LDS) = range(9)
+
+
+def conv_geo_wr(wmv, kg, ksc1, twlog, s2=0, coop=0, roll=0, fuse1=0, xs=0, ys=0) -> int:
+    """LAMA_CONV_GEO_WR: the geometry word of a CONV_FAM_CONV_WR route."""
+    return wmv | kg << 4 | ksc1 << 8 | twlog << 12 | s2 << 16 | coop << 17 | roll << 18 | fuse1 << 19 | xs << 20 | ys << 21
+
+
+def conv_geo_lds(bm, bn, mode=0, trf=0) -> int:
+    """The geometry word of a CONV_FAM_LDS route."""
+    return bm | bn << 8 | mode << 20 | trf << 22
 POOL_MAX, POOL_AVG_EXCLUDE_PAD = 0, 1      # lama_pool3x3_fwd mode
 ABI_VERSION = 112      # LAMA_HIP_VERSION of include/lama_hip.h
 PREC_NAMES = {'f32': PREC_F32, 'bf16x3': PREC_BF16X3, 'f16x3': PREC_F16X3, 'f16': PREC_F16}
@@ -146,6 +159,8 @@ class LamaLib:
         L.lama_conv2d_fwd.argtypes = [vp, C.POINTER(Conv2dArgs)]
         L.lama_conv2d_list_fwd.restype, L.lama_conv2d_list_fwd.argtypes = C.c_int, [vp, C.POINTER(Conv2dArgs), vp, vp, i32]
         L.lama_conv2d_list_supported.restype, L.lama_conv2d_list_supported.argtypes = i32, [C.POINTER(Conv2dArgs), i32]
+        L.lama_conv2d_route_query.restype = C.c_int
+        L.lama_conv2d_route_query.argtypes = [C.POINTER(Conv2dArgs), i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.lama_tail_lists_workspace_bytes.restype, L.lama_tail_lists_workspace_bytes.argtypes = sz, [i32, i32, i32, C.POINTER(TailLists)]
         L.lama_tail_lists_build.restype, L.lama_tail_lists_build.argtypes = C.c_int, [vp, T, i32, C.POINTER(TailLists), vp, sz]
         L.lama_rfft2_fwd.restype = C.c_int
@@ -278,13 +293,14 @@ class LamaLib:
                act: int = ACT_NONE, resid: Optional[Tensor4] = None, x2: Optional[Tensor4] = None,
                w2_packed: Optional[torch.Tensor] = None, precision: int = PREC_F32, stream: int = 0,
                range_flag: Optional[torch.Tensor] = None, fuse1: Optional[tuple] = None, cooperative: bool = False, siblings_log2: int = 0,
-               tile_list: Optional[tuple] = None, query: bool = False):
+               tile_list: Optional[tuple] = None, query: bool = False, route: bool = False):
         """``fuse1`` = (packed conv1 weights with the channel order of fuse1_channel_order(), BatchNorm shift [192], x1 view): the NEXT
         layer's SpectralTransform.conv1 in the epilogue of this (global-branch) launch -- lama_conv2d_args.fuse1_*.  ``siblings_log2`` (v109):
         this launch covers 1 / 2^n of a batch whose other parts run beside it (LAMA_CONV_SIBLINGS_*).  ``tile_list`` = (list, count, head_rs), the
         int32 tensors of ``tail_lists_alloc``: lama_conv2d_list_fwd, the launch over the listed work units only (LamaError with code ERR_UNSUPPORTED
         where the dedicated kernels do not take the shape); with ``query`` nothing is launched and the verdict is returned
-        (lama_conv2d_list_supported)."""
+        (lama_conv2d_list_supported).  ``route``: nothing is launched either; returns (code, family, geometry) of lama_conv2d_route_query
+        for exactly these arguments (family and geometry are None unless code == 0)."""
         a = Conv2dArgs()
         a.x, a.w_packed = x, w_packed.data_ptr()
         a.kh = a.kw = k
@@ -300,6 +316,10 @@ class LamaLib:
         if fuse1 is not None:
             a.fuse1_w, a.fuse1_bias, a.fuse1_y = fuse1[0].data_ptr(), fuse1[1].data_ptr(), fuse1[2]
         a.flags = (CONV_COOPERATIVE if cooperative else 0) | (int(siblings_log2) << CONV_SIBLINGS_SHIFT)   # lama_conv2d_args.flags
+        if route:
+            fam, geo = C.c_int32(-1), C.c_int32(-1)
+            rc = self._l.lama_conv2d_route_query(C.byref(a), -1 if tile_list is None else int(tile_list[2]), C.byref(fam), C.byref(geo))
+            return (int(rc), fam.value, geo.value) if rc == 0 else (int(rc), None, None)
         if tile_list is not None:
             lst, cnt, head_rs = tile_list
             if query:

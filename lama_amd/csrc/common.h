@@ -151,16 +151,16 @@ __device__ __forceinline__ lama_buf_t lama_make_buf(const void* ptr, long long b
 #define LAMA_OPAQUE_S(x) asm volatile("" : "+s"(x))
 #endif
 
-// the work list of a persistent tail launch (lama_conv2d_list_fwd): device int32 indices + their count; head_rs: rows per head segment;
-// dry: run every check of the launch and return its verdict without launching (lama_conv2d_list_supported)
-struct LamaTileList { const int32_t* list; const int32_t* count; int head_rs; bool dry; };
+// the work list of a persistent tail launch (lama_conv2d_list_fwd): device int32 indices + their count; head_rs: rows per head segment
+struct LamaTileList { const int32_t* list; const int32_t* count; int head_rs; };
 // 3-term split convolution back ends (conv_split3.inc compiled as conv_bf16x3.hip / conv_f16x3.hip), reached through
 // lama_conv2d_* with LAMA_PREC_BF16X3 / LAMA_PREC_F16X3
 #define LAMA_CB_DECL(sfx)                                                                                                        \
     int64_t lama_cb_packed_weight_bytes##sfx(int cout, int cin, int kh, int kw, int stride, int transposed);                       \
     int lama_cb_pack_weight##sfx(hipStream_t stream, const float* w, const float* scale, int cout, int cin, int kh, int kw,       \
                                  int stride, int transposed, void* dst);                                                         \
-    int lama_cb_conv2d_fwd##sfx(hipStream_t stream, const lama_conv2d_args* a, int Ho, int Wo, const LamaTileList* tl = nullptr);
+    int lama_cb_conv2d_fwd##sfx(hipStream_t stream, const lama_conv2d_args* a, int Ho, int Wo, const LamaTileList* tl = nullptr, \
+                                int32_t* query = nullptr);
 LAMA_CB_DECL(_bf16x3)
 LAMA_CB_DECL(_f16x3)
 LAMA_CB_DECL(_f16)

@@ -388,7 +388,8 @@ bool fill_seg(ConvSeg* s, const lama_tensor& x, const float* w, const ConvPlan& 
 }
 
 template <int T1, int BKC1, int T2, int BKC2>
-int launch_bm(hipStream_t st, const ConvParams& p, int BM, int grid, size_t shmem) {
+int launch_bm(hipStream_t st, const ConvParams& p, int BM, int grid, size_t shmem, bool dry) {
+    if (dry) return (BM == 128 || BM == 64 || BM == 32) ? LAMA_OK : LAMA_ERR_UNSUPPORTED;
     switch (BM) {
         case 128: hipLaunchKernelGGL((conv_mfma_f32_kernel<T1, BKC1, T2, BKC2, 128>), dim3(grid), dim3(LAMA_NTHREADS), shmem, st, p); break;
         case 64: hipLaunchKernelGGL((conv_mfma_f32_kernel<T1, BKC1, T2, BKC2, 64>), dim3(grid), dim3(LAMA_NTHREADS), shmem, st, p); break;
@@ -399,7 +400,8 @@ int launch_bm(hipStream_t st, const ConvParams& p, int BM, int grid, size_t shme
     return LAMA_OK;
 }
 
-int launch_conv(hipStream_t st, const ConvParams& p, int T1, int BKC1, int T2, int BKC2, int BM) {
+// ``dry`` (lama_conv2d_route_query): every check and the verdict, no launch
+int launch_conv(hipStream_t st, const ConvParams& p, int T1, int BKC1, int T2, int BKC2, int BM, bool dry = false) {
     const int a1 = T1 * BKC1 * BM, a2 = T2 * BKC2 * BM;
     const int amax = a1 > a2 ? a1 : a2;
     const int p1 = BKC1 * p.s1.PH * p.s1.PW, p2 = T2 ? BKC2 * p.s2.PH * p.s2.PW : 0;
@@ -408,7 +410,7 @@ int launch_conv(hipStream_t st, const ConvParams& p, int T1, int BKC1, int T2, i
     const int grid = p.B * p.tiles_x * p.tiles_y * p.MT;
     if (grid <= 0) return LAMA_OK;
 #define CONV_CASE(t1, b1, t2, b2) \
-    if (T1 == t1 && BKC1 == b1 && T2 == t2 && BKC2 == b2) return launch_bm<t1, b1, t2, b2>(st, p, BM, grid, shmem);
+    if (T1 == t1 && BKC1 == b1 && T2 == t2 && BKC2 == b2) return launch_bm<t1, b1, t2, b2>(st, p, BM, grid, shmem, dry);
     CONV_CASE(9, 8, 0, 0)
     CONV_CASE(9, 8, 1, 32)
     CONV_CASE(9, 4, 0, 0)
@@ -643,7 +645,8 @@ extern "C" void lama_fuse1_channel_order(int32_t* order) {
             for (int i = 0; i < 8; ++i) order[16 * kq + 8 * kh + i] = 32 * (kq / 2) + 16 * (kq & 1) + 8 * (i / 4) + 4 * kh + (i % 4);
 }
 
-static int conv2d_impl(void* stream, const lama_conv2d_args* a, const LamaTileList* tl) {
+// ``query`` (lama_conv2d_route_query): nothing is launched; the code is the launch's, query[0] = LAMA_CONV_FAMILY_*, query[1] its geometry
+static int conv2d_impl(void* stream, const lama_conv2d_args* a, const LamaTileList* tl, int32_t* query = nullptr) {
     if (!a || !tensor_ok(a->x) || !tensor_ok(a->y) || !a->w_packed || a->batch <= 0) return LAMA_ERR_BAD_ARG;
     if (a->precision != LAMA_PREC_F32 && a->precision != LAMA_PREC_BF16X3 && a->precision != LAMA_PREC_F16X3 && a->precision != LAMA_PREC_F16)
         return LAMA_ERR_UNSUPPORTED;
@@ -686,10 +689,11 @@ static int conv2d_impl(void* stream, const lama_conv2d_args* a, const LamaTileLi
             (a->precision != LAMA_PREC_BF16X3 && a->precision != LAMA_PREC_F16X3))
             return LAMA_ERR_UNSUPPORTED;
     }
-    if (a->precision == LAMA_PREC_BF16X3) return lama_cb_conv2d_fwd_bf16x3((hipStream_t)stream, a, Ho, Wo, tl);
-    if (a->precision == LAMA_PREC_F16X3) return lama_cb_conv2d_fwd_f16x3((hipStream_t)stream, a, Ho, Wo, tl);
-    if (a->precision == LAMA_PREC_F16) return lama_cb_conv2d_fwd_f16((hipStream_t)stream, a, Ho, Wo, tl);
+    if (a->precision == LAMA_PREC_BF16X3) return lama_cb_conv2d_fwd_bf16x3((hipStream_t)stream, a, Ho, Wo, tl, query);
+    if (a->precision == LAMA_PREC_F16X3) return lama_cb_conv2d_fwd_f16x3((hipStream_t)stream, a, Ho, Wo, tl, query);
+    if (a->precision == LAMA_PREC_F16) return lama_cb_conv2d_fwd_f16((hipStream_t)stream, a, Ho, Wo, tl, query);
     if (tl) return LAMA_ERR_UNSUPPORTED;   // the work lists are walked by the split-precision tail kernels only
+    if (query) { query[0] = LAMA_CONV_FAMILY_F32; query[1] = pl.BM; }
 
     ConvPlan pl2;
     if (has2 && !make_plan(cout, a->x2.C, 1, 1, 1, 0, 0, &pl2)) return LAMA_ERR_UNSUPPORTED;
@@ -738,7 +742,7 @@ static int conv2d_impl(void* stream, const lama_conv2d_args* a, const LamaTileLi
             if (!fill_seg(&p.s2, a->x2, (const float*)a->w2_packed, pl2, 0, 1, LAMA_PAD_ZERO, twlog, BKC2 * CONV_BN / LAMA_NTHREADS, false))
                 return LAMA_ERR_UNSUPPORTED;
         }
-        int rc = launch_conv((hipStream_t)stream, p, pl.T[cls], pl.BKC[cls], T2, BKC2, pl.BM);
+        int rc = launch_conv((hipStream_t)stream, p, pl.T[cls], pl.BKC[cls], T2, BKC2, pl.BM, query != nullptr);
         if (rc != LAMA_OK) return rc;
     }
     return LAMA_OK;
@@ -749,10 +753,19 @@ extern "C" int lama_conv2d_fwd(void* stream, const lama_conv2d_args* a) { return
 // The same convolution over a compacted list of its work units (sparse tail): the dedicated ConvTranspose2d / 7x7 head kernels only
 extern "C" int lama_conv2d_list_fwd(void* stream, const lama_conv2d_args* a, const int32_t* list, const int32_t* count, int32_t head_rs) {
     if (!list || !count) return LAMA_ERR_BAD_ARG;
-    const LamaTileList tl = {list, count, head_rs, false};
+    const LamaTileList tl = {list, count, head_rs};
     return conv2d_impl(stream, a, &tl);
 }
+// Which kernels would serve a launch, asked on the host: conv2d_impl's checks and the back end's route, nothing launched (head_rs < 0: no list)
+extern "C" int lama_conv2d_route_query(const lama_conv2d_args* a, int32_t head_rs, int32_t* family, int32_t* geometry) {
+    if (!family || !geometry) return LAMA_ERR_BAD_ARG;
+    const LamaTileList tl = {nullptr, nullptr, head_rs};
+    int32_t q[2] = {0, 0};
+    const int rc = conv2d_impl(nullptr, a, head_rs < 0 ? nullptr : &tl, q);
+    if (rc == LAMA_OK) { *family = q[0]; *geometry = q[1]; }
+    return rc;
+}
 extern "C" int32_t lama_conv2d_list_supported(const lama_conv2d_args* a, int32_t head_rs) {
-    const LamaTileList tl = {nullptr, nullptr, head_rs, true};
-    return conv2d_impl(nullptr, a, &tl) == LAMA_OK ? 1 : 0;
+    int32_t family, geometry;   // (a negative head_rs is a list launch all the same: one the head refuses and the transposed conv ignores)
+    return lama_conv2d_route_query(a, head_rs < 0 ? 0 : head_rs, &family, &geometry) == LAMA_OK ? 1 : 0;
 }

@@ -818,7 +818,7 @@ bool cb_make_plan(int cout, int cin, int kh, int kw, int stride, int pad, int tr
             }
         pl->T[0] = 9;
         pl->oy0[0] = pl->ox0[0] = 0;
-        // ... and packed a second time class by class for convt2_kernel (ct_try_launch, conv_wreg_host.inc): output
+        // ... and packed a second time class by class for convt2_kernel (ct_route / ct_launch, conv_wreg_host.inc): output
         // parity (py, px) is a stride-1 convolution of the input with the 1, 2 or 4 taps that reach it, stored with step 2 from
         // (py, px); heaviest class first
         pl->nseg = 5;
@@ -903,14 +903,18 @@ int cb_fill_seg(CbSeg* s, const lama_tensor& x, const char* w, const CbPlan& pl,
     return s->PH * s->PW * 2 * pl.KS[cls];
 }
 
+// The LDS-staged launcher: the instantiation tables of conv_kernel, fed by cb_route() (conv_wreg_host.inc: lds_has_kernel states their conditions).
+// CB_ERR_ROUTE (hipErrorUnknown): a launcher met a route cb_route() does not produce -- a bug, never a reason to fall through to another kernel.
+#define CB_ERR_ROUTE 999
+
 template <int T1, int TG1, int KS1, int T2, int TG2, int KS2, int BM, int IOM>
 int cb_launch_u_io(hipStream_t st, const CbParams& p, int maxu, int grid, size_t shmem) {
 #ifdef CB_DEV_NO_GENERIC   // kernel-development builds (tools/kres.py): skip the LDS-staged instantiations, 10x shorter compile
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 #endif
     if (maxu <= 1) hipLaunchKernelGGL((CB_NAME(conv_kernel)<T1, TG1, KS1, T2, TG2, KS2, BM, 1, 0, 1, 0, IOM>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
     else if (maxu <= 3) hipLaunchKernelGGL((CB_NAME(conv_kernel)<T1, TG1, KS1, T2, TG2, KS2, BM, 3, 0, 1, 0, IOM>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
-    else return LAMA_ERR_UNSUPPORTED;
+    else return CB_ERR_ROUTE;
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }
@@ -923,14 +927,13 @@ int cb_launch_u(hipStream_t st, const CbParams& p, int maxu, int grid, size_t sh
     if (io == CB_IO_F32) return cb_launch_u_io<T1, TG1, KS1, T2, TG2, KS2, BM, CB_IO_F32>(st, p, maxu, grid, shmem);
 #else
     constexpr int X2 = T2 > 0 ? CB_IO_X2H : 0;
-    if (T2 > 0 && !(io & CB_IO_X2H)) return LAMA_ERR_UNSUPPORTED;
     switch (io & 3) {
         case CB_IO_F16: return cb_launch_u_io<T1, TG1, KS1, T2, TG2, KS2, BM, CB_IO_F16 | X2>(st, p, maxu, grid, shmem);
         case CB_IO_F32_F16: return cb_launch_u_io<T1, TG1, KS1, T2, TG2, KS2, BM, CB_IO_F32_F16 | X2>(st, p, maxu, grid, shmem);
         case CB_IO_F16_F32: return cb_launch_u_io<T1, TG1, KS1, T2, TG2, KS2, BM, CB_IO_F16_F32 | X2>(st, p, maxu, grid, shmem);
     }
 #endif
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 }
 
 template <int T1, int TG1, int KS1, int T2, int TG2, int KS2>
@@ -941,17 +944,17 @@ int cb_launch_bm(hipStream_t st, const CbParams& p, int BM, int maxu, int grid, 
         case 64: return cb_launch_u<T1, TG1, KS1, T2, TG2, KS2, 64>(st, p, maxu, grid, shmem, io);
         case 32: return cb_launch_u<T1, TG1, KS1, T2, TG2, KS2, 32>(st, p, maxu, grid, shmem, io);
     }
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 }
 
 template <int BM, int IOM>
 int cb_launch_trf_io(hipStream_t st, const CbParams& p, int maxu, int grid, size_t shmem) {
 #ifdef CB_DEV_NO_GENERIC   // kernel-development builds (tools/kres.py): skip the LDS-staged instantiations, 10x shorter compile
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 #endif
     if (maxu <= 1) hipLaunchKernelGGL((CB_NAME(conv_kernel)<9, 3, 1, 0, 0, 0, BM, 1, 0, 4, 0, IOM>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
     else if (maxu <= 3) hipLaunchKernelGGL((CB_NAME(conv_kernel)<9, 3, 1, 0, 0, 0, BM, 3, 0, 4, 0, IOM>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
-    else return LAMA_ERR_UNSUPPORTED;
+    else return CB_ERR_ROUTE;
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }
@@ -965,14 +968,13 @@ int cb_launch_trf_u(hipStream_t st, const CbParams& p, int maxu, int grid, size_
     if (io == CB_IO_F32_F16) return cb_launch_trf_io<BM, CB_IO_F32_F16>(st, p, maxu, grid, shmem);   // the first upsample reads the fp32 residual stream
     if (io == CB_IO_F16_F32) return cb_launch_trf_io<BM, CB_IO_F16_F32>(st, p, maxu, grid, shmem);
 #endif
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 }
 
 int cb_launch_folded7(hipStream_t st, const CbParams& p, int mode, int BM, int maxu, int grid, size_t shmem, int io) {
 #ifdef CB_DEV_NO_GENERIC   // kernel-development builds (tools/kres.py): skip the LDS-staged instantiations, 10x shorter compile
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 #endif
-    if (maxu > 3) return LAMA_ERR_UNSUPPORTED;
 #if CB_HALF
     // LAMA_PREC_F16: the stem reads the fp32 network input and writes fp16, the head reads fp16 and writes the fp32 image
     if (io == CB_IO_F32_F16 && mode == 1 && BM == 64) {
@@ -985,23 +987,20 @@ int cb_launch_folded7(hipStream_t st, const CbParams& p, int mode, int BM, int m
         LAMA_CHECK_LAUNCH();
         return LAMA_OK;
     }
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 #else
-    if (io != CB_IO_F32) return LAMA_ERR_UNSUPPORTED;
+    if (io != CB_IO_F32) return CB_ERR_ROUTE;
     if (mode == 2 && BM == 32) hipLaunchKernelGGL((CB_NAME(conv_kernel)<7, 7, 1, 0, 0, 0, 32, 3, 0, 1, 2>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
     else if (mode == 1 && BM == 64) hipLaunchKernelGGL((CB_NAME(conv_kernel)<7, 7, 2, 0, 0, 0, 64, 3, 0, 1, 1>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
     else if (mode == 1 && BM == 128) hipLaunchKernelGGL((CB_NAME(conv_kernel)<7, 7, 2, 0, 0, 0, 128, 3, 0, 1, 1>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
     else if (mode == 1 && BM == 32) hipLaunchKernelGGL((CB_NAME(conv_kernel)<7, 7, 2, 0, 0, 0, 32, 3, 0, 1, 1>), dim3(grid), dim3(CB_THREADS), shmem, st, p);
-    else return LAMA_ERR_UNSUPPORTED;
+    else return CB_ERR_ROUTE;
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 #endif
 }
 
-int cb_launch(hipStream_t st, const CbParams& p, int T1, int T2, int BM, int maxu, bool trf, int mode, int io) {
-    const size_t shmem = (size_t)p.nwbuf * p.wbytes + 2 * (size_t)p.pbytes;
-    if (shmem > 160 * 1024) return LAMA_ERR_UNSUPPORTED;
-    const int grid = p.B * p.tiles_x * p.tiles_y * p.MT;
+int cb_launch(hipStream_t st, const CbParams& p, int T1, int T2, int BM, int maxu, bool trf, int mode, int io, int grid, size_t shmem) {
     if (grid <= 0) return LAMA_OK;
     if (mode) return cb_launch_folded7(st, p, mode, BM, maxu, grid, shmem, io);
     if (trf) {
@@ -1010,7 +1009,7 @@ int cb_launch(hipStream_t st, const CbParams& p, int T1, int T2, int BM, int max
             case 64: return cb_launch_trf_u<64>(st, p, maxu, grid, shmem, io);
             case 32: return cb_launch_trf_u<32>(st, p, maxu, grid, shmem, io);
         }
-        return LAMA_ERR_UNSUPPORTED;
+        return CB_ERR_ROUTE;
     }
 #if defined(LAMA_PROFILING) && !CB_HALF
     if (!CB_F16 && T1 == 9 && T2 == 0 && BM == 128 && maxu <= 1) {   // profiling tools only: timing ablations of the bottleneck 3x3 kernel
@@ -1030,7 +1029,7 @@ int cb_launch(hipStream_t st, const CbParams& p, int T1, int T2, int BM, int max
     CB_CASE(2, 2, 1, 0, 0, 0)
     CB_CASE(4, 4, 1, 0, 0, 0)
 #undef CB_CASE
-    return LAMA_ERR_UNSUPPORTED;
+    return CB_ERR_ROUTE;
 }
 
 #include "conv_wreg_host.inc"
@@ -1077,115 +1076,38 @@ int CB_NAME(lama_cb_pack_weight)(hipStream_t stream, const float* w, const float
     return LAMA_OK;
 }
 
-// arguments were validated by lama_conv2d_fwd (conv_mfma.hip)
-// ``tl`` (lama_conv2d_list_fwd): only the two persistent tail kernels walk a work list -- everything else is LAMA_ERR_UNSUPPORTED, nothing launched
-int CB_NAME(lama_cb_conv2d_fwd)(hipStream_t stream, const lama_conv2d_args* a, int Ho, int Wo, const LamaTileList* tl) {
-    const int cout = a->y.C, cin = a->x.C;
-    CbPlan pl;
-    if (!cb_make_plan(cout, cin, a->kh, a->kw, a->stride, a->pad, a->transposed, &pl)) return LAMA_ERR_UNSUPPORTED;
+// arguments were validated by lama_conv2d_fwd (conv_mfma.hip).  ``tl``: the work list of lama_conv2d_list_fwd.  ``query`` (lama_conv2d_route_query):
+// nothing is launched; the code is the launch's, query[0] the family and query[1] its geometry (cb_route_geometry).
+int CB_NAME(lama_cb_conv2d_fwd)(hipStream_t stream, const lama_conv2d_args* a, int Ho, int Wo, const LamaTileList* tl, int32_t* query) {
+    CbPlan pl, pl2;
+    if (!cb_make_plan(a->y.C, a->x.C, a->kh, a->kw, a->stride, a->pad, a->transposed, &pl)) return LAMA_ERR_UNSUPPORTED;
     const bool has2 = a->x2.ptr != nullptr;
-    if (tl) {
-        if (has2 || a->fuse1_w) return LAMA_ERR_UNSUPPORTED;
-        const int io_l = (a->x.dtype == LAMA_DT_F16 ? 1 : 0) | (a->y.dtype == LAMA_DT_F16 ? 2 : 0);
-        if ((io_l != CB_IO_F32) != (CB_HALF != 0)) return LAMA_ERR_UNSUPPORTED;
-        return a->transposed ? ct_try_launch(stream, a, pl, Ho, Wo, io_l, tl) : head_try_launch(stream, a, pl, Ho, Wo, io_l, tl);
-    }
-    CbPlan pl2;
-    if (has2 && !cb_make_plan(cout, a->x2.C, 1, 1, 1, 0, 0, &pl2)) return LAMA_ERR_UNSUPPORTED;
-    if (has2 && pl.mode) return LAMA_ERR_UNSUPPORTED;
-    const int io = (a->x.dtype == LAMA_DT_F16 ? 1 : 0) | (a->y.dtype == LAMA_DT_F16 ? 2 : 0) | ((has2 && a->x2.dtype == LAMA_DT_F16) ? CB_IO_X2H : 0);   // CB_IO_*
+    if (has2 && (!cb_make_plan(a->y.C, a->x2.C, 1, 1, 1, 0, 0, &pl2) || pl.mode)) return LAMA_ERR_UNSUPPORTED;
+    int io = (a->x.dtype == LAMA_DT_F16 ? 1 : 0) | (a->y.dtype == LAMA_DT_F16 ? 2 : 0) | ((has2 && a->x2.dtype == LAMA_DT_F16) ? CB_IO_X2H : 0);   // CB_IO_*
     if ((io != CB_IO_F32) != (CB_HALF != 0)) return LAMA_ERR_UNSUPPORTED;   // fp16 tensors <-> the LAMA_PREC_F16 translation unit
-    {   // LAMA_DT_SPLIT16 (validated by lama_conv2d_fwd: split precisions, no x2 / resid / fuse1): the two dedicated kernels or nothing
-        const int ios = (a->x.dtype == LAMA_DT_SPLIT16 ? CB_IO_XS : 0) | (a->y.dtype == LAMA_DT_SPLIT16 ? CB_IO_YS : 0);
-        if (ios) {
-            if (CB_HALF || has2 || a->transposed) return LAMA_ERR_UNSUPPORTED;
-            if (ios == CB_IO_YS) {
-                const int rc = stem_try_launch(stream, a, pl, Ho, Wo, ios);
-                if (rc != LAMA_ERR_UNSUPPORTED) return rc;
-            }
-            return cw_try_launch(stream, a, pl, nullptr, Ho, Wo, ios);
+    // LAMA_DT_SPLIT16 (validated by lama_conv2d_fwd: split precisions, no x2 / resid / fuse1)
+    io |= (a->x.dtype == LAMA_DT_SPLIT16 ? CB_IO_XS : 0) | (a->y.dtype == LAMA_DT_SPLIT16 ? CB_IO_YS : 0);
+    const CbPlan* p2 = has2 ? &pl2 : nullptr;
+    CbRoute r;
+    const int rc = cb_route(a, pl, p2, Ho, Wo, io, tl, &r);
+    if (query && rc == LAMA_OK) { query[0] = r.family; query[1] = cb_route_geometry(r); }
+    if (query || rc != LAMA_OK) return rc;
+    const long long HW = (long long)Ho * Wo;
+    switch (r.family) {
+        case CB_FAM_WK: return wk_launch(stream, a, pl, HW, r);
+        case CB_FAM_W4: return w4_launch(stream, a, pl, HW, r);
+        case CB_FAM_WS: return ws_launch(stream, a, pl, HW, r);
+        case CB_FAM_WR: return wr_launch(stream, a, pl, p2, Ho, Wo, r);
+        case CB_FAM_CT: return ct_launch(stream, a, pl, tl, r);
+        case CB_FAM_STEM: return stem_launch(stream, a, pl, Ho, Wo, r);
+        case CB_FAM_HEAD: return head_launch(stream, a, pl, Ho, Wo, tl, r);
+        case CB_FAM_LDS: {
+            CbParams p;
+            lds_fill(&p, a, pl, p2, Ho, Wo, r);
+            return cb_launch(stream, p, pl.T[0], has2 ? 1 : 0, r.BM, r.maxu, r.trf, r.mode, io, r.grid, r.shmem);
         }
     }
-    {   // bottleneck shapes: weights-in-registers kernel (conv_wreg_dev.inc)
-        int rc = cw_try_launch(stream, a, pl, has2 ? &pl2 : nullptr, Ho, Wo, io);
-        if (rc != LAMA_ERR_UNSUPPORTED) return rc;
-        if (!has2) {
-            rc = ct_try_launch(stream, a, pl, Ho, Wo, io);
-            if (rc != LAMA_ERR_UNSUPPORTED) return rc;
-        }
-    }
-    if (a->fuse1_w) return LAMA_ERR_UNSUPPORTED;   // the fused conv1 exists in the 12 x 1 weights-in-registers launch only: never silently dropped
-
-    if (!has2) {   // stem / head: weights-stationary kernels with wave- / lane-private windows (conv_stem_dev.inc, conv_head_dev.inc)
-        int rc = stem_try_launch(stream, a, pl, Ho, Wo, io);
-        if (rc != LAMA_ERR_UNSUPPORTED) return rc;
-        rc = head_try_launch(stream, a, pl, Ho, Wo, io);
-        if (rc != LAMA_ERR_UNSUPPORTED) return rc;
-    }
-    int BM = cb_pick_bm(pl.rows, pl.mode ? 49 : pl.T[0], a->transposed ? 1 : a->stride, a->batch, a->transposed ? a->x.H : Ho,
-                        a->transposed ? a->x.W : Wo);
-    { static const int bm_env = lama_env_int("LAMA_CB_BM", 0); if (bm_env && a->transposed) BM = bm_env; }   // profiling tools: M tile of the transposed convs
-    if (BM < 128 && !a->transposed && a->stride == 2) BM = 128;   // a 256-pixel stride-2 tile does not leave room for two patch buffers
-    if (pl.mode == 1) BM = cout > 64 ? 128 : 64;   // 128-pixel tiles: 4 channel octets per pixel have to be staged
-    const int BN = (BM >= 128 || ((a->transposed || pl.mode == 1) && BM == 64)) ? 128 : 256;
-    if ((long long)a->x.C * a->x.H * a->x.W >= (1ll << 31) || (has2 && (long long)a->x2.C * a->x2.H * a->x2.W >= (1ll << 31)))
-        return LAMA_ERR_UNSUPPORTED;   // 32-bit element offsets inside one image
-
-    for (int cls = 0; cls < (a->transposed ? 1 : pl.nseg); ++cls) {   // ConvTranspose2d: the fused tap list (class 0) only
-        CbParams p;
-        memset(&p, 0, sizeof(p));
-        const bool flat = (pl.T[cls] == 1 && !a->transposed && a->stride == 1 && a->pad == 0 && !has2);
-        p.bias = a->bias;
-        p.resid = (const float*)a->resid.ptr;
-        p.resid_bstride = a->resid.batch_stride;
-        p.y = (float*)a->y.ptr;
-        p.y_bstride = a->y.batch_stride;
-        p.M = pl.rows;
-        p.MT = lama_ceil_div(pl.rows, BM);
-        p.B = a->batch;
-        p.act = a->act;
-        p.range_flag = a->range_flag;
-        if (flat) {
-            p.Ho = 1; p.Wo = Ho * Wo; p.GH = 1; p.GW = Ho * Wo; p.ostep = 1;
-        } else if (a->transposed) {
-            p.Ho = Ho; p.Wo = Wo; p.GH = a->x.H; p.GW = a->x.W; p.ostep = 2;
-            p.oy0 = pl.oy0[cls]; p.ox0 = pl.ox0[cls];
-        } else {
-            p.Ho = Ho; p.Wo = Wo; p.GH = Ho; p.GW = Wo; p.ostep = 1;
-        }
-        const int stride = a->transposed ? 1 : a->stride;
-        const int pad_mode = a->transposed ? LAMA_PAD_ZERO : a->pad_mode;
-        // tile: TW = 32 output pixels of one row per wave (conflict-free B fragments), narrower only for narrow images
-        int twlog = flat ? lama_ilog2(BN) : 5;
-        while (pl.mode != 2 && twlog > 3 && (1 << (twlog - 1)) >= p.GW) --twlog;
-        const int TW = 1 << twlog, TH = BN >> twlog;
-        p.TWlog = twlog;
-        p.tiles_x = pl.mode == 2 ? lama_ceil_div(p.GW, 26) : lama_ceil_div(p.GW, TW);
-        p.tiles_y = lama_ceil_div(p.GH, TH);
-        int units = cb_fill_seg(&p.s1, a->x, (const char*)a->w_packed + pl.woff[cls], pl, cls, stride, pad_mode, TH, TW, flat);
-        p.s1.vpad = a->pad;
-        long long wbytes = (long long)pl.TG[cls] * pl.KS[cls] * (BM / 32) * 2048;
-        long long pbytes = (long long)2 * 2 * pl.KS[cls] * p.s1.npix * 16;
-        int TG2 = 0, KS2 = 0;
-        if (has2) {
-            TG2 = pl2.TG[0]; KS2 = pl2.KS[0];
-            int u2 = cb_fill_seg(&p.s2, a->x2, (const char*)a->w2_packed, pl2, 0, 1, LAMA_PAD_ZERO, TH, TW, false);
-            units = u2 > units ? u2 : units;
-            long long w2 = (long long)TG2 * KS2 * (BM / 32) * 2048, p2 = (long long)2 * 2 * KS2 * p.s2.npix * 16;
-            wbytes = w2 > wbytes ? w2 : wbytes;
-            pbytes = p2 > pbytes ? p2 : pbytes;
-        }
-        p.wbytes = (int)wbytes;
-        p.pbytes = (int)pbytes;
-        {   // a segment with S stages touches min(3, S) weight buffers
-            int smax = p.s1.nchunk * p.s1.NG;
-            if (has2 && p.s2.nchunk * p.s2.NG > smax) smax = p.s2.nchunk * p.s2.NG;
-            p.nwbuf = smax < 3 ? smax : 3;
-        }
-        int rc = cb_launch(stream, p, pl.T[cls], has2 ? 1 : 0, BM, lama_ceil_div(units, CB_THREADS), a->transposed != 0, pl.mode, io);
-        if (rc != LAMA_OK) return rc;
-    }
-    return LAMA_OK;
+    return CB_ERR_ROUTE;
 }
 
 #if !CB_HALF

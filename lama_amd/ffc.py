@@ -134,9 +134,6 @@ class _Exec:
         self.winograd = True              # the local 3x3 conv of a two-branch FFC layer as Winograd F(2x2, 3x3) where the shape allows (wino_dev.inc)
         self.local_first = True           # capture order at the fork: the first successor of a hipGraph node stays on its queue
         self.cooperative_serial = False   # tests: the one-stream launch order with the overlapped order's kernel geometry (bit-equal results)
-        # the stem kernel that can write LAMA_DT_SPLIT16 takes launches from this many 32-pixel row segments on (stem_try_launch); 0 with a
-        # library that takes it whatever the size (emulator / forced-path tests) -- FFCResNetGenerator.presplit_outer
-        self.presplit_stem_min_tiles = 4096
 
     @property
     def lib(self) -> L.LamaLib:
@@ -701,7 +698,7 @@ class FFC(_HipModule):
     # -- launch --------------------------------------------------------------------------------------
     def launch(self, pk: dict, act: int, src: torch.Tensor, dst: torch.Tensor, scratch: Optional[dict],
                resid: Optional[torch.Tensor] = None, extra_pad: int = 0, side: Optional['torch.cuda.Stream'] = None,
-               x1_ready: bool = False, fuse_next: Optional['SpectralTransform'] = None, split=(False, False)) -> bool:
+               x1_ready: bool = False, fuse_next: Optional['SpectralTransform'] = None, split=(False, False), route: bool = False) -> bool:
         """src [B, in_cl+in_cg, H, W] -> dst [B, out_cl+out_cg, Ho, Wo] (x_l | x_g channel-contiguous), as 1 launch (no global
         input) or 6 launches (conv1x1, rfft2, spectral conv1x1, irfft2+add, fused local conv, fused global conv).
 
@@ -713,16 +710,17 @@ class FFC(_HipModule):
         ``x1_ready``: scratch['x1'] already holds conv1 of this layer (written by the previous layer's global launch).
         ``fuse_next``: the SpectralTransform of the NEXT layer: its conv1 rides in the epilogue of this layer's global launch
         (lama_conv2d_args.fuse1_*).  Returns True when it did (the next layer then passes x1_ready=True).
-        ``split`` = (src, dst) hold LAMA_DT_SPLIT16 parts instead of fp32 (layers without a global input only; FFCResNetGenerator.presplit_outer)."""
+        ``split`` = (src, dst) hold LAMA_DT_SPLIT16 parts instead of fp32 (layers without a global input only; FFCResNetGenerator.presplit_outer);
+        ``route`` (those layers only): nothing is launched, returns the (code, family, geometry) of lama_conv2d_route_query for that launch."""
         f, ex, prec = self, self._exec, self.precision
         B = src.shape[0]
         st = ex.stream(src)
         pad = f.padding + extra_pad
         if f.in_cg == 0:
-            ex.conv2d(L.view_split(src) if split[0] else L.view(src), pk['w_all'], L.view_split(dst) if split[1] else L.view(dst), B,
-                      f.kernel_size, f.stride, pad, L.PAD_REFLECT, False, pk['b_all'],
-                      act, None if resid is None else L.view(resid), precision=prec, stream=st)
-            return False
+            rt = ex.conv2d(L.view_split(src) if split[0] else L.view(src), pk['w_all'], L.view_split(dst) if split[1] else L.view(dst), B,
+                           f.kernel_size, f.stride, pad, L.PAD_REFLECT, False, pk['b_all'],
+                           act, None if resid is None else L.view(resid), precision=prec, stream=st, route=route)
+            return rt if route else False
         if split[0] or split[1]:
             raise LamaError('LAMA_DT_SPLIT16 tensors: layers without a global input only')
         cl, cg, ocl, ocg = f.in_cl, f.in_cg, f.out_cl, f.out_cg
@@ -868,7 +866,7 @@ class FFC_BN_ACT(_HipModule):
     # -- launch --------------------------------------------------------------------------------------
     def run(self, src: torch.Tensor, dst: torch.Tensor, scratch: Optional[dict], resid: Optional[torch.Tensor] = None,
             extra_pad: int = 0, side: Optional['torch.cuda.Stream'] = None, x1_ready: bool = False,
-            fuse_next: Optional['FFC_BN_ACT'] = None, split=(False, False)) -> bool:
+            fuse_next: Optional['FFC_BN_ACT'] = None, split=(False, False), route: bool = False) -> bool:
         f = self.ffc
         if f.in_cg and self._packed is not None and (f.convg2g._packed or {}).get('fused_scale') != id(self._packed.get('_sg')):
             self._packed = None   # a stand-alone SpectralTransform.forward / FFC.forward re-packed conv2 without bn_g
@@ -876,7 +874,7 @@ class FFC_BN_ACT(_HipModule):
         if fuse_next is not None and fuse_next.ffc.in_cg:
             fuse_next._pack()                                  # its conv1 weights must exist before they can ride along
             nxt = fuse_next.ffc.convg2g
-        return f.launch(self._pack(), self._act, src, dst, scratch, resid, extra_pad, side, x1_ready, nxt, split=split)
+        return f.launch(self._pack(), self._act, src, dst, scratch, resid, extra_pad, side, x1_ready, nxt, split=split, route=route)
 
     def out_shape(self, src_shape, extra_pad: int = 0):
         return self.ffc.out_shape(src_shape, extra_pad)
@@ -1336,34 +1334,31 @@ class FFCResNetGenerator(_PlanGenerator):
     def _presplit_edges(self, steps, bufs, shape) -> frozenset:
         """``presplit_outer``: the names of the plan buffers that hold LAMA_DT_SPLIT16 parts instead of fp32.  An edge qualifies when its buffer
         is written by an 'ffc' step without a global branch on either side and read by exactly one step, the NEXT one, a 3 x 3 stride-2 'ffc'
-        step without a global input -- and when the dedicated kernels take both launches: the conditions below are those of stem_try_launch /
-        cw_try_launch (conv_wreg_host.inc); a launch they refuse all the same raises (LAMA_ERR_UNSUPPORTED), it never falls back silently."""
+        step without a global input -- and when the library routes both launches, with the split element types, to the dedicated kernels
+        (lama_conv2d_route_query: the 7x7 stem kernel or the weights-in-registers kernel writes it, the weights-in-registers kernel reads it)."""
         if not self.presplit_outer or self.precision not in (L.PREC_F16X3, L.PREC_BF16X3):
             return frozenset()
-        ex = self._exec
-
-        def s2_conv(st, src_shape):          # the 4 x 1 weights-in-registers launch of the stride-2 convs
-            f, (_, C, H, W) = st[1].ffc, src_shape
-            return (f.in_cg == 0 and f.kernel_size == 3 and f.stride == 2 and f.padding + st[4] == 1 and C % 32 == 0
-                    and f.out_cl + f.out_cg >= 96 and (f.out_cl + f.out_cg) % 8 == 0 and C * H * W < (1 << 29))
-
-        def stem(st, src_shape, dst_shape):  # stem7_ws_kernel
-            f, (B, C, _, _), (_, M, Ho, Wo) = st[1].ffc, src_shape, dst_shape
-            return (f.in_cg == 0 and f.kernel_size == 7 and f.stride == 1 and f.padding + st[4] == 3 and C <= 4 and 33 <= M <= 64 and M % 8 == 0
-                    and Ho >= 4 and Wo >= 4 and 64 * Ho * Wo < (1 << 29) and B * Ho * ((Wo + 31) // 32) >= ex.presplit_stem_min_tiles)
-
-        def shape_of(name):
-            return tuple(shape) if name == 'in' else tuple(bufs[name].shape)
-
         split = set()
+        dev = next(iter(bufs.values())).device if bufs else None
+
+        def family(st, src_split, dst_split):      # of the step's launch with these element types; None where the library refuses it
+            lay, s, d, pad = st[1:5]
+            if lay.ffc.in_cg or (src_split and s == 'in'):
+                return None
+            src = torch.empty(tuple(shape), device=dev, dtype=torch.float32) if s == 'in' else bufs[s]
+            if any(t.dtype != torch.float32 or t.shape[1] % 8 for t, sp in ((src, src_split), (bufs[d], dst_split)) if sp):
+                return None
+            rc, fam, _ = lay.run(src, bufs[d], None, extra_pad=pad, split=(src_split, dst_split), route=True)
+            return fam if rc == 0 else None
+
         for i in range(len(steps) - 1):
             p, c = steps[i], steps[i + 1]
             if p[0] != 'ffc' or c[0] != 'ffc' or c[2] != p[3] or p[1].ffc.out_cg or sum(1 for st in steps if st[2] == p[3]) != 1:
                 continue
-            ps, ds = shape_of(p[2]), shape_of(p[3])
-            if ds[1] * ds[2] * ds[3] >= (1 << 29) or not s2_conv(c, ds):
+            if c[1].ffc.kernel_size != 3 or c[1].ffc.stride != 2:
                 continue
-            if stem(p, ps, ds) or s2_conv(p, ps):
+            if (family(p, p[2] in split, True) in (L.CONV_FAM_STEM7, L.CONV_FAM_CONV_WR)
+                    and family(c, True, False) == L.CONV_FAM_CONV_WR):
                 split.add(p[3])
         return frozenset(split)
 
@@ -1466,7 +1461,12 @@ class FFCResNetGenerator(_PlanGenerator):
     def _build_split_plan(self, shape, device, n: int) -> dict:
         B = int(shape[0])
         h = B // n
-        parts = [self._build_plan((h,) + tuple(shape[1:]), device, one_stream=True) for _ in range(n)]
+        ex = self._exec
+        keep, ex.siblings_log2 = ex.siblings_log2, n.bit_length() - 1     # the route queries of the plan builder ask about the parts' launches
+        try:
+            parts = [self._build_plan((h,) + tuple(shape[1:]), device, one_stream=True) for _ in range(n)]
+        finally:
+            ex.siblings_log2 = keep
         out_shape = (B,) + tuple(parts[0]['bufs'][parts[0]['out']].shape[1:])
         out_full = torch.empty(out_shape, device=device, dtype=parts[0]['bufs'][parts[0]['out']].dtype)
         for i, pl in enumerate(parts):

@@ -199,9 +199,7 @@ def make_model(ex_factory, dev, presplit, sd=None, head_only=False):
     if dev != 'cpu':
         m.to(dev)
     if ex_factory is not None:
-        ex = ex_factory()
-        ex.presplit_stem_min_tiles = 0          # the library of these tests takes the stem kernel at any size (LAMA_STEM_WS=2, tests/emu.py)
-        m.generator.set_exec(ex)
+        m.generator.set_exec(ex_factory())
     m.generator.presplit_outer = presplit
     if head_only:
         from lama_amd import ffc as F

@@ -29,76 +29,159 @@ def _conv_ref(x, w, stride, pad, reflect, transposed, bias, act, resid, x2=None,
 
 
 CONV_CASES = [
-    # cin, cout, k, stride, pad, reflect, transposed, H, W, act, bias, resid, scale
-    dict(cin=8, cout=16, k=3, stride=1, pad=1, H=12, W=20, act=1, bias=True, resid=True, scale=True),
-    dict(cin=12, cout=40, k=3, stride=1, pad=1, H=9, W=7, act=0, bias=False, resid=False, scale=False),
-    dict(cin=4, cout=8, k=7, stride=1, pad=3, H=16, W=24, act=1, bias=True, resid=False, scale=True),
-    dict(cin=8, cout=3, k=7, stride=1, pad=3, H=16, W=16, act=2, bias=True, resid=False, scale=False),
-    dict(cin=8, cout=16, k=3, stride=2, pad=1, H=16, W=24, act=1, bias=True, resid=False, scale=True),
-    dict(cin=6, cout=16, k=3, stride=2, pad=1, H=10, W=14, act=1, bias=True, resid=False, scale=True),
-    dict(cin=24, cout=12, k=1, stride=1, pad=0, H=6, W=11, act=1, bias=True, resid=False, scale=True),
-    dict(cin=40, cout=72, k=1, stride=1, pad=0, H=16, W=9, act=0, bias=False, resid=True, scale=False),
-    dict(cin=16, cout=8, k=3, stride=2, pad=1, H=8, W=12, act=1, bias=True, resid=False, scale=True, transposed=True),
-    dict(cin=20, cout=36, k=3, stride=2, pad=1, H=5, W=7, act=0, bias=True, resid=False, scale=False, transposed=True),
-    dict(cin=140, cout=130, k=3, stride=1, pad=1, H=8, W=8, act=1, bias=True, resid=True, scale=True),
-    dict(cin=24, cout=192, k=1, stride=1, pad=0, H=9, W=16, act=1, bias=True, resid=False, scale=True),     # 192-row M tiles (bf16x3)
-    dict(cin=20, cout=384, k=3, stride=1, pad=1, H=6, W=36, act=1, bias=True, resid=True, scale=False),
-    dict(cin=24, cout=70, k=3, stride=2, pad=1, H=9, W=34, act=1, bias=True, resid=False, scale=True, transposed=True),   # fused classes, BM=128
+    # cin, cout, k, stride, pad, reflect, transposed, H, W, act, bias, resid, scale; fam / fam_prod / egeo: the route the row promises under the
+    # two split precisions (expected_conv_route below), asserted through lama_conv2d_route_query before the launch
+    dict(cin=8, cout=16, k=3, stride=1, pad=1, H=12, W=20, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_LDS),
+    dict(cin=12, cout=40, k=3, stride=1, pad=1, H=9, W=7, act=0, bias=False, resid=False, scale=False, fam=L.CONV_FAM_LDS),
+    dict(cin=4, cout=8, k=7, stride=1, pad=3, H=16, W=24, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_LDS),
+    dict(cin=8, cout=3, k=7, stride=1, pad=3, H=16, W=16, act=2, bias=True, resid=False, scale=False, fam=L.CONV_FAM_LDS),
+    dict(cin=8, cout=16, k=3, stride=2, pad=1, H=16, W=24, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_LDS),
+    dict(cin=6, cout=16, k=3, stride=2, pad=1, H=10, W=14, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_LDS),
+    dict(cin=24, cout=12, k=1, stride=1, pad=0, H=6, W=11, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_LDS),
+    dict(cin=40, cout=72, k=1, stride=1, pad=0, H=16, W=9, act=0, bias=False, resid=True, scale=False, fam=L.CONV_FAM_LDS),
+    dict(cin=16, cout=8, k=3, stride=2, pad=1, H=8, W=12, act=1, bias=True, resid=False, scale=True, transposed=True, fam=L.CONV_FAM_LDS),
+    dict(cin=20, cout=36, k=3, stride=2, pad=1, H=5, W=7, act=0, bias=True, resid=False, scale=False, transposed=True, fam=L.CONV_FAM_LDS),
+    dict(cin=140, cout=130, k=3, stride=1, pad=1, H=8, W=8, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_LDS),
+    dict(cin=24, cout=192, k=1, stride=1, pad=0, H=9, W=16, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_LDS),     # 192 rows (at 4 pixel tiles cb_pick_bm keeps two 128-row tiles)
+    dict(cin=20, cout=384, k=3, stride=1, pad=1, H=6, W=36, act=1, bias=True, resid=True, scale=False, fam=L.CONV_FAM_LDS),
+    dict(cin=24, cout=70, k=3, stride=2, pad=1, H=9, W=34, act=1, bias=True, resid=False, scale=True, transposed=True, fam=L.CONV_FAM_LDS),   # fused classes, BM=128
     # weights-in-registers kernels (conv_wreg_dev.inc): 3x3 with cin % 32 == 0 / 1x1 with cin % 64 == 0, cout >= 96
-    dict(cin=64, cout=130, k=3, stride=1, pad=1, H=7, W=37, act=1, bias=True, resid=True, scale=True),      # ragged tiles, 2 M tiles
-    dict(cin=32, cout=96, k=3, stride=1, pad=1, H=5, W=6, act=0, bias=False, resid=False, scale=False),    # one chunk, narrow image
-    dict(cin=128, cout=100, k=1, stride=1, pad=0, H=9, W=15, act=1, bias=True, resid=True, scale=True),    # flat 1x1, two chunks
-    dict(cin=192, cout=200, k=1, stride=1, pad=0, H=12, W=11, act=2, bias=True, resid=False, scale=False),  # odd chunk count
+    dict(cin=64, cout=130, k=3, stride=1, pad=1, H=7, W=37, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_CONV_WR),      # ragged tiles, 2 M tiles
+    dict(cin=32, cout=96, k=3, stride=1, pad=1, H=5, W=6, act=0, bias=False, resid=False, scale=False, fam=L.CONV_FAM_CONV_WR),    # one chunk, narrow image
+    dict(cin=128, cout=100, k=1, stride=1, pad=0, H=9, W=15, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_CONV_WR),    # flat 1x1, two chunks
+    dict(cin=192, cout=200, k=1, stride=1, pad=0, H=12, W=11, act=2, bias=True, resid=False, scale=False, fam=L.CONV_FAM_LDS),  # odd chunk count; 7 row fragments: no 128-row tiling -> the LDS-staged kernel
     # ... the local conv's geometries by launch size (conv_wreg_host.inc), forced here with LAMA_CW_41: 3 = LAMA_CONV_COOPERATIVE's one
     # 4-wave workgroup per CU (32-channel chunks, six-deep A ring), 2 = two 4-wave workgroups per CU (16-channel chunks); row-rolling
     # and plain B reads each
-    dict(cin=64, cout=128, k=3, stride=1, pad=1, H=7, W=37, act=1, bias=True, resid=True, scale=True, geo=3),
-    dict(cin=96, cout=128, k=3, stride=1, pad=1, H=9, W=12, act=0, bias=False, resid=False, scale=False, geo=3),
-    dict(cin=64, cout=256, k=3, stride=1, pad=1, H=7, W=37, act=1, bias=True, resid=True, scale=True, geo=2),
-    dict(cin=96, cout=128, k=3, stride=1, pad=1, H=9, W=12, act=0, bias=False, resid=False, scale=False, geo=2),
+    dict(cin=64, cout=128, k=3, stride=1, pad=1, H=7, W=37, act=1, bias=True, resid=True, scale=True, geo=3, fam=L.CONV_FAM_CONV_WR, egeo=L.conv_geo_wr(4, 1, 2, 5, coop=1, roll=1)),
+    dict(cin=96, cout=128, k=3, stride=1, pad=1, H=9, W=12, act=0, bias=False, resid=False, scale=False, geo=3, fam=L.CONV_FAM_CONV_WR, egeo=L.conv_geo_wr(4, 1, 2, 4, coop=1)),
+    dict(cin=64, cout=256, k=3, stride=1, pad=1, H=7, W=37, act=1, bias=True, resid=True, scale=True, geo=2, fam=L.CONV_FAM_CONV_WR, egeo=L.conv_geo_wr(4, 1, 1, 5, roll=1)),
+    dict(cin=96, cout=128, k=3, stride=1, pad=1, H=9, W=12, act=0, bias=False, resid=False, scale=False, geo=2, fam=L.CONV_FAM_CONV_WR, egeo=L.conv_geo_wr(4, 1, 1, 4)),
     # ... ConvTranspose2d as ONE launch with all four parity classes in a wave (convt2_kernel, convt_dev.inc: cin % 32 == 0, cout % 64 == 0, W % 32 == 0, H % 4 == 0): one
     # tile / one chunk; 2 x 2 tiles, two chunks, two 64-row groups; and the fused LDS-staged launch on the same shape (LAMA_CT=0)
-    dict(cin=32, cout=64, k=3, stride=2, pad=1, H=4, W=32, act=1, bias=True, resid=False, scale=True, transposed=True),
-    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=0, bias=False, resid=False, scale=False, transposed=True),
-    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=0, bias=False, resid=False, scale=False, transposed=True, ct=0),
-    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=2, bias=True, resid=False, scale=True, transposed=True),            # sigmoid: not convt2_kernel's epilogue -> the fused LDS-staged launch
-    dict(cin=32, cout=64, k=3, stride=2, pad=1, H=5, W=37, act=1, bias=True, resid=False, scale=True, transposed=True),            # round 6: convt2_kernel with ragged last tiles (H % 4, W % 32 != 0)
-    dict(cin=64, cout=64, k=3, stride=2, pad=1, H=6, W=70, act=0, bias=False, resid=False, scale=False, transposed=True, ct_grid=2),
-    dict(cin=128, cout=64, k=3, stride=2, pad=1, H=12, W=32, act=1, bias=True, resid=False, scale=True, transposed=True, ct_grid=2),  # up3's channel counts: 8 sub-chunks, 6 tiles on 2 workgroups
-    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=1, bias=True, resid=False, scale=True, transposed=True, ct_grid=3),   # 16 tiles on 3 persistent workgroups
+    dict(cin=32, cout=64, k=3, stride=2, pad=1, H=4, W=32, act=1, bias=True, resid=False, scale=True, transposed=True, fam=L.CONV_FAM_CONVT2),
+    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=0, bias=False, resid=False, scale=False, transposed=True, fam=L.CONV_FAM_CONVT2),
+    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=0, bias=False, resid=False, scale=False, transposed=True, ct=0, fam=L.CONV_FAM_LDS, fam_prod=L.CONV_FAM_CONVT2, egeo=L.conv_geo_lds(128, 128, trf=1)),
+    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=2, bias=True, resid=False, scale=True, transposed=True, fam=L.CONV_FAM_LDS),            # sigmoid: not convt2_kernel's epilogue -> the fused LDS-staged launch
+    dict(cin=32, cout=64, k=3, stride=2, pad=1, H=5, W=37, act=1, bias=True, resid=False, scale=True, transposed=True, fam=L.CONV_FAM_CONVT2),            # round 6: convt2_kernel with ragged last tiles (H % 4, W % 32 != 0)
+    dict(cin=64, cout=64, k=3, stride=2, pad=1, H=6, W=70, act=0, bias=False, resid=False, scale=False, transposed=True, ct_grid=2, fam=L.CONV_FAM_CONVT2),
+    dict(cin=128, cout=64, k=3, stride=2, pad=1, H=12, W=32, act=1, bias=True, resid=False, scale=True, transposed=True, ct_grid=2, fam=L.CONV_FAM_CONVT2),  # up3's channel counts: 8 sub-chunks, 6 tiles on 2 workgroups
+    dict(cin=64, cout=128, k=3, stride=2, pad=1, H=8, W=64, act=1, bias=True, resid=False, scale=True, transposed=True, ct_grid=3, fam=L.CONV_FAM_CONVT2),   # 16 tiles on 3 persistent workgroups
     # ... stride 2 (the downsampling convs): parity-split patch columns, five staging units per thread; odd sizes, ragged tiles, 2 M tiles
-    dict(cin=32, cout=128, k=3, stride=2, pad=1, H=16, W=70, act=1, bias=True, resid=False, scale=True),
-    dict(cin=64, cout=200, k=3, stride=2, pad=1, H=11, W=37, act=0, bias=False, resid=True, scale=False),
-    # full-M 1x1 workgroups: 384 rows = 12 M-waves, 192 rows = 6 M-waves x 2 K-groups (K-group exchange + one residual set)
-    dict(cin=128, cout=384, k=1, stride=1, pad=0, H=5, W=33, act=1, bias=True, resid=True, scale=True),
-    dict(cin=192, cout=192, k=1, stride=1, pad=0, H=9, W=16, act=1, bias=True, resid=True, scale=True),
-    dict(cin=64, cout=370, k=1, stride=1, pad=0, H=3, W=50, act=0, bias=False, resid=False, scale=False),   # ragged rows, one chunk
+    dict(cin=32, cout=128, k=3, stride=2, pad=1, H=16, W=70, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_CONV_WR),
+    dict(cin=64, cout=200, k=3, stride=2, pad=1, H=11, W=37, act=0, bias=False, resid=True, scale=False, fam=L.CONV_FAM_CONV_WR),
+    # full-M 1x1 workgroups: 384 rows = 12 M-waves (192 rows = 6 M-waves x 2 K-groups exist for K % 64 == 0 other than 192 / 384: at K = 192 the
+    # persistent GEMM below comes first)
+    dict(cin=128, cout=384, k=1, stride=1, pad=0, H=5, W=33, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_CONV_WR, egeo=L.conv_geo_wr(12, 1, 4, 7)),
+    dict(cin=192, cout=192, k=1, stride=1, pad=0, H=9, W=16, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_GEMM1X1_WS, fam_prod=L.CONV_FAM_LDS),
+    dict(cin=64, cout=370, k=1, stride=1, pad=0, H=3, W=50, act=0, bias=False, resid=False, scale=False, fam=L.CONV_FAM_CONV_WR, egeo=L.conv_geo_wr(12, 1, 4, 7)),   # ragged rows, one chunk
     # weights-stationary persistent GEMM (conv_ws_dev.inc): K = 192 / 384, rows in groups of 96, ragged last tile, 1 / 2 / 4 row groups
-    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=5, W=21, act=1, bias=True, resid=True, scale=True),
-    dict(cin=192, cout=384, k=1, stride=1, pad=0, H=3, W=50, act=0, bias=False, resid=False, scale=False),
-    dict(cin=384, cout=180, k=1, stride=1, pad=0, H=8, W=33, act=2, bias=True, resid=False, scale=True),      # rows past M in the last fragment
+    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=5, W=21, act=1, bias=True, resid=True, scale=True, fam=L.CONV_FAM_GEMM1X1_WS, fam_prod=L.CONV_FAM_LDS),
+    dict(cin=192, cout=384, k=1, stride=1, pad=0, H=3, W=50, act=0, bias=False, resid=False, scale=False, fam=L.CONV_FAM_GEMM1X1_WS, fam_prod=L.CONV_FAM_CONV_WR),
+    dict(cin=384, cout=180, k=1, stride=1, pad=0, H=8, W=33, act=2, bias=True, resid=False, scale=True, fam=L.CONV_FAM_GEMM1X1_WS, fam_prod=L.CONV_FAM_LDS),      # rows past M in the last fragment
     # ... and over 64-pixel super-tiles of two interleaved MFMA tiles (gemm1x1_w4_kernel; LAMA_GEMM_W4=2 forces it at any launch size, LAMA_GEMM_W4_SLOTS
     # caps the workgroups per row group): super-tiles across the image boundary, groups past the batch, several rounds, left-over super-tiles, K = 192
-    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=7, W=38, act=1, bias=True, resid=True, scale=True, w4_slots=0),        # 532 pixels = 8.3 super-tiles, one round
-    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=7, W=38, act=1, bias=True, resid=True, scale=True, w4_slots=4),        # two rounds + one left-over super-tile
-    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=7, W=38, act=0, bias=False, resid=False, scale=False, w4_slots=2),     # four rounds + one left-over
-    dict(cin=192, cout=192, k=1, stride=1, pad=0, H=6, W=40, act=1, bias=True, resid=False, scale=False, w4_slots=3),     # K = 192, two row groups, two rounds + 2 whole left-overs
-    dict(cin=192, cout=96, k=1, stride=1, pad=0, H=6, W=40, act=1, bias=True, resid=True, scale=True, w4_slots=1),        # K = 192, eight rounds on one workgroup
-    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=1, bias=True, resid=True, scale=True, w4_slots=2),       # four row groups, 264 pixels
+    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=7, W=38, act=1, bias=True, resid=True, scale=True, w4_slots=0, fam=L.CONV_FAM_GEMM1X1_W4, fam_prod=L.CONV_FAM_LDS),        # 532 pixels = 8.3 super-tiles, one round
+    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=7, W=38, act=1, bias=True, resid=True, scale=True, w4_slots=4, fam=L.CONV_FAM_GEMM1X1_W4, fam_prod=L.CONV_FAM_LDS),        # two rounds + one left-over super-tile
+    dict(cin=384, cout=96, k=1, stride=1, pad=0, H=7, W=38, act=0, bias=False, resid=False, scale=False, w4_slots=2, fam=L.CONV_FAM_GEMM1X1_W4, fam_prod=L.CONV_FAM_LDS),     # four rounds + one left-over
+    dict(cin=192, cout=192, k=1, stride=1, pad=0, H=6, W=40, act=1, bias=True, resid=False, scale=False, w4_slots=3, fam=L.CONV_FAM_GEMM1X1_W4, fam_prod=L.CONV_FAM_LDS),     # K = 192, two row groups, two rounds + 2 whole left-overs
+    dict(cin=192, cout=96, k=1, stride=1, pad=0, H=6, W=40, act=1, bias=True, resid=True, scale=True, w4_slots=1, fam=L.CONV_FAM_GEMM1X1_W4, fam_prod=L.CONV_FAM_LDS),        # K = 192, eight rounds on one workgroup
+    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=1, bias=True, resid=True, scale=True, w4_slots=2, fam=L.CONV_FAM_GEMM1X1_W4, fam_prod=L.CONV_FAM_CONV_WR),       # four row groups, 264 pixels
     # ... and with all of K in one wave (gemm1x1_wk_kernel, gemm_wk_dev.inc; LAMA_GEMM_WK=2 forces it at any launch size, LAMA_GEMM_WK_SLOTS caps the
     # workgroups): 384 -> 384 only
-    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=1, bias=True, resid=False, scale=True, wk_slots=0),      # 264 pixels = 4.1 super-tiles, one round, ragged last one
-    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=1, bias=True, resid=False, scale=True, wk_slots=4),      # one round + 1 left-over = 24 units on four fifth waves
-    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=0, bias=False, resid=False, scale=False, wk_slots=2),    # left-over too big for the fifth waves: 3 / 2 rounds
-    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=20, W=40, act=1, bias=True, resid=False, scale=False, wk_slots=12),   # 25 super-tiles: two rounds + 24 units, two per fifth wave
-    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=7, W=38, act=1, bias=True, resid=False, scale=True, wk_slots=8),      # HW = 266: an image boundary inside a super-tile
+    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=1, bias=True, resid=False, scale=True, wk_slots=0, fam=L.CONV_FAM_GEMM1X1_WK, fam_prod=L.CONV_FAM_CONV_WR),      # 264 pixels = 4.1 super-tiles, one round, ragged last one
+    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=1, bias=True, resid=False, scale=True, wk_slots=4, fam=L.CONV_FAM_GEMM1X1_WK, fam_prod=L.CONV_FAM_CONV_WR),      # one round + 1 left-over = 24 units on four fifth waves
+    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=4, W=33, act=0, bias=False, resid=False, scale=False, wk_slots=2, fam=L.CONV_FAM_GEMM1X1_WK, fam_prod=L.CONV_FAM_CONV_WR),    # left-over too big for the fifth waves: 3 / 2 rounds
+    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=20, W=40, act=1, bias=True, resid=False, scale=False, wk_slots=12, fam=L.CONV_FAM_GEMM1X1_WK, fam_prod=L.CONV_FAM_GEMM1X1_WS),   # 25 super-tiles: two rounds + 24 units, two per fifth wave
+    dict(cin=384, cout=384, k=1, stride=1, pad=0, H=7, W=38, act=1, bias=True, resid=False, scale=True, wk_slots=8, fam=L.CONV_FAM_GEMM1X1_WK, fam_prod=L.CONV_FAM_GEMM1X1_WS),      # HW = 266: an image boundary inside a super-tile
     # stem kernel (conv_stem_dev.inc): 7x7, cin <= 4, 33..64 output channels; ragged last segment, rows past M, image narrower than a segment
-    dict(cin=4, cout=64, k=7, stride=1, pad=3, H=9, W=40, act=1, bias=True, resid=False, scale=True),
-    dict(cin=3, cout=40, k=7, stride=1, pad=3, H=6, W=20, act=0, bias=False, resid=False, scale=False),
+    dict(cin=4, cout=64, k=7, stride=1, pad=3, H=9, W=40, act=1, bias=True, resid=False, scale=True, fam=L.CONV_FAM_STEM7, fam_prod=L.CONV_FAM_LDS),
+    dict(cin=3, cout=40, k=7, stride=1, pad=3, H=6, W=20, act=0, bias=False, resid=False, scale=False, fam=L.CONV_FAM_STEM7, fam_prod=L.CONV_FAM_LDS),
     # head kernel (conv_head_dev.inc): 7x7, 64 input channels, <= 4 output channels; two 26-column segments (ragged), rows not a multiple of 7
-    dict(cin=64, cout=3, k=7, stride=1, pad=3, H=10, W=40, act=2, bias=True, resid=False, scale=False),
-    dict(cin=64, cout=4, k=7, stride=1, pad=3, H=16, W=26, act=0, bias=False, resid=False, scale=True),
+    dict(cin=64, cout=3, k=7, stride=1, pad=3, H=10, W=40, act=2, bias=True, resid=False, scale=False, fam=L.CONV_FAM_HEAD7, fam_prod=L.CONV_FAM_LDS),
+    dict(cin=64, cout=4, k=7, stride=1, pad=3, H=16, W=26, act=0, bias=False, resid=False, scale=True, fam=L.CONV_FAM_HEAD7, fam_prod=L.CONV_FAM_LDS),
 ]
+
+
+def expected_conv_route(case, prec, production=False):
+    """(family, geometry or None) a CONV_CASES row promises: ``fam`` under the two split precisions with the kernels forced at any size (the
+    emulator library and the profiling build: tests/emu.py), ``fam_prod`` where the production selection of liblama_hip.so differs at this
+    size; ``egeo`` where the row's comment promises a geometry (forced libraries only: production ignores LAMA_CW_41 and the like)."""
+    if prec == L.PREC_F32:
+        return L.CONV_FAM_F32, None
+    if production:
+        return case.get('fam_prod', case['fam']), None
+    return case['fam'], case.get('egeo')
+
+
+def assert_conv_route(lib, case, prec, args, kw, production=False, geometry=True):
+    rc, fam, geo = lib.conv2d(*args, route=True, **kw)
+    efam, egeo = expected_conv_route(case, prec, production)
+    assert (rc, fam) == (0, efam), (rc, fam, geo, efam)
+    if egeo is not None and geometry:
+        assert geo == egeo, (hex(geo), hex(egeo))
+
+
+def check_conv_route_contract(lib, dev='cpu', production=False):
+    """lama_conv2d_route_query against the launching entries on a handful of small CONV_CASES shapes, refusals included: the query's code is the
+    launch's code, a poisoned output is untouched after a query, and query-then-launch gives the bits of a launch alone."""
+    g = torch.Generator().manual_seed(77)
+    P = L.PREC_F16X3
+    st = torch.cuda.current_stream().cuda_stream if dev != 'cpu' else 0
+
+    def rnd(*shape, s=1.0):
+        return (torch.randn(*shape, generator=g) * s).to(dev)
+
+    def packed(cout, cin, k, stride=1, tr=False):
+        return lib.pack_conv_weight(rnd(*((cin, cout, k, k) if tr else (cout, cin, k, k)), s=0.2), None, stride=stride, transposed=tr, precision=P)
+
+    B = 2
+    lst = (torch.zeros(64, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), 16)
+    x384, x64, x4, x32, x24 = rnd(B, 384, 4, 33), rnd(B, 64, 8, 64), rnd(B, 4, 9, 40), rnd(B, 32, 6, 35), rnd(B, 24, 6, 35)
+    t64 = rnd(B, 64, 6, 35)
+    f1 = (packed(192, 384, 1), rnd(192), L.view(torch.zeros(B, 192, 6, 35, device=dev)))
+    w2 = packed(384, 64, 1)
+    forced = not production
+    rows = [   # name, x view, weights, output shape, split output, conv2d arguments behind batch, keywords, expected (code, family)
+        ('1x1_384', L.view(x384), packed(384, 384, 1), (B, 384, 4, 33), False, (1, 1, 0, L.PAD_REFLECT, False, None, L.ACT_RELU), {},
+         (0, L.CONV_FAM_GEMM1X1_WS if forced else L.CONV_FAM_CONV_WR)),
+        ('convt2', L.view(x64), packed(128, 64, 3, 2, True), (B, 128, 16, 128), False, (3, 2, 1, L.PAD_ZERO, True, None, L.ACT_RELU), {}, (0, L.CONV_FAM_CONVT2)),
+        ('stem7', L.view(x4), packed(64, 4, 7), (B, 64, 9, 40), False, (7, 1, 3, L.PAD_REFLECT, False, None, L.ACT_RELU), {},
+         (0, L.CONV_FAM_STEM7 if forced else L.CONV_FAM_LDS)),
+        # refusals: nothing serves the launch, LAMA_ERR_UNSUPPORTED from the query and from the entry alike
+        ('fuse1_refused', L.view(x24), packed(384, 24, 3), (B, 384, 6, 35), False, (3, 1, 1, L.PAD_REFLECT, False, None, L.ACT_RELU),
+         dict(x2=L.view(t64), w2_packed=w2, fuse1=f1), (L.ERR_UNSUPPORTED, None)),           # 24 input channels: not a shape of the 12 x 1 launch
+        ('split16_y_stride1', L.view(x32), packed(96, 32, 3), (B, 96, 6, 35), True, (3, 1, 1, L.PAD_REFLECT, False, None, L.ACT_RELU), {}, (L.ERR_UNSUPPORTED, None)),
+        ('list_stride1', L.view(x32), packed(96, 32, 3), (B, 96, 6, 35), False, (3, 1, 1, L.PAD_REFLECT, False, None, L.ACT_RELU), dict(tile_list=lst),
+         (L.ERR_UNSUPPORTED, None)),
+        ('list_convt2_sigmoid', L.view(x64), packed(128, 64, 3, 2, True), (B, 128, 16, 128), False, (3, 2, 1, L.PAD_ZERO, True, None, L.ACT_SIGMOID),
+         dict(tile_list=lst), (L.ERR_UNSUPPORTED, None)),                                     # sigmoid is not convt2_kernel's epilogue
+    ]
+    for name, xv, wp, yshape, ysplit, a, kw, (ecode, efam) in rows:
+        outs = []
+        for ask in (False, True):
+            y = torch.full(yshape, 7.0, device=dev)
+            yv = L.view_split(y) if ysplit else L.view(y)
+            if ask:
+                rc, fam, _ = lib.conv2d(xv, wp, yv, B, *a, precision=P, route=True, **kw)
+                assert (rc, fam) == (ecode, efam), (name, rc, fam)
+                assert bool((y == 7.0).all()), name                       # the query wrote nothing
+            try:
+                lib.conv2d(xv, wp, yv, B, *a, precision=P, stream=st, **kw)
+                code = 0
+            except L.LamaError as e:
+                code = e.code
+            if dev != 'cpu':
+                torch.cuda.synchronize()
+            assert code == ecode, (name, code)
+            outs.append(y.cpu())
+        assert torch.equal(outs[0], outs[1]), name                        # query-then-launch == launch alone, bit for bit
+        if ecode != 0:
+            assert bool((outs[0] == 7.0).all()), name                     # a refused launch wrote nothing
+
+
+def test_conv_route_contract_emulated():
+    check_conv_route_contract(emu_lib())
 
 
 PRECISIONS = [L.PREC_F32, L.PREC_BF16X3, L.PREC_F16X3]
@@ -136,9 +219,11 @@ def test_conv2d_emulated(case, prec, monkeypatch):
     wp = lib.pack_conv_weight(w, scale, stride=case['stride'], transposed=tr, precision=prec)
     # write into a channel slice of a wider buffer to exercise the view arithmetic
     ybuf = torch.full((B, cout + 3, ref.shape[2], ref.shape[3]), 7.0)
-    lib.conv2d(L.view(x), wp, L.view(ybuf, 2, cout), B, k, case['stride'], case['pad'],
-               L.PAD_ZERO if tr else L.PAD_REFLECT, tr, bias, case['act'], None if resid is None else L.view(resid), precision=prec,
-               cooperative=case.get('geo') == 3)
+    args = (L.view(x), wp, L.view(ybuf, 2, cout), B, k, case['stride'], case['pad'],
+            L.PAD_ZERO if tr else L.PAD_REFLECT, tr, bias, case['act'], None if resid is None else L.view(resid))
+    kw = dict(precision=prec, cooperative=case.get('geo') == 3)
+    assert_conv_route(lib, case, prec, args, kw)              # a case can only claim a kernel it can see
+    lib.conv2d(*args, **kw)
     y = ybuf[:, 2:2 + cout]
     assert torch.allclose(y, ref, **CONV_TOL[prec]), float((y - ref).abs().max())
     assert float(ybuf[:, :2].min()) == 7.0 and float(ybuf[:, -1].max()) == 7.0   # nothing written outside the view

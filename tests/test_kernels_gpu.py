@@ -11,7 +11,7 @@ from lama_amd import _lib as L
 pytestmark = pytest.mark.gpu
 
 from tests.test_kernels_emu import (WINO_CASES, CONV_CASES, CONV_TOL, F16_CASES, F16_MIXED, F16_STEM_HEAD, FFT_SIZES, PREC_IDS, PRECISIONS, _conv_f16_ref, _conv_ref,  # noqa: E402
-                                    _inv_ref, _spec_ref, check_fft_route_contract)
+                                    _inv_ref, _spec_ref, check_fft_route_contract, check_conv_route_contract, assert_conv_route)
 
 
 @pytest.fixture(scope='module')
@@ -43,7 +43,7 @@ DEV = 'cuda'
 
 @pytest.mark.parametrize('prec', PRECISIONS, ids=PREC_IDS)
 @pytest.mark.parametrize('case', CONV_CASES, ids=lambda c: f"k{c['k']}s{c['stride']}c{c['cin']}o{c['cout']}{'T' if c.get('transposed') else ''}{'w4s%d' % c['w4_slots'] if 'w4_slots' in c else ''}{'wks%d' % c['wk_slots'] if 'wk_slots' in c else ''}{'ct%d' % c['ct'] if 'ct' in c else ''}{'ctg%d' % c['ct_grid'] if 'ct_grid' in c else ''}")
-def test_conv2d(anylib, case, prec, monkeypatch):
+def test_conv2d(anylib, lib_forced, case, prec, monkeypatch):
     lib = anylib
     if 'ct' in case:
         monkeypatch.setenv('LAMA_CT', str(case['ct']))
@@ -71,8 +71,14 @@ def test_conv2d(anylib, case, prec, monkeypatch):
     rd = None if resid is None else resid.to(DEV)
     bd = None if bias is None else bias.to(DEV)
     st = torch.cuda.current_stream().cuda_stream
-    lib.conv2d(L.view(xd), wp, L.view(ybuf, 2, cout), B, k, case['stride'], case['pad'],
-               L.PAD_ZERO if tr else L.PAD_REFLECT, tr, bd, case['act'], None if rd is None else L.view(rd), precision=prec, stream=st)
+    args = (L.view(xd), wp, L.view(ybuf, 2, cout), B, k, case['stride'], case['pad'],
+            L.PAD_ZERO if tr else L.PAD_REFLECT, tr, bd, case['act'], None if rd is None else L.view(rd))
+    kw = dict(precision=prec)
+    if case.get('geo') and lib is lib_forced:   # the local conv's geometries, forced as in the emulator test (the production library reads no knob)
+        monkeypatch.setenv('LAMA_CW_41', str(case['geo']))
+        kw['cooperative'] = case['geo'] == 3
+    assert_conv_route(lib, case, prec, args, kw, production=lib is not lib_forced)
+    lib.conv2d(*args, stream=st, **kw)
     torch.cuda.synchronize()
     y = ybuf[:, 2:2 + cout].cpu()
     assert torch.allclose(y, ref, **CONV_TOL[prec]), float((y - ref).abs().max())
@@ -131,12 +137,12 @@ def test_conv2d_local_conv_geometries(lib, shape, prec):
     assert float((ys[0] - ys[1]).abs().max()) < (2e-4 if prec == L.PREC_BF16X3 else 2e-5)
 
 
-# Shapes on BOTH sides of every size threshold of the production kernel selection (conv_wreg_host.inc): the specialised kernel
-# just takes the launch / the launch just falls through to the next kernel in line.
-#   gw_try_launch   (persistent pointwise GEMM): C in {192, 384}, rows % 96 == 0, 32-pixel tiles x row groups >= 64
-#   cw_try_launch   (full-M 1x1 workgroups):     128-pixel tiles >= 96  (cin % 64 == 0, rows = 384 / 192, not taken by gw)
-#   stem_try_launch (7x7, cin <= 4):             B * H * ceil(W / 32) >= 4096
-#   head_try_launch (7x7, cin 64, cout <= 4):    B * ceil(W / 26) * H >= 8192
+# Shapes on BOTH sides of every size threshold of the production kernel selection (cb_route, conv_wreg_host.inc): the specialised kernel
+# just takes the launch / the launch just goes to the next family of the table.
+#   WS   (persistent pointwise GEMM): C in {192, 384}, rows % 96 == 0, 32-pixel tiles x row groups >= 64
+#   WR   (full-M 1x1 workgroups):     128-pixel tiles >= 96  (cin % 64 == 0, rows = 384 / 192, not taken by WS)
+#   STEM (7x7, cin <= 4):             B * H * ceil(W / 32) >= 4096
+#   HEAD (7x7, cin 64, cout <= 4):    B * ceil(W / 26) * H >= 8192
 THRESHOLD_SHAPES = [
     # B, cin, cout, k, H, W
     (2, 192, 96, 1, 32, 32), (2, 192, 96, 1, 31, 32),          # gw: 64 tiles x 1 group on / 62 off (-> 128-row wreg tiles refused: generic)
@@ -313,6 +319,11 @@ def test_fft_masked_entries(lib):
 def test_fft_route_contract(anylib):
     """The refusals and the no-workspace routes of the FFT entries, both directions (tests/test_kernels_emu.py check_fft_route_contract)."""
     check_fft_route_contract(anylib, DEV)
+
+
+def test_conv_route_contract(anylib, lib_forced):
+    """lama_conv2d_route_query against the launching entries, refusals included (tests/test_kernels_emu.py check_conv_route_contract)."""
+    check_conv_route_contract(anylib, DEV, production=anylib is not lib_forced)
 
 
 @pytest.mark.parametrize('n_seq', [(64, 1), (64, 2), (64, 3), (128, 2), (128, 3)], ids=lambda s: f'{s[0]}seq{s[1]}')
