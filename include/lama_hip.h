@@ -566,6 +566,23 @@ int    lama_range_stats_fwd(void* stream, const lama_tensor* x, int32_t batch, f
 int lama_fourier_unit_workspace_views(int32_t batch, int32_t C, int32_t h, int32_t w, int32_t dtype, void* workspace, size_t workspace_bytes,
                                       lama_tensor* spec_in, lama_tensor* spec_out);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) the local Fourier unit of SpectralTransform (ffc.py:136-138,148-159) ----
+ * With x1 [batch, C, h, h], q = C / 4 and s = h / 2 the reference forms xs_in = cat(split(cat(split(x1[:, :q], s, dim=-2), 1), s, dim=-1), 1), runs a
+ * second FourierUnit on it and adds xs.repeat(1, 1, 2, 2) to x1 + fu(x1).  The two data movements around that FourierUnit:
+ *   lama_lfu_gather_fwd:   y[b, (2 j + i) q + c, yy, xx] = x[b, c, i s + yy, j s + xx]   c < q; i, j in {0, 1}; yy, xx < s.  x: a [batch, q, h, h] view
+ *                          (the first quarter of x1's channels, batch_stride that of x1), y: [batch, 4 q, s, s].  A copy: bit-exact.
+ *   lama_lfu_tile_add_fwd: out[b, c, y, x] = a[b, c, y, x] + xs[b, c, y mod s, x mod s].  a, out: [batch, C, h, h], xs: [batch, C, s, s]; out may be a
+ *                          itself (in place), xs overlaps neither.  One fp32 add per element; fp16 tensors: the add in fp32, rounded once.
+ * Element types LAMA_DT_F32 or LAMA_DT_F16, every tensor of a call the same.  Any batch_stride >= C H W, channel-slice views, any element-aligned start:
+ * 16-byte accesses where a row of s elements, the pointers and the batch strides allow, narrower ones (down to one element) where they do not.  One
+ * launch each, plain vector loads and stores, no atomics, no workspace: asynchronous and hipGraph-capturable.  Like the reference (which splits BOTH axes
+ * by h / 2) only square planes with an even side.
+ * LAMA_ERR_BAD_ARG: a null pointer, batch <= 0, an empty view, shapes that do not match the above, batch_stride < C H W, a pointer that is not
+ * element-aligned; LAMA_ERR_UNSUPPORTED: H != W or odd H (of x / a), an unknown or mixed dtype, LAMA_DT_SPLIT16, a plane of 2^30 pieces or more.
+ * Nothing is launched on an error. */
+int lama_lfu_gather_fwd(void* stream, const lama_tensor* x, const lama_tensor* y, int32_t batch);
+int lama_lfu_tile_add_fwd(void* stream, const lama_tensor* a, const lama_tensor* xs, const lama_tensor* out, int32_t batch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -243,6 +243,8 @@ class LamaLib:
         L.lama_range_stats_workspace_bytes.restype, L.lama_range_stats_workspace_bytes.argtypes = sz, [i32] * 4
         L.lama_range_stats_fwd.restype, L.lama_range_stats_fwd.argtypes = C.c_int, [vp, T, i32, C.c_float, vp, vp, sz]
         L.lama_fourier_unit_workspace_views.restype, L.lama_fourier_unit_workspace_views.argtypes = C.c_int, [i32, i32, i32, i32, i32, vp, sz, T, T]
+        L.lama_lfu_gather_fwd.restype, L.lama_lfu_gather_fwd.argtypes = C.c_int, [vp, T, T, i32]
+        L.lama_lfu_tile_add_fwd.restype, L.lama_lfu_tile_add_fwd.argtypes = C.c_int, [vp, T, T, T, i32]
         del dp
         if L.lama_version() != ABI_VERSION:
             raise LamaError(f'{path}: ABI version {L.lama_version()} != {ABI_VERSION}')
@@ -545,6 +547,15 @@ class LamaLib:
         self.check(self._l.lama_range_stats_fwd(stream, C.byref(x), batch, float(limit), out.data_ptr(), ws.data_ptr(),
                                                 ws.numel() * ws.element_size()), 'lama_range_stats_fwd')
         return out
+
+    # -- local Fourier unit (lfu.hip) ----------------------------------------------------------------
+    def lfu_gather(self, x: Tensor4, y: Tensor4, batch: int, stream: int = 0):
+        """y [B, 4q, h/2, h/2] = the four quadrants of x [B, q, h, h] stacked along the channels, row half fastest (ffc.py:152-155)."""
+        self.check(self._l.lama_lfu_gather_fwd(stream, C.byref(x), C.byref(y), batch), 'lama_lfu_gather_fwd')
+
+    def lfu_tile_add(self, a: Tensor4, xs: Tensor4, out: Tensor4, batch: int, stream: int = 0):
+        """out = a + xs.repeat(1, 1, 2, 2) (ffc.py:156-161); ``out`` may be ``a``."""
+        self.check(self._l.lama_lfu_tile_add_fwd(stream, C.byref(a), C.byref(xs), C.byref(out), batch), 'lama_lfu_tile_add_fwd')
 
     # -- elementwise -------------------------------------------------------------------------------
     def mask_compose(self, image: Tensor4, mask: Tensor4, out: Tensor4, batch: int, stream: int = 0):

@@ -10,7 +10,8 @@ only -- their ``forward`` is never called; all arithmetic goes through ``lama_am
 library must be built, otherwise ``LamaError`` is raised.
 
 Inference only (eval-mode BatchNorm folded into the conv weights; reference ffc.py:60-61,101,
-130-133,236-239,253-254).  Options no shipped config enables (LFU, SE, gates, spectral positional
+130-133,236-239,253-254).  The local Fourier unit (enable_lfu=True, the reference classes' default) is SpectralTransformLFU, on the
+square even-sided planes the reference's own LFU runs on.  Options no shipped config enables (SE, gates, spectral positional
 encoding, spatial scaling, 3-D FFC, groups != 1, spatial-transform wrappers, out_ffc) raise
 ``NotImplementedError`` at construction.
 """
@@ -543,12 +544,14 @@ class FourierUnit(_HipModule):
 
 
 class SpectralTransform(_HipModule):
-    """ffc.py:116-163 with stride 1 and LFU disabled: conv2(x1 + fu(x1)), x1 = relu(bn(conv1(x)))."""
+    """ffc.py:116-163 with stride 1 and LFU disabled: conv2(x1 + fu(x1)), x1 = relu(bn(conv1(x))).  The local Fourier unit is the
+    subclass SpectralTransformLFU (FFC constructs it when ``enable_lfu`` is set)."""
 
     def __init__(self, in_channels, out_channels, stride=1, groups=1, enable_lfu=True, **fu_kwargs):
         super().__init__()
-        if enable_lfu:
-            raise NotImplementedError('SpectralTransform: enable_lfu=True is not used by any shipped LaMa config')
+        if enable_lfu and not isinstance(self, SpectralTransformLFU):
+            raise NotImplementedError('SpectralTransform: enable_lfu=True is served by the subclass SpectralTransformLFU '
+                                      '(FFC / FFC_BN_ACT / FFCResnetBlock construct it when enable_lfu is set)')
         if stride != 1 or groups != 1:
             raise NotImplementedError('SpectralTransform: stride 2 / groups != 1 are not implemented')
         self.enable_lfu = enable_lfu
@@ -569,14 +572,25 @@ class SpectralTransform(_HipModule):
         return self._packed
 
     def run_front(self, xg: L.Tensor4, x1: torch.Tensor, t: torch.Tensor, ws: torch.Tensor, batch: int, stream: int,
-                  x1_ready: bool = False, wino_out=None):
+                  x1_ready: bool = False, wino_out=None, lfu: Optional[tuple] = None):
         """x1 = relu(bn(conv1(xg))); t = x1 + fu(x1).  (conv2 is fused by the caller.)  ``x1_ready``: the producer of xg already
         wrote x1 from its epilogue (fuse1_operands).  ``wino_out``: the deferred output transform of the previous layer's Winograd local
-        conv, finished inside this FourierUnit's first launch (round 4)."""
+        conv, finished inside this FourierUnit's first launch (round 4).  ``lfu``: the buffers of the local Fourier unit
+        (FFC.make_scratch; SpectralTransformLFU only)."""
         pk = self._packed
         if not x1_ready:
             self._exec.conv2d(xg, pk['w1'], L.view(x1), batch, 1, bias=pk['b1'], act=L.ACT_RELU, precision=self.precision, stream=stream)
+        self._spectral(x1, t, ws, batch, stream, wino_out, lfu)
+
+    def _spectral(self, x1: torch.Tensor, t: torch.Tensor, ws: torch.Tensor, batch: int, stream: int, wino_out, lfu):
         self.fu.run(L.view(x1), L.view(t), batch, True, ws, stream, wino_out=wino_out)
+
+    def _pack_units(self):
+        self.fu._pack()
+
+    def scratch(self, x1: torch.Tensor, own_lfu_ws: bool = False) -> dict:
+        """What ``run_front`` needs besides x1 and t: the FourierUnit's workspace."""
+        return dict(ws=self.fu.workspace(x1))
 
     def fuse1_operands(self, x1: torch.Tensor) -> Optional[tuple]:
         """(packed conv1 weights in the channel order of the producing kernel's accumulators, BatchNorm shift, x1 view) for the
@@ -606,10 +620,69 @@ class SpectralTransform(_HipModule):
             x1 = torch.empty(b, half, h, w, device=x.device, dtype=x.dtype)
             t = torch.empty_like(x1)
             st = self._exec.stream(x)
-            self.run_front(L.view(x), x1, t, self.fu.workspace(x1), b, st)
+            sc = self.scratch(x1)
+            self.run_front(L.view(x), x1, t, sc['ws'], b, st, lfu=sc.get('lfu'))
             y = torch.empty(b, self.conv2.out_channels, h, w, device=x.device, dtype=x.dtype)
             self._exec.conv2d(L.view(t), self._packed['w2'], L.view(y), b, 1, precision=self.precision, stream=st)
         return y
+
+
+class SpectralTransformLFU(SpectralTransform):
+    """ffc.py:116-163 with the local Fourier unit (ffc.py:136-138,148-159): with x1 [B, C, h, h], q = C / 4 and s = h / 2
+
+        xs_in[b, (2 j + i) q + c, y, x] = x1[b, c, i s + y, j s + x]        (lama_lfu_gather_fwd; the row half i is the fast index)
+        xs = lfu(xs_in)                                                      (a second FourierUnit(C, C), on s x s planes)
+        t  = (x1 + fu(x1)) + xs.repeat(1, 1, 2, 2)                           (lama_lfu_tile_add_fwd, in place over t)
+
+    and conv2(t) as without it.  Like the reference -- which splits BOTH axes by h // 2 -- square planes with an even side only, and
+    C % 4 == 0."""
+
+    def __init__(self, in_channels, out_channels, stride=1, groups=1, enable_lfu=True, **fu_kwargs):
+        if not enable_lfu:
+            raise ValueError('SpectralTransformLFU is the SpectralTransform with enable_lfu=True')
+        if (out_channels // 2) % 4:
+            raise NotImplementedError(f'SpectralTransformLFU: the local Fourier unit splits the first quarter of the {out_channels // 2} '
+                                      'channels of x1 four ways: out_channels // 2 must be a multiple of 4 (the reference fails there too)')
+        super().__init__(in_channels, out_channels, stride, groups, True, **fu_kwargs)
+        self.lfu = FourierUnit(out_channels // 2, out_channels // 2, groups)
+
+    @staticmethod
+    def check_plane(h: int, w: int):
+        if h != w or h % 2:
+            raise LamaError(f'SpectralTransformLFU: the reference\'s LFU splits both axes by h // 2, so it runs on square planes with an '
+                            f'even side only; this plane is {h} x {w} (a generator with three downsamplings takes square inputs whose '
+                            'side is a multiple of 16)')
+
+    def _pack_units(self):
+        self.fu._pack()
+        self.lfu._pack()
+
+    def scratch(self, x1: torch.Tensor, own_lfu_ws: bool = False) -> dict:
+        """The gather output and the LFU's output, [B, C, h/2, h/2] each.  The LFU runs behind the main FourierUnit on the same stream, when
+        that one's spectra are dead: it works in the same workspace (``own_lfu_ws``: in one of its own -- probe.py reads both units' spectra)."""
+        B, C1, H, W = x1.shape
+        self.check_plane(H, W)
+        ws = self.fu.workspace(x1)
+        xs_in = torch.empty(B, C1, H // 2, W // 2, device=x1.device, dtype=x1.dtype)
+        need = self._exec.lib.fourier_unit_workspace_bytes(B, C1, H // 2, W // 2)
+        own = own_lfu_ws or need > ws.numel() * ws.element_size()
+        return dict(ws=ws, lfu=(xs_in, torch.empty_like(xs_in), self.lfu.workspace(xs_in) if own else None))      # None: the main unit's
+
+    def run_front(self, xg: L.Tensor4, x1: torch.Tensor, t: torch.Tensor, ws: torch.Tensor, batch: int, stream: int,
+                  x1_ready: bool = False, wino_out=None, lfu: Optional[tuple] = None):
+        self.check_plane(x1.shape[2], x1.shape[3])             # (before anything is launched)
+        if lfu is None:
+            raise LamaError('SpectralTransformLFU.run_front: the scratch set has no LFU buffers (FFC.make_scratch allocates them)')
+        super().run_front(xg, x1, t, ws, batch, stream, x1_ready, wino_out, lfu)
+
+    def _spectral(self, x1: torch.Tensor, t: torch.Tensor, ws: torch.Tensor, batch: int, stream: int, wino_out, lfu):
+        xs_in, xs, ws_lfu = lfu
+        lib = self._exec.lib
+        # the gather FIRST: with t aliased to x1 (FFC.make_scratch alias_t) the main irfft2 overwrites x1 with x1 + fu(x1)
+        lib.lfu_gather(L.view(x1, 0, x1.shape[1] // 4), L.view(xs_in), batch, stream)
+        self.fu.run(L.view(x1), L.view(t), batch, True, ws, stream, wino_out=wino_out)
+        self.lfu.run(L.view(xs_in), L.view(xs), batch, False, ws if ws_lfu is None else ws_lfu, stream)
+        lib.lfu_tile_add(L.view(t), L.view(xs), L.view(t), batch, stream)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -643,8 +716,8 @@ class FFC(_HipModule):
         self.convl2l = nn.Identity() if in_cl == 0 or out_cl == 0 else conv(in_cl, out_cl)
         self.convl2g = nn.Identity() if in_cl == 0 or out_cg == 0 else conv(in_cl, out_cg)
         self.convg2l = nn.Identity() if in_cg == 0 or out_cl == 0 else conv(in_cg, out_cl)
-        self.convg2g = nn.Identity() if in_cg == 0 or out_cg == 0 else SpectralTransform(in_cg, out_cg, stride, 1, enable_lfu,
-                                                                                         **spectral_kwargs)
+        spectral = SpectralTransformLFU if enable_lfu else SpectralTransform
+        self.convg2g = nn.Identity() if in_cg == 0 or out_cg == 0 else spectral(in_cg, out_cg, stride, 1, enable_lfu, **spectral_kwargs)
         self.gated = gated
         self.gate = nn.Identity()
         if in_cl == 0:
@@ -692,7 +765,7 @@ class FFC(_HipModule):
             st._packed = None
             st._pack(sg)
             st._packed['fused_scale'] = id(sg) if sg is not None else 'none'
-            st.fu._pack()
+            st._pack_units()
         return pk
 
     # -- launch --------------------------------------------------------------------------------------
@@ -749,13 +822,16 @@ class FFC(_HipModule):
             ex.conv2d(L.view(src), pk['w_lout'], L.view(dst, 0, ocl), B, 3, 1, pad, L.PAD_REFLECT, False, pk['b_l'], act, rl, precision=prec,
                       stream=stream, cooperative=cooperative)
 
+        def front(stream, **kw):
+            spec.run_front(L.view(src, cl, cg), scratch['x1'], scratch['t'], scratch['ws'], B, stream, x1_ready, lfu=scratch.get('lfu'), **kw)
+
         if isinstance(side, SidePipe) and src.is_cuda:
             main = torch.cuda.current_stream(src.device)
             side.stream.wait_stream(main)               # the previous layer's global launch (x_g) -- and every reader of dst's x_l slice
             local_conv(side.stream.cuda_stream, True)
             done = torch.cuda.Event()
             done.record(side.stream)
-            spec.run_front(L.view(src, cl, cg), scratch['x1'], scratch['t'], scratch['ws'], B, st, x1_ready)
+            front(st)
             if side.prev_local is not None:
                 main.wait_event(side.prev_local)        # the global launch reads x_l written by the previous layer's local conv, and
             side.prev_local = done                      # overwrites an x_g slice that local convs up to that one have read
@@ -763,13 +839,13 @@ class FFC(_HipModule):
             main = torch.cuda.current_stream(src.device)
             side.wait_stream(main)                      # fork: src (and the scratch buffers' last readers) are ordered before
             if not ex.local_first:
-                spec.run_front(L.view(src, cl, cg), scratch['x1'], scratch['t'], scratch['ws'], B, side.cuda_stream, x1_ready)
+                front(side.cuda_stream)
             local_conv(st, True)
             if ex.local_first:
-                spec.run_front(L.view(src, cl, cg), scratch['x1'], scratch['t'], scratch['ws'], B, side.cuda_stream, x1_ready)
+                front(side.cuda_stream)
             main.wait_stream(side)                      # join: t is ready for the global conv
         else:
-            spec.run_front(L.view(src, cl, cg), scratch['x1'], scratch['t'], scratch['ws'], B, st, x1_ready, wino_out=scratch.pop('pending_out', None))
+            front(st, wino_out=scratch.pop('pending_out', None))
             local_conv(st, ex.cooperative_serial)
         # the global branch; by the time it runs this layer's own x1 has been consumed (rfft2 and the x + fu(x) add are upstream of t)
         fuse1 = None
@@ -801,15 +877,16 @@ class FFC(_HipModule):
         Wo = (W + 2 * pad - self.kernel_size) // self.stride + 1
         return (B, self.out_cl + self.out_cg, Ho, Wo)
 
-    def make_scratch(self, src_shape, device, alias_t: bool = False) -> Optional[dict]:
+    def make_scratch(self, src_shape, device, alias_t: bool = False, own_lfu_ws: bool = False) -> Optional[dict]:
         """``alias_t``: t = x1 + fu(x1) is written over x1 (irfft2 reads the residual element where it writes; the global-branch launch reads t
-        for the pixels of a tile before its epilogue writes the NEXT layer's x1 for the same pixels)."""
+        for the pixels of a tile before its epilogue writes the NEXT layer's x1 for the same pixels).  A layer with a local Fourier unit adds
+        its buffers (SpectralTransformLFU.scratch; raises LamaError for a plane the LFU does not take)."""
         if self.in_cg == 0:
             return None
         B, _, H, W = src_shape
         half = self.convg2g.conv2.in_channels
         x1 = torch.empty(B, half, H, W, device=device, dtype=_act_dtype(self.precision))
-        sc = dict(x1=x1, t=x1 if alias_t else torch.empty_like(x1), ws=self.convg2g.fu.workspace(x1))
+        sc = dict(x1=x1, t=x1 if alias_t else torch.empty_like(x1), **self.convg2g.scratch(x1, own_lfu_ws))
         lib = self._exec.lib
         if (self._exec.winograd and self.kernel_size == 3 and self.stride == 1 and self.padding == 1 and self.out_cl
                 and lib.winograd_preferred(B, self.out_cl, self.in_cl + self.in_cg, H, W, self.precision)):
@@ -879,8 +956,8 @@ class FFC_BN_ACT(_HipModule):
     def out_shape(self, src_shape, extra_pad: int = 0):
         return self.ffc.out_shape(src_shape, extra_pad)
 
-    def make_scratch(self, src_shape, device, alias_t: bool = False) -> Optional[dict]:
-        return self.ffc.make_scratch(src_shape, device, alias_t)
+    def make_scratch(self, src_shape, device, alias_t: bool = False, own_lfu_ws: bool = False) -> Optional[dict]:
+        return self.ffc.make_scratch(src_shape, device, alias_t, own_lfu_ws)
 
     def forward(self, x, extra_pad: int = 0):
         x_l, x_g = x if type(x) is tuple else (x, 0)

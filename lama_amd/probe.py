@@ -208,13 +208,26 @@ def _spectral_rows(m: _Meter, lay: 'F.FFC_BN_ACT', name: str, scratch: dict):
             flat = ws.view(torch.uint8)[v.ptr - ws.data_ptr():][:B * v.batch_stride * x1.element_size()]
             kept = flat.view(x1.dtype).view(B, v.C, v.H, v.W)
         m.view(nm, p + '.fu.conv_layer', v, B, kept)
+    if 'lfu' in scratch:
+        # the local Fourier unit (SpectralTransformLFU): its input (the gathered quadrants of x1), and the operand and the output of its spectral
+        # 1x1 in the workspace of its own that _ffc_layer asked for; ':t' below then includes the tiled LFU output
+        xs_in, _, ws_l = scratch['lfu']
+        s = xs_in.shape[2]
+        m.tensor(p + '.lfu:in', p + '.lfu', xs_in)
+        si, so = m.lib.fourier_unit_views(ws_l, B, C1, s, s, dt)
+        for nm, v in ((p + '.lfu:spectrum', si), (p + '.lfu:spectrum_out', so)):
+            kept = None
+            if m.keep:
+                flat = ws_l.view(torch.uint8)[v.ptr - ws_l.data_ptr():][:B * v.batch_stride * x1.element_size()]
+                kept = flat.view(x1.dtype).view(B, v.C, v.H, v.W)
+            m.view(nm, p + '.lfu.conv_layer', v, B, kept)
     m.tensor(p + ':t', p + '.conv2', t)
 
 
 def _ffc_layer(m: _Meter, lay: 'F.FFC_BN_ACT', name: str, src: torch.Tensor, dst: torch.Tensor, src_rows, resid=None, pad: int = 0):
     """One FFC_BN_ACT through its stand-alone path with a scratch set of the probe's own; returns nothing, measures the inner tensors."""
     f = lay.ffc
-    scratch = lay.make_scratch(src.shape, src.device)
+    scratch = lay.make_scratch(src.shape, src.device, own_lfu_ws=True)      # (both units' spectra are read below)
     _with_fallback(m, lay, name, name, lambda: lay.run(src, dst, scratch, resid, pad))
     if f.in_cg:
         _spectral_rows(m, lay, name, scratch)

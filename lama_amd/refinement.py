@@ -289,6 +289,14 @@ def _first_resblock(model) -> Tuple[int, int]:
     return first_resblock_ind, n_resnet_blocks
 
 
+def _refuse_lfu(gen, who: str):
+    """The reverse pass (lama_amd/backward.py) has no adjoints of the local Fourier unit: refuse before anything is launched."""
+    for name, m in gen.named_modules():
+        if isinstance(m, ffc.SpectralTransformLFU):
+            raise NotImplementedError(f'{who}: refinement of a generator with a local Fourier unit (enable_lfu=True; {name}.lfu) is not '
+                                      'implemented: the reverse pass has no LFU adjoints')
+
+
 def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: int, lr: float, min_side: int, max_scales: int,
                    px_budget: int, trace: Optional[list] = None, bwd_precision: Optional[int] = None):
     """refinement.py:228-314: coarse-to-fine refinement of the features after generator.model[:first_resblock].
@@ -305,6 +313,7 @@ def refine_predict(batch: dict, inpainter, gpu_ids: str, modulo: int, n_iters: i
         # refinement.py:128 unpacks ``z1, z2 = forward_front(...)``: only an FFC front returns the (x_l, x_g) pair, so the reference cannot
         # refine a pix2pixhd_global generator either
         raise NotImplementedError(f'refine=True needs an ffc_resnet generator; {type(gen).__name__} has no (local, global) feature pair to refine')
+    _refuse_lfu(gen, 'refine_predict')
     model = gen.model
     first_resblock_ind, n_resnet_blocks = _first_resblock(model)
     if not n_resnet_blocks:
@@ -382,6 +391,7 @@ def refine_predict_batch(batch: dict, inpainter, gpu_ids: str, modulo: int, n_it
     gen = inpainter.generator
     if not isinstance(gen, ffc.FFCResNetGenerator):
         raise NotImplementedError(f'refine=True needs an ffc_resnet generator; {type(gen).__name__} has no (local, global) feature pair to refine')
+    _refuse_lfu(gen, 'refine_predict_batch')
     first_resblock_ind, n_resnet_blocks = _first_resblock(gen.model)
     if not n_resnet_blocks:
         raise LamaError('refine_predict_batch: the generator has no resnet blocks')
