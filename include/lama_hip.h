@@ -583,6 +583,30 @@ int lama_fourier_unit_workspace_views(int32_t batch, int32_t C, int32_t h, int32
 int lama_lfu_gather_fwd(void* stream, const lama_tensor* x, const lama_tensor* y, int32_t batch);
 int lama_lfu_tile_add_fwd(void* stream, const lama_tensor* a, const lama_tensor* xs, const lama_tensor* out, int32_t batch);
 
+/* ---- (added to v112 without a version bump: one new symbol, nothing else changes) paste_back: the result of a dataset.scale_factor step resampled
+ * to the SOURCE grid and pasted into the decoded u8 original, in one launch.  THIS OUTPUT HAS NO COUNTERPART IN THE REFERENCE, which writes the
+ * scaled image (bin/predict.py:86-94): it is this engine's own definition, pinned byte for byte by tests/paste_back_util.py::paste_back_ref.
+ * image_hwc [B][Hs][Ws][3], mask [B][Hs][Ws], out_hwc [B][Hs][Ws][3]: u8 source slots on the device, each image's own h x w pixels in the
+ * top-left corner; src_sizes / dst_sizes: device int32 [B][2] = (h, w) / (dh, dw), the arrays lama_resize_u8_fwd takes (h = 0: an empty slot);
+ * lowres: fp32 [B,3,Hp,Wp] of which [:dh, :dw] is valid and nothing else is read (any batch_stride >= 3 Hp Wp: channel-slice views work).
+ * For image b and source pixel (y, x), y < h, x < w:
+ *   v = F.interpolate(lowres[b, :, :dh, :dw], size=(h, w), mode='bilinear', align_corners=False)[:, y, x] -- BILINEAR, the index arithmetic of
+ *     lama_bilinear_fwd: sy = (float)dh / (float)h (IEEE fp32), s = max(0, (y + 0.5f) * sy - 0.5f), i0 = min((int)s, dh - 1), i1 = min(i0 + 1, dh - 1),
+ *     l = s - i0, the same in x; v = (1 - ly) * ((1 - lx) * v00 + lx * v01) + ly * ((1 - lx) * v10 + lx * v11), every operation rounded on its own
+ *     (no floating-point contraction anywhere in the kernel);
+ *   binarize != 0: mask > 0 -> clip(v * 255, 0, 255) truncated, else the three source bytes;
+ *   binarize == 0: m = mask / 255.f, r = m * v + (1 - m) * (u8 / 255.f), byte = clip(r * 255, 0, 255) truncated (= the source byte where m = 0;
+ *     lowres is read only where the mask byte is not 0).  A NaN quantises to 0, as in lama_blend_quantize_u8_fwd.
+ * Slot bytes outside h x w are written as 0; so is a whole slot that is empty or whose sizes do not fit (h > Hs, w > Ws, dh > Hp, dw > Wp, dh or
+ * dw < 1): the sizes are device data, nothing is read or written out of bounds.  7 bytes per source pixel (1 + 3 read, 3 written); dword accesses
+ * where Ws % 4 == 0 and the three slot pointers are 4-byte aligned, byte accesses otherwise.  One launch, no workspace, no atomics:
+ * asynchronous and hipGraph-capturable.
+ * LAMA_ERR_BAD_ARG: a null pointer; batch, Hs or Ws <= 0; a view that is not [., 3, H, W]; batch_stride < 3 H W; a view pointer that is not
+ * 4-byte aligned; out_hwc == image_hwc.  LAMA_ERR_UNSUPPORTED: a view that is not fp32; a slot of 2^30 work items (of 4 pixels) or more; a view plane of 2^30 elements or more.
+ * Nothing is launched on an error. */
+int lama_paste_back_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes, int32_t Hs,
+                           int32_t Ws, const lama_tensor* lowres, uint8_t* out_hwc, int32_t batch, int32_t binarize);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,8 @@ class LamaLib:
         L.lama_blend_quantize_u8_fwd.argtypes = [vp, vp, vp, vp, T, vp, i32, i32]
         L.lama_resize_u8_fwd.restype = C.c_int
         L.lama_resize_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, T, T, i32, i32]
+        L.lama_paste_back_u8_fwd.restype = C.c_int
+        L.lama_paste_back_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, vp, i32, i32]
         L.lama_eval_ingest_u8_fwd.restype = C.c_int
         L.lama_eval_ingest_u8_fwd.argtypes = [vp, vp, vp, vp, C.POINTER(i32), i32, i32, i32, i32, C.c_float, C.c_float, T, T, vp, i32]
         L.lama_affine_act_fwd.restype = C.c_int
@@ -590,6 +592,24 @@ class LamaLib:
         self.check(self._l.lama_resize_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
                                               int(image_hwc.shape[1]), int(image_hwc.shape[2]), float(factor), C.byref(out_image), C.byref(out_mask),
                                               batch, int(bool(binarize))), 'lama_resize_u8_fwd')
+
+    def paste_back_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, dst_sizes: torch.Tensor, lowres: Tensor4,
+                      out_hwc: torch.Tensor, batch: int, binarize: bool = True, stream: int = 0):
+        """lama_paste_back_u8_fwd: the fp32 result ``lowres`` [B,3,Hp,Wp] of a ``scale_factor`` step (valid in [:dh, :dw] per image) resampled
+        bilinearly to each image's source grid and pasted into the u8 source slots [B,Hs,Ws,3] wherever the u8 mask [B,Hs,Ws] is not 0 ->
+        ``out_hwc`` [B,Hs,Ws,3] u8 (another buffer than ``image_hwc``).  Source pixels pass through byte for byte where the mask is 0."""
+        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
+            raise LamaError(f'paste_back_u8: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
+        if tuple(out_hwc.shape) != tuple(image_hwc.shape):
+            raise LamaError(f'paste_back_u8: out slots {tuple(out_hwc.shape)} != image slots {tuple(image_hwc.shape)}')
+        for t, dt in ((image_hwc, torch.uint8), (mask, torch.uint8), (out_hwc, torch.uint8), (src_sizes, torch.int32), (dst_sizes, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise LamaError(f'paste_back_u8: a contiguous {dt} tensor is needed, got {t.dtype}')
+        if src_sizes.numel() < 2 * batch or dst_sizes.numel() < 2 * batch:
+            raise LamaError('paste_back_u8: src_sizes / dst_sizes are [B,2] int32')
+        self.check(self._l.lama_paste_back_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
+                                                  int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(lowres), out_hwc.data_ptr(), batch,
+                                                  int(bool(binarize))), 'lama_paste_back_u8_fwd')
 
     def eval_ingest_u8(self, image_hwc: torch.Tensor, pred_hwc: torch.Tensor, mask: torch.Tensor, sizes, pad_mod: int,
                        out_image: Optional[torch.Tensor], out_pred: Optional[torch.Tensor], mask_sum: Optional[torch.Tensor], batch: int,

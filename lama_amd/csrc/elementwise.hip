@@ -577,6 +577,175 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void resize_u8_kernel(ResizeParams p
     }
 }
 
+// ---- paste_back: the scaled step's fp32 result resampled to the SOURCE grid and pasted into the decoded u8 original, in one launch --
+//   out = source pixel where the mask is 0; elsewhere F.interpolate(lowres[:, :dh, :dw], size=(h, w), mode='bilinear', align_corners=False)
+//   (index arithmetic of rf_bilin_src, csrc/refine.hip) blended as mask * v + (1 - mask) * image and quantised as clip(. * 255, 0, 255) truncated.
+// This output has no counterpart in the reference (which writes the scaled image): the contract is BYTE-IDENTITY with the numpy restatement
+// tests/paste_back_util.py::paste_back_ref -- every operation rounded on its own, so every function below switches floating-point contraction
+// OFF, as resize_u8_kernel does.  Where the mask byte is 0 both forms of the mask give the source byte back ((k / 255.f) * 255.f truncates to k
+// for all 256 values): those pixels are copied, and the low-resolution tensor is read only for pixels whose mask byte is not 0.
+// A streaming kernel: 7 bytes per source pixel (1 mask + 3 in + 3 out) against a low-resolution tensor of 1 / 16 of that at factor 0.25, which
+// stays in L2 / the Infinity Cache.  One work item = 4 consecutive pixels of a slot row: one dword of mask, three dwords of RGB in, three out
+// (dword accesses where Ws % 4 == 0 and the pointers allow, byte accesses otherwise).  A 256-thread workgroup takes PB_UNROLL * 256 items of ONE
+// image (its sizes and scales are uniform: scalar loads, one division per workgroup) -- ROW: 256 consecutive items of PB_UNROLL consecutive rows
+// (slots of 192 items per row or more: the row and its y taps are uniform too); otherwise consecutive items of the slot, a lane divides once per
+// item by the items per row.  A lane has the streaming loads of all its items in flight before the gather, and every load before its first
+// store; the loads are unconditional (a lane past the end re-reads the last item and stores nothing).  No LDS, no atomics.
+#define PB_THREADS 256
+#define PB_UNROLL 4
+#define PB_ROW_MIN_ITEMS 192
+struct PasteParams {
+    const uint8_t* img;          // [B][Hs][Ws][3], each image's h x w pixels in the top-left corner of its slot
+    const uint8_t* mask;         // [B][Hs][Ws]
+    const int32_t* src_sizes;    // [B][2] = (h, w); h = 0: an empty slot -> zeros
+    const int32_t* dst_sizes;    // [B][2] = (dh, dw): the valid corner of lowres
+    const float* low;            // [B,3,LH,LW]
+    long long low_bs;
+    uint8_t* out;                // [B][Hs][Ws][3]
+    int Hs, Ws, LH, LW, binarize;
+    int qpr, chunks, ygroups;    // items per slot row; workgroups per row (ROW) / per slot; groups of PB_UNROLL rows per slot (ROW)
+};
+struct PbAxis {
+    int i0, i1;
+    float l;
+};
+// rf_bilin_src (csrc/refine.hip): src = max(0, (dst + 0.5) * scale - 0.5); i0 = (int)src; i1 = min(i0 + 1, n - 1); l = src - i0
+__device__ __forceinline__ PbAxis pb_axis(int o, float scale, int n) {
+#pragma clang fp contract(off)
+    PbAxis a;
+    float s = ((float)o + 0.5f) * scale - 0.5f;
+    s = s < 0.0f ? 0.0f : s;
+    a.i0 = (int)s;
+    if (a.i0 > n - 1) a.i0 = n - 1;
+    a.i1 = a.i0 + 1 < n ? a.i0 + 1 : n - 1;
+    a.l = s - (float)a.i0;
+    return a;
+}
+// np.clip(r * 255, 0, 255).astype('uint8') as blend_quantize_u8_kernel does it (a NaN becomes 0: fmaxf returns its other operand)
+__device__ __forceinline__ uint32_t pb_quant(float r) {
+#pragma clang fp contract(off)
+    float t = r * 255.0f;
+    t = fminf(fmaxf(t, 0.0f), 255.0f);
+    return (uint32_t)(uint8_t)t;
+}
+template <bool VEC, bool ROW> __global__ __launch_bounds__(PB_THREADS) void paste_back_u8_kernel(PasteParams p) {
+#pragma clang fp contract(off)
+    int blk = blockIdx.x;
+    const int chunk = blk % p.chunks; blk /= p.chunks;
+    const int yg = ROW ? blk % p.ygroups : 0, b = ROW ? blk / p.ygroups : blk;
+    const int tid = threadIdx.x;
+    const int h = p.src_sizes[2 * b], w = p.src_sizes[2 * b + 1], dh = p.dst_sizes[2 * b], dw = p.dst_sizes[2 * b + 1];
+    // an empty slot, or sizes that do not fit the slot / the low-resolution view (the host cannot see them without a synchronisation): zeros
+    const bool ok = h > 0 && w > 0 && dh > 0 && dw > 0 && h <= p.Hs && w <= p.Ws && dh <= p.LH && dw <= p.LW;
+    const float sy = ok ? (float)dh / (float)h : 0.0f, sx = ok ? (float)dw / (float)w : 0.0f;
+    const long long slot = (long long)b * p.Hs * p.Ws;
+    const uint8_t* img = p.img + slot * 3;
+    const uint8_t* msk = p.mask + slot;
+    uint8_t* out = p.out + slot * 3;
+    const char* low = reinterpret_cast<const char*>(p.low + (long long)b * p.low_bs);
+    const long long plane = 4ll * p.LH * p.LW;           // bytes of one low-resolution plane, < 2^32
+    const unsigned rowb = 4u * (unsigned)p.LW;
+    const int nitems = p.Hs * p.qpr;
+
+    int yy[PB_UNROLL], qq[PB_UNROLL];
+    bool valid[PB_UNROLL];
+    uint32_t m4[PB_UNROLL], d[PB_UNROLL][3];
+#pragma unroll
+    for (int k = 0; k < PB_UNROLL; ++k) {                 // the streaming loads of every item, none behind a branch
+        int y, q;
+        if (ROW) {
+            y = yg * PB_UNROLL + k; q = chunk * PB_THREADS + tid;
+            valid[k] = y < p.Hs && q < p.qpr;
+            y = y < p.Hs ? y : p.Hs - 1; q = q < p.qpr ? q : p.qpr - 1;
+        } else {
+            const int v = (chunk * PB_UNROLL + k) * PB_THREADS + tid;
+            valid[k] = v < nitems;
+            const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
+            y = (int)(vc / (unsigned)p.qpr); q = (int)(vc - (unsigned)y * (unsigned)p.qpr);
+        }
+        yy[k] = y; qq[k] = q;
+        const long long row = (long long)y * p.Ws;
+        if (VEC) {
+            const long long px = row + 4 * q;
+            m4[k] = *reinterpret_cast<const ei_u32*>(msk + px);
+            const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
+            d[k][0] = s[0]; d[k][1] = s[1]; d[k][2] = s[2];
+        } else {
+            m4[k] = d[k][0] = d[k][1] = d[k][2] = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                 // (a column past the slot's edge re-reads the last one; it is never stored)
+                const int x = 4 * q + j < p.Ws ? 4 * q + j : p.Ws - 1;
+                m4[k] |= (uint32_t)msk[row + x] << (8 * j);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) d[k][(3 * j + c) >> 2] |= (uint32_t)img[(row + x) * 3 + c] << (8 * ((3 * j + c) & 3));
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PB_UNROLL; ++k) {                 // the bytes to store, in place of the bytes loaded
+        uint32_t o[3] = {0u, 0u, 0u};
+        const int y = yy[k], x0 = 4 * qq[k];
+        if (valid[k] && ok && y < h) {
+            const PbAxis ay = pb_axis(y, sy, dh);
+            const float hy = 1.0f - ay.l;
+            const unsigned r0 = (unsigned)ay.i0 * rowb, r1 = (unsigned)ay.i1 * rowb;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x0 + j;
+                if (x < w) {
+                    const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
+                    uint32_t sb[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sb[c] = (d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3))) & 255u;
+                    if (mu != 0u) {                       // the only lanes that read the low-resolution tensor
+                        const PbAxis ax = pb_axis(x, sx, dw);
+                        const float hx = 1.0f - ax.l;
+                        // byte offsets inside one plane in 32 bits (the entry has checked that they fit) on a plane pointer that is uniform
+                        const unsigned c0 = 4u * (unsigned)ax.i0, c1 = 4u * (unsigned)ax.i1;
+                        float t[3][4];                    // the pixel's twelve taps in flight together, then the arithmetic
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const char* pl = low + c * plane;
+                            t[c][0] = *reinterpret_cast<const float*>(pl + (r0 + c0)); t[c][1] = *reinterpret_cast<const float*>(pl + (r0 + c1));
+                            t[c][2] = *reinterpret_cast<const float*>(pl + (r1 + c0)); t[c][3] = *reinterpret_cast<const float*>(pl + (r1 + c1));
+                        }
+                        float v[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) v[c] = hy * (hx * t[c][0] + ax.l * t[c][1]) + ay.l * (hx * t[c][2] + ax.l * t[c][3]);
+                        if (p.binarize) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) sb[c] = pb_quant(v[c]);
+                        } else {
+                            const float m = (float)mu / 255.0f, km = 1.0f - m;
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) sb[c] = pb_quant(m * v[c] + km * ((float)sb[c] / 255.0f));
+                        }
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) o[(3 * j + c) >> 2] |= sb[c] << (8 * ((3 * j + c) & 3));
+                }
+            }
+        }
+        d[k][0] = o[0]; d[k][1] = o[1]; d[k][2] = o[2];
+    }
+#pragma unroll
+    for (int k = 0; k < PB_UNROLL; ++k) {
+        if (!valid[k]) continue;
+        const long long px = (long long)yy[k] * p.Ws + 4 * qq[k];
+        if (VEC) {
+            ei_u32* s = reinterpret_cast<ei_u32*>(out + px * 3);
+            s[0] = d[k][0]; s[1] = d[k][1]; s[2] = d[k][2];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * qq[k] + j < p.Ws) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) out[(px + j) * 3 + c] = (uint8_t)(d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3)));
+                }
+        }
+    }
+}
+
 struct AffineParams {
     const float* x;
     long long x_bs;
@@ -866,6 +1035,45 @@ extern "C" int lama_resize_u8_fwd(void* stream, const uint8_t* image_hwc, const 
         p.inv_area = (float)(1.0 / ((double)p.isc * p.isc));
     }
     hipLaunchKernelGGL(resize_u8_kernel, dim3(ew_grid((long long)batch * p.Hp * p.Wp)), dim3(LAMA_NTHREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// the scaled step's result pasted back into the source image: see paste_back_u8_kernel
+extern "C" int lama_paste_back_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes,
+                                      int32_t Hs, int32_t Ws, const lama_tensor* lowres, uint8_t* out_hwc, int32_t batch, int32_t binarize) {
+    if (!image_hwc || !mask || !src_sizes || !dst_sizes || !lowres || !lowres->ptr || !out_hwc) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0 || lowres->C != 3 || lowres->H <= 0 || lowres->W <= 0) return LAMA_ERR_BAD_ARG;
+    if (lowres->batch_stride < (int64_t)3 * lowres->H * lowres->W || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({lowres})) return LAMA_ERR_UNSUPPORTED;
+    if ((uintptr_t)lowres->ptr & 3) return LAMA_ERR_BAD_ARG;
+    if ((long long)lowres->H * lowres->W > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;      // 32-bit byte offsets inside a low-resolution plane
+    PasteParams p;
+    memset(&p, 0, sizeof(p));
+    p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.dst_sizes = dst_sizes;
+    p.low = (const float*)lowres->ptr; p.low_bs = lowres->batch_stride;
+    p.out = out_hwc;
+    p.Hs = Hs; p.Ws = Ws; p.LH = lowres->H; p.LW = lowres->W; p.binarize = binarize != 0;
+    p.qpr = lama_ceil_div(Ws, 4);
+    const bool vec = Ws % 4 == 0 && !(((uintptr_t)image_hwc | (uintptr_t)mask | (uintptr_t)out_hwc) & 3);
+    const bool row = p.qpr >= PB_ROW_MIN_ITEMS;
+    long long nwg;
+    if (row) {
+        p.chunks = lama_ceil_div(p.qpr, PB_THREADS);
+        p.ygroups = lama_ceil_div(Hs, PB_UNROLL);
+        nwg = (long long)batch * p.ygroups * p.chunks;
+    } else {
+        const long long n = (long long)Hs * p.qpr;
+        if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;            // 32-bit item indices
+        p.chunks = (int)lama_ceil_div64(n, PB_THREADS * PB_UNROLL);
+        nwg = (long long)batch * p.chunks;
+    }
+    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
+    const dim3 grid((unsigned)nwg), block(PB_THREADS);
+#define PB_LAUNCH(V, R) hipLaunchKernelGGL((paste_back_u8_kernel<V, R>), grid, block, 0, (hipStream_t)stream, p)
+    if (vec) { if (row) PB_LAUNCH(true, true); else PB_LAUNCH(true, false); }
+    else { if (row) PB_LAUNCH(false, true); else PB_LAUNCH(false, false); }
+#undef PB_LAUNCH
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }

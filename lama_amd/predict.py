@@ -3,13 +3,15 @@
 
     python -m lama_amd.predict model.path=<dir> indir=<dir> outdir=<dir> \
         [model.checkpoint=best.ckpt] [dataset.img_suffix=.png] [dataset.pad_out_to_modulo=8] [out_ext=.png] \
-        [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8]
+        [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]]
     python -m torch.distributed.run --nproc-per-node N -m lama_amd.predict ...        # one process per GPU
 
 Same on-disk contract as the reference: masks are ``**/*mask*.png`` (sorted, recursive), the image of a mask
 is ``<mask path up to '_mask'><img_suffix>`` (``evaluation/data.py:59-62``), the result of a mask is written to
 ``<outdir>/<mask path relative to indir, extension replaced by out_ext>`` (``bin/predict.py:69-72``) as
 ``clip(inpainted*255, 0, 255).astype(uint8)`` cropped to the unpadded size (``bin/predict.py:86-94``).
+``paste_back=true`` (with ``dataset.scale_factor`` only; an output of this driver's own, the reference has none like it) writes the SOURCE image
+with the pixels under the mask taken from the scaled prediction, resampled bilinearly on the device (lama_paste_back_u8_fwd).
 
 What differs from the reference's batch-1 Python loop: images are padded to ``pad_out_to_modulo`` and *bucketed by
 padded shape*, each bucket is cut into batches, batches are dealt round-robin to the ranks (one process per GPU,
@@ -36,7 +38,8 @@ from . import trainers
 
 DEFAULTS = {'model.checkpoint': 'best.ckpt', 'dataset.img_suffix': '.png', 'dataset.pad_out_to_modulo': 8,
             'out_ext': '.png', 'out_key': 'inpainted', 'batch_size': 8, 'precision': 'f16x3',
-            'io_threads': 8}   # configs/prediction/default.yaml (+ batch_size / precision / io_threads: this driver's own)
+            'io_threads': 8,   # configs/prediction/default.yaml (+ batch_size / precision / io_threads: this driver's own)
+            'paste_back': False}   # extension, with dataset.scale_factor only: write the SOURCE image with the hole taken from the scaled prediction
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -56,7 +59,7 @@ REFINER_DEFAULTS = {'refiner.gpu_ids': '0,', 'refiner.modulo': 8, 'refiner.n_ite
 # a file name); everything else is a bool / int / float as in the YAML defaults
 STRING_KEYS = {'model.path', 'model.checkpoint', 'indir', 'outdir', 'device', 'dataset.kind', 'dataset.img_suffix', 'out_ext', 'out_key',
                'precision', 'refiner.gpu_ids'}
-BOOL_KEYS = {'refine', 'profile'}
+BOOL_KEYS = {'refine', 'profile', 'paste_back'}
 INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
             'refiner.px_budget', 'refiner.batch_size'}
 FLOAT_KEYS = {'refiner.lr', 'dataset.scale_factor'}
@@ -105,6 +108,16 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
         raise SystemExit(f"dataset.scale_factor={cfg['dataset.scale_factor']!r}: a positive factor (evaluation/data.py:74-77)")
     if cfg['refiner.batch_size'] < 1:
         raise SystemExit(f"refiner.batch_size={cfg['refiner.batch_size']!r}: at least 1 image per refinement")
+    if cfg['paste_back']:
+        # the scaled prediction resampled (bilinear) to the source grid and pasted into the source image where the mask is not 0
+        # (lama_paste_back_u8_fwd): this driver's own output, the reference writes the scaled image
+        if cfg.get('dataset.scale_factor') is None:
+            raise SystemExit('paste_back=true needs dataset.scale_factor: without one the result has the source size already')
+        if cfg.get('refine', False):
+            raise SystemExit('paste_back=true with refine=true is not served: refinement writes its own result at the scaled size')
+        if cfg['out_key'] != 'inpainted':
+            raise SystemExit(f"paste_back=true with out_key={cfg['out_key']!r} is not served: the pasted result is made from 'inpainted' "
+                             f"('predicted_image' is undefined where the mask is 0)")
     return cfg
 
 
@@ -452,11 +465,16 @@ class HostFedStep:
     Three input forms: u8 HWC images as decoded, in padded slots (the default; ``put``); the same in SOURCE slots of ``src_hw`` pixels with
     ``scale_factor`` set -- the step's first launch, lama_resize_u8_fwd, then builds the loader's rescaled, padded fp32 image and 0 / 1 mask on
     the device and the fp32 chain (mask compose, generator, blend, u8 quantisation) runs on them; fp32 NCHW tensors the caller made
-    (``u8_input=False``).  Every mode serves every form; in 'graph' the resize is one more kernel node of the captured step."""
+    (``u8_input=False``).  Every mode serves every form; in 'graph' the resize is one more kernel node of the captured step.
+
+    ``paste_back`` (with ``scale_factor`` only; no counterpart in the reference, which writes the scaled image): the step ends with
+    lama_paste_back_u8_fwd instead of the u8 quantisation -- the fp32 ``inpainted`` of the scaled step resampled bilinearly to each image's
+    source grid and pasted into the decoded original (still on the device, in the source slots) wherever its mask is not 0.  The result sets are
+    then source slots [n, Hs, Ws, 3], and every source pixel outside the mask comes back byte for byte."""
 
     def __init__(self, model, batch_size: int, Hp: int, Wp: int, device, *, drain: bool = True, binarize: bool = True, mode: str = 'auto',
                  u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True, scale_factor: Optional[float] = None,
-                 src_hw: Optional[Tuple[int, int]] = None):
+                 src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False):
         self.model, self.n, self.Hp, self.Wp = model, int(batch_size), int(Hp), int(Wp)
         # ``scale_factor`` (dataset.scale_factor, evaluation/data.py:74-77): the third input form -- the step is fed with the DECODED u8 originals in
         # source slots of ``src_hw`` = (Hs, Ws) pixels, and its first launch (lama_resize_u8_fwd) does / 255, the INTER_AREA / INTER_NEAREST
@@ -471,6 +489,12 @@ class HostFedStep:
         if out_key not in ('inpainted', 'predicted_image'):                        # bin/predict.py:86: batch[predict_config.out_key]
             raise L.LamaError(f"out_key {out_key!r}: 'inpainted' or 'predicted_image'")
         self.out_key = out_key
+        self.paste_back = bool(paste_back)
+        if self.paste_back and self.scale is None:
+            raise L.LamaError('paste_back needs scale_factor: without one the result has the source size already')
+        if self.paste_back and out_key != 'inpainted':
+            raise L.LamaError(f"paste_back with out_key {out_key!r}: the pasted result is made from 'inpainted' ('predicted_image' is undefined "
+                              f"where the mask is 0)")
         self.device = torch.device(device)
         self.on_gpu = self.device.type == 'cuda'
         self.drain, self.binarize = drain, binarize
@@ -523,8 +547,9 @@ class HostFedStep:
             self.d_img = [torch.zeros(self.n, 3, Hp, Wp, dtype=torch.float32, device=self.device) for _ in range(2)]
             self.d_mask = [torch.zeros(self.n, 1, Hp, Wp, dtype=torch.float32, device=self.device) for _ in range(2)]
             self.h_sizes = self.d_sizes = None
-        self.h_u8 = [torch.zeros(self.n, Hp, Wp, 3, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
-        self.u8 = [torch.zeros(self.n, Hp, Wp, 3, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self.out_hw = (self.Hs, self.Ws) if self.paste_back else (self.Hp, self.Wp)       # paste_back: the results are source slots
+        self.h_u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
+        self.u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, device=self.device) for _ in range(2)]
         self.graphs = [None, None]
         self.span_events = None       # a list: launch() (mode 'host') appends (start, end) timing events around each step's compute
         self.done = [torch.cuda.Event() for _ in range(2)] if self.on_gpu else None
@@ -609,6 +634,10 @@ class HostFedStep:
         finally:
             self.model.keep_predicted_image = keep
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.on_gpu else 0
+        if self.paste_back:     # the scaled result back on the source grid, inside the source image (the originals are still in their slots)
+            lib.paste_back_u8(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.d_dsizes[p], L.view(out), self.u8[p], self.n,
+                              binarize=self.binarize, stream=stream)
+            return
         lib.quantize_u8_hwc(L.view(out), self.u8[p], self.n, self.Hp, self.Wp, stream)             # bin/predict.py:92 on the device
 
     def _upload(self, q: int, non_blocking: bool):
@@ -743,10 +772,12 @@ class HostFedStep:
 
 def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[str, str]], indir: str, outdir: str, *,
             pad_mod: int = 8, batch_size: int = 8, out_ext: str = '.png', device='cuda', rank: int = 0, world: int = 1,
-            dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None) -> int:
+            dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None, paste_back: bool = False) -> int:
     """Run every (mask, image) pair through ``model`` and write the results (rank 0).  Returns the number of images written.
     ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled before the padding -- on the device, by
     the first launch of the step, which is fed with the decoded u8 originals (lama_resize_u8_fwd) -- and the results have the rescaled size.
+    ``paste_back`` (with ``scale_factor``): the results have the SOURCE size instead -- the source image, with the pixels under the mask taken from
+    the scaled prediction resampled bilinearly (lama_paste_back_u8_fwd; the reference has no such output).
 
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
@@ -756,13 +787,15 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
         for _attempt in range(2):
             try:
                 return _predict_once(model, items, indir, outdir, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext, device=device,
-                                     rank=rank, world=world, dist=dist, io_threads=io_threads, out_key=out_key, scale_factor=scale_factor)
+                                     rank=rank, world=world, dist=dist, io_threads=io_threads, out_key=out_key, scale_factor=scale_factor,
+                                     paste_back=paste_back)
             except _RangeRestart:
                 continue                     # the generator switched to the 3-term bf16 split (every rank alike): all images again
         raise L.LamaError('range restart did not converge')
 
 
-def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, device, rank, world, dist, io_threads, out_key='inpainted', scale_factor=None) -> int:
+def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, device, rank, world, dist, io_threads, out_key='inpainted', scale_factor=None,
+                  paste_back=False) -> int:
     from PIL import Image
 
     def header_size(item):                   # padded shape from the IMAGE's PNG header only: every rank builds the same plan
@@ -770,6 +803,8 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
             w, h = im.size
         return (h, w)
 
+    if paste_back and scale_factor is None:
+        raise L.LamaError('paste_back needs scale_factor: without one the result has the source size already')
     lib = model.generator._exec.lib
     pool = ThreadPoolExecutor(io_threads)
     # the copies into / out of the pinned sets are on the round loop's critical path (the next launch waits for them) and take 0.1-0.3 ms each: they
@@ -786,18 +821,20 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
         rounds = plan_rounds(shapes, batch_size, world)
         return _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext,
                                device=device, rank=rank, world=world, dist=dist, out_key=out_key, fast=fast, scale_factor=scale_factor,
-                               src_sizes=src_sizes)
+                               src_sizes=src_sizes, paste_back=paste_back)
     finally:
         fast.shutdown()
         pool.shutdown()                      # on every exit path (a raise out of a bucket included): no worker thread outlives the call
 
 
 def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pad_mod, batch_size, out_ext, device, rank, world, dist, out_key='inpainted', fast=None,
-                    scale_factor=None, src_sizes=None) -> int:
+                    scale_factor=None, src_sizes=None, paste_back=False) -> int:
     """The rounds of one attempt.  Per bucket (padded shape) a ``HostFedStep``: round k computes from device input set k & 1 while the SAME graph
     launch uploads round k + 1's decoded images into the other set and (one rank) downloads round k - 1's u8 results; the host fills the
     pinned set of round k + 1 and queues round k - 2's PNG writes while round k runs.  Several ranks: the results go through the one
-    collective -- ``gather_to_root`` of the u8 batch, on a side stream behind the step -- and rank 0 downloads the gathered rounds."""
+    collective -- ``gather_to_root`` of the u8 batch, on a side stream behind the step -- and rank 0 downloads the gathered rounds.
+    ``paste_back``: the buckets stay keyed by the padded scaled size, but the u8 results (and the gathered rounds) are the bucket's source slots
+    and each PNG is the h x w crop of its SOURCE size."""
     futures, written = [], 0                 # futures of the snapshot jobs; each returns the future of its encode + write
     fast = fast if fast is not None else pool
     bucket_paths: List[str] = []             # the PNGs queued for the bucket whose range flag has not been read yet
@@ -817,16 +854,17 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             loads[r] = [pool.submit(load_item_u8, *items[i]) for i in rounds[r]['batches'][rank]]
 
     snapped = [_Latch(), _Latch()]           # per pinned result set: the workers that still copy their image out of it
+    crops = src_sizes if paste_back else sizes
 
     def write_round(rd, host, pset):
         """Rank 0: queue the PNG writes of one round from its u8 results on the host (``host`` = [ranks * batch_size, Hp, Wp, 3] = pinned result
-        set ``pset``).  The workers snapshot their image themselves (the main thread only queues); ``snapped[pset].wait()`` before that set is
+        set ``pset``; ``paste_back``: [ranks * batch_size, Hs, Ws, 3]).  The workers snapshot their image themselves (the main thread only queues); ``snapped[pset].wait()`` before that set is
         downloaded into again."""
         nonlocal written
         for r, idxs in enumerate(rd['batches']):
             for j, i in enumerate(idxs):
                 mask_path = items[i][0]
-                h, w = sizes[i]
+                h, w = crops[i]
                 rel = os.path.splitext(mask_path[len(indir):].lstrip(os.sep))[0] + out_ext      # bin/predict.py:69-72
                 bucket_paths.append(os.path.join(outdir, rel))
                 snapped[pset].add()
@@ -848,14 +886,14 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             members = [src_sizes[i] for rd in rounds[r0:r1] for b in rd['batches'] for i in b]
             src_hw = (max(h for h, _ in members), max(w for _, w in members))
         hs = HostFedStep(model, batch_size, Hp, Wp, device, drain=(world == 1), tune=(K >= TUNE_MIN_ROUNDS), capture=(K >= CAPTURE_MIN_ROUNDS), out_key=out_key,
-                         scale_factor=scale_factor, src_hw=src_hw)
+                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back)
         LOOP_TIMES['bucket_setup'] = LOOP_TIMES.get('bucket_setup', 0.0) + time.perf_counter() - t_
         if PROFILE_SPANS:
             hs.span_events = []
         gathered = h_out = None
         if world > 1 and rank == 0:
-            gathered = [torch.empty(world * batch_size, Hp, Wp, 3, dtype=torch.uint8, device=device) for _ in range(2)]
-            h_out = [torch.zeros(world * batch_size, Hp, Wp, 3, dtype=torch.uint8, **(dict(pin_memory=True) if on_gpu else {})) for _ in range(2)]
+            gathered = [torch.empty(world * batch_size, *hs.out_hw, 3, dtype=torch.uint8, device=device) for _ in range(2)]
+            h_out = [torch.zeros(world * batch_size, *hs.out_hw, 3, dtype=torch.uint8, **(dict(pin_memory=True) if on_gpu else {})) for _ in range(2)]
         works = [None, None]
         collected = [torch.cuda.Event() for _ in range(2)] if (on_gpu and world > 1) else None
 
@@ -1097,7 +1135,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     t0 = time.perf_counter()
     n = predict(model, items, indir, cfg['outdir'], pad_mod=int(cfg['dataset.pad_out_to_modulo']), batch_size=int(cfg['batch_size']),
                 out_ext=cfg['out_ext'], device=device, rank=rank, world=world, dist=dist, io_threads=int(cfg['io_threads']), out_key=cfg['out_key'],
-                scale_factor=cfg.get('dataset.scale_factor'))
+                scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']))
     dt = time.perf_counter() - t0
     if rank == 0:
         # (the loop's own wall time: plan build + graph capture of every shape bucket, PNG decode, upload, compute, download, PNG encode + write)
