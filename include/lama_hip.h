@@ -607,6 +607,34 @@ int lama_lfu_tile_add_fwd(void* stream, const lama_tensor* a, const lama_tensor*
 int lama_paste_back_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes, int32_t Hs,
                            int32_t Ws, const lama_tensor* lowres, uint8_t* out_hwc, int32_t batch, int32_t binarize);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) the zlib stream of a PNG's IDAT, made on the device from u8
+ * HWC slots.  A PNG encoder owes the decoder the pixels, not particular bytes: THE STREAM IS THIS ENGINE'S OWN DEFINITION, pinned byte for byte by
+ * tests/png_ref.py::deflate_ref.  image_hwc [batch][Hs][Ws][channels] u8 slots, each image's h x w pixels in the top-left corner; sizes: device int32
+ * [batch][2] = (h, w).  Per image:
+ *   filtered bytes  per row the byte 1 (filter Sub), then w c bytes x[i] - x[i - c] mod 256 (the first pixel as is): row = 1 + w c bytes
+ *   chunks          R = max(1, chunk_bytes / row) whole rows each, the last one may be shorter; chunk_bytes 0 = the default 24576
+ *   one chunk       one dynamic-Huffman block (BFINAL 0, BTYPE 10; HLIT 0, HDIST 0 with one distance code of length 0, HCLEN 15 with the lengths 4 for the
+ *                   code-length symbols 0..15 and 0 for 16 / 17 / 18: every code length travels as 4 bits) of the chunk's bytes as literals and symbol
+ *                   256, then an empty stored block (000, pad to a byte, 00 00 FF FF).  Code lengths: the depths of the Huffman tree over the used
+ *                   symbols (256 counts once) by the two-queue merge over the symbols sorted by (count, symbol), a leaf before an internal node on ties;
+ *                   deeper than 15, every non-zero count n becomes (n + 1) >> 1 and the tree is built again.  Canonical codes.
+ *                   Where that is not shorter than raw + 5 bytes the chunk is stored: 00, LEN, ~LEN (little endian), the raw bytes.
+ *   stream          78 01, the chunks in order, 01 00 00 FF FF, Adler-32 of the filtered bytes (big endian)
+ * No matches (a flat region costs 1 bit per byte), no filter but Sub, 8-bit gray (channels 1) or RGB (3); the PNG container and its CRC are the
+ * caller's (lama_amd.predict.png_from_zlib).  Image j's stream starts at out + j * out_stride and has out_bytes[j] bytes; the bytes behind it are not
+ * touched.  An empty slot (h or w < 1) and one whose sizes do not fit (h > Hs, w > Ws) give out_bytes[j] = 0 and touch nothing else: the sizes are device
+ * data, nothing is read or written outside a slot.  Two launches (one workgroup per chunk, then one per four chunks and one per image), no global atomics, plain vector stores;
+ * asynchronous and hipGraph-capturable.  The same operands give the same bytes.
+ * lama_png_deflate_bound: the most bytes one h x w image's stream can take (every chunk stored); 0 for an empty image or refused arguments.
+ * lama_png_deflate_workspace_bytes: the workspace (16-byte aligned) of a call with these slots.
+ * LAMA_ERR_BAD_ARG: a null pointer; batch, Hs or Ws <= 0; channels not 1 or 3; chunk_bytes neither 0 nor in [64, 32768]; out_stride below
+ * lama_png_deflate_bound(Hs, Ws, ...); a workspace that is not 16-byte aligned, sizes / out_bytes that are not 4-byte aligned.  LAMA_ERR_UNSUPPORTED: a row of
+ * the slot (1 + Ws channels) beyond 65535 bytes; 2^30 chunks or more.  LAMA_ERR_WORKSPACE: a smaller workspace.  Nothing is launched on an error. */
+size_t lama_png_deflate_bound(int32_t h, int32_t w, int32_t channels, int32_t chunk_bytes);
+int    lama_png_deflate_workspace_bytes(int32_t batch, int32_t Hs, int32_t Ws, int32_t channels, int32_t chunk_bytes, size_t* bytes);
+int    lama_png_deflate_u8_fwd(void* stream, const uint8_t* image_hwc, const int32_t* sizes, int32_t Hs, int32_t Ws, int32_t channels, int32_t batch,
+                               int32_t chunk_bytes, uint8_t* out, size_t out_stride, int32_t* out_bytes, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

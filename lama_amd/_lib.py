@@ -201,6 +201,10 @@ class LamaLib:
         L.lama_resize_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, T, T, i32, i32]
         L.lama_paste_back_u8_fwd.restype = C.c_int
         L.lama_paste_back_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, vp, i32, i32]
+        L.lama_png_deflate_bound.restype, L.lama_png_deflate_bound.argtypes = sz, [i32] * 4
+        L.lama_png_deflate_workspace_bytes.restype, L.lama_png_deflate_workspace_bytes.argtypes = C.c_int, [i32] * 5 + [C.POINTER(sz)]
+        L.lama_png_deflate_u8_fwd.restype = C.c_int
+        L.lama_png_deflate_u8_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, sz]
         L.lama_eval_ingest_u8_fwd.restype = C.c_int
         L.lama_eval_ingest_u8_fwd.argtypes = [vp, vp, vp, vp, C.POINTER(i32), i32, i32, i32, i32, C.c_float, C.c_float, T, T, vp, i32]
         L.lama_affine_act_fwd.restype = C.c_int
@@ -610,6 +614,35 @@ class LamaLib:
         self.check(self._l.lama_paste_back_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
                                                   int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(lowres), out_hwc.data_ptr(), batch,
                                                   int(bool(binarize))), 'lama_paste_back_u8_fwd')
+
+    def png_deflate_bound(self, h: int, w: int, channels: int = 3, chunk_bytes: int = 0) -> int:
+        """lama_png_deflate_bound: the most bytes the stream of one h x w image can take (0: empty, or arguments the encoder refuses)."""
+        return int(self._l.lama_png_deflate_bound(int(h), int(w), int(channels), int(chunk_bytes)))
+
+    def png_deflate_workspace_bytes(self, batch: int, Hs: int, Ws: int, channels: int = 3, chunk_bytes: int = 0) -> int:
+        n = C.c_size_t(0)
+        self.check(self._l.lama_png_deflate_workspace_bytes(int(batch), int(Hs), int(Ws), int(channels), int(chunk_bytes), C.byref(n)),
+                   'lama_png_deflate_workspace_bytes')
+        return int(n.value)
+
+    def png_deflate_u8(self, image_hwc: torch.Tensor, sizes: torch.Tensor, out: torch.Tensor, out_stride: int, out_bytes: torch.Tensor,
+                       workspace: torch.Tensor, batch: int, chunk_bytes: int = 0, stream: int = 0):
+        """lama_png_deflate_u8_fwd: the zlib stream (Sub filter, literal-only dynamic Huffman chunks; tests/png_ref.py) of the h x w crop of every
+        u8 slot of ``image_hwc`` [B,Hs,Ws,3] / [B,Hs,Ws,1] / [B,Hs,Ws], ``sizes`` = device int32 [B,2], into ``out`` (flat u8: slot j starts at
+        byte j * ``out_stride``) and its length into ``out_bytes`` (int32 [B]; 0 for an empty slot).  Two launches, asynchronous, capturable."""
+        if image_hwc.dim() not in (3, 4) or (image_hwc.dim() == 4 and image_hwc.shape[3] not in (1, 3)) or image_hwc.shape[0] < batch:
+            raise LamaError(f'png_deflate_u8: image slots {tuple(image_hwc.shape)}: [B,Hs,Ws,3], [B,Hs,Ws,1] or [B,Hs,Ws] u8')
+        for t, dt in ((image_hwc, torch.uint8), (out, torch.uint8), (workspace, torch.uint8), (sizes, torch.int32), (out_bytes, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise LamaError(f'png_deflate_u8: a contiguous {dt} tensor is needed, got {t.dtype}')
+            if not self.host_emulated and not t.is_cuda:
+                raise LamaError('png_deflate_u8: every operand is a device tensor')
+        if sizes.numel() < 2 * batch or out_bytes.numel() < batch or out.numel() < batch * int(out_stride):
+            raise LamaError('png_deflate_u8: sizes [B,2] / out_bytes [B] int32, out of batch * out_stride bytes')
+        c = 1 if image_hwc.dim() == 3 else int(image_hwc.shape[3])
+        self.check(self._l.lama_png_deflate_u8_fwd(stream, image_hwc.data_ptr(), sizes.data_ptr(), int(image_hwc.shape[1]), int(image_hwc.shape[2]), c,
+                                                   int(batch), int(chunk_bytes), out.data_ptr(), int(out_stride), out_bytes.data_ptr(),
+                                                   workspace.data_ptr(), workspace.numel()), 'lama_png_deflate_u8_fwd')
 
     def eval_ingest_u8(self, image_hwc: torch.Tensor, pred_hwc: torch.Tensor, mask: torch.Tensor, sizes, pad_mod: int,
                        out_image: Optional[torch.Tensor], out_pred: Optional[torch.Tensor], mask_sum: Optional[torch.Tensor], batch: int,

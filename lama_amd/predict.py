@@ -3,7 +3,7 @@
 
     python -m lama_amd.predict model.path=<dir> indir=<dir> outdir=<dir> \
         [model.checkpoint=best.ckpt] [dataset.img_suffix=.png] [dataset.pad_out_to_modulo=8] [out_ext=.png] \
-        [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]]
+        [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]] [device_png=true]
     python -m torch.distributed.run --nproc-per-node N -m lama_amd.predict ...        # one process per GPU
 
 Same on-disk contract as the reference: masks are ``**/*mask*.png`` (sorted, recursive), the image of a mask
@@ -39,7 +39,8 @@ from . import trainers
 DEFAULTS = {'model.checkpoint': 'best.ckpt', 'dataset.img_suffix': '.png', 'dataset.pad_out_to_modulo': 8,
             'out_ext': '.png', 'out_key': 'inpainted', 'batch_size': 8, 'precision': 'f16x3',
             'io_threads': 8,   # configs/prediction/default.yaml (+ batch_size / precision / io_threads: this driver's own)
-            'paste_back': False}   # extension, with dataset.scale_factor only: write the SOURCE image with the hole taken from the scaled prediction
+            'paste_back': False,   # extension, with dataset.scale_factor only: write the SOURCE image with the hole taken from the scaled prediction
+            'device_png': False}   # extension: the PNGs' zlib streams are made on the device (lama_png_deflate_u8_fwd), the host wraps and writes
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -59,7 +60,7 @@ REFINER_DEFAULTS = {'refiner.gpu_ids': '0,', 'refiner.modulo': 8, 'refiner.n_ite
 # a file name); everything else is a bool / int / float as in the YAML defaults
 STRING_KEYS = {'model.path', 'model.checkpoint', 'indir', 'outdir', 'device', 'dataset.kind', 'dataset.img_suffix', 'out_ext', 'out_key',
                'precision', 'refiner.gpu_ids'}
-BOOL_KEYS = {'refine', 'profile', 'paste_back'}
+BOOL_KEYS = {'refine', 'profile', 'paste_back', 'device_png'}
 INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
             'refiner.px_budget', 'refiner.batch_size'}
 FLOAT_KEYS = {'refiner.lr', 'dataset.scale_factor'}
@@ -118,6 +119,11 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
         if cfg['out_key'] != 'inpainted':
             raise SystemExit(f"paste_back=true with out_key={cfg['out_key']!r} is not served: the pasted result is made from 'inpainted' "
                              f"('predicted_image' is undefined where the mask is 0)")
+    if cfg['device_png']:
+        if not str(cfg['out_ext']).lower().endswith('.png'):
+            raise SystemExit(f"device_png=true writes PNG files only: out_ext={cfg['out_ext']!r}")
+        if cfg.get('refine', False):
+            raise SystemExit('device_png=true with refine=true is not served: refinement writes from host tensors')
     return cfg
 
 
@@ -369,6 +375,21 @@ def encode_png(rgb: np.ndarray) -> bytes:
     return b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', ihdr) + chunk(b'IDAT', data) + chunk(b'IEND', b'')
 
 
+def png_from_zlib(h: int, w: int, channels: int, stream) -> bytes:
+    """The PNG file around a finished zlib stream of the h x w image's filtered rows (lama_png_deflate_u8_fwd made it on the device): signature,
+    IHDR (8 bits; RGB for 3 channels, gray for 1), ONE IDAT whose CRC is zlib.crc32 over the compressed bytes, IEND.  The host's share of a
+    device-encoded PNG: one CRC pass and two copies."""
+    import struct
+    import zlib
+    if channels not in (1, 3) or h < 1 or w < 1:
+        raise L.LamaError(f'png_from_zlib: an 8-bit gray / RGB image of at least one pixel, got {h}x{w}x{channels}')
+    ihdr = b'IHDR' + struct.pack('>IIBBBBB', w, h, 8, 2 if channels == 3 else 0, 0, 0, 0)
+    n = len(stream)
+    return b''.join((b'\x89PNG\r\n\x1a\n', struct.pack('>I', 13), ihdr, struct.pack('>I', zlib.crc32(ihdr) & 0xffffffff),
+                     struct.pack('>I', n), b'IDAT', stream, struct.pack('>I', zlib.crc32(stream, zlib.crc32(b'IDAT')) & 0xffffffff),
+                     b'\x00\x00\x00\x00IEND\xaeB`\x82'))
+
+
 class _Latch:
     """Count-down latch: the round loop waits on it before a pinned result set is overwritten while pool workers still snapshot it."""
 
@@ -400,6 +421,22 @@ def _snap_and_write(path: str, view: np.ndarray, latch: _Latch, pool):
     finally:
         latch.done()
     return pool.submit(_write_png, path, rgb)
+
+
+def _snap_and_wrap(path: str, view: np.ndarray, h: int, w: int, latch: _Latch, pool):
+    """``fast`` pool job of ``device_png``: copy the image's zlib stream out of the pinned result set (then release the latch) and queue its wrap
+    (CRC + container) + write on ``pool``; returns that future."""
+    try:
+        data = view.tobytes()
+    finally:
+        latch.done()
+    return pool.submit(_write_png_stream, path, h, w, data)
+
+
+def _write_png_stream(path: str, h: int, w: int, data: bytes):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(png_from_zlib(h, w, 3, data))
 
 
 def _write_png(path: str, rgb: np.ndarray):
@@ -470,11 +507,17 @@ class HostFedStep:
     ``paste_back`` (with ``scale_factor`` only; no counterpart in the reference, which writes the scaled image): the step ends with
     lama_paste_back_u8_fwd instead of the u8 quantisation -- the fp32 ``inpainted`` of the scaled step resampled bilinearly to each image's
     source grid and pasted into the decoded original (still on the device, in the source slots) wherever its mask is not 0.  The result sets are
-    then source slots [n, Hs, Ws, 3], and every source pixel outside the mask comes back byte for byte."""
+    then source slots [n, Hs, Ws, 3], and every source pixel outside the mask comes back byte for byte.
+
+    ``encode_png`` (off by default; the u8 input forms): the step ends with lama_png_deflate_u8_fwd over its u8 results -- the zlib stream of every
+    image's PNG (Sub filter, literal-only dynamic Huffman chunks: tests/png_ref.py), cropped by the sizes array of the form (the scaled sizes with
+    ``scale_factor``, the source sizes with ``paste_back``).  The result sets are then ONE flat u8 buffer per parity, ``n`` stream slots of
+    ``png_slot`` bytes followed by the ``n`` int32 lengths (``d_out`` on the device, ``h_out`` pinned): one D2H, or one gather, carries both, the u8
+    images are not downloaded (``h_u8`` is None) and ``result_png(p, j)`` is the j-th stream.  ``predict.png_from_zlib`` wraps it into the file."""
 
     def __init__(self, model, batch_size: int, Hp: int, Wp: int, device, *, drain: bool = True, binarize: bool = True, mode: str = 'auto',
                  u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True, scale_factor: Optional[float] = None,
-                 src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False):
+                 src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False, encode_png: bool = False):
         self.model, self.n, self.Hp, self.Wp = model, int(batch_size), int(Hp), int(Wp)
         # ``scale_factor`` (dataset.scale_factor, evaluation/data.py:74-77): the third input form -- the step is fed with the DECODED u8 originals in
         # source slots of ``src_hw`` = (Hs, Ws) pixels, and its first launch (lama_resize_u8_fwd) does / 255, the INTER_AREA / INTER_NEAREST
@@ -548,8 +591,25 @@ class HostFedStep:
             self.d_mask = [torch.zeros(self.n, 1, Hp, Wp, dtype=torch.float32, device=self.device) for _ in range(2)]
             self.h_sizes = self.d_sizes = None
         self.out_hw = (self.Hs, self.Ws) if self.paste_back else (self.Hp, self.Wp)       # paste_back: the results are source slots
-        self.h_u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
+        self.encode_png = bool(encode_png)
         self.u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        if self.encode_png:
+            # the step ends with lama_png_deflate_u8_fwd over u8[p]: ONE flat u8 buffer per parity -- n stream slots, then the n int32 lengths -- is
+            # what the D2H (or the gather) carries; the u8 images stay on the device
+            if self.d_sizes is None:
+                raise L.LamaError('encode_png needs a u8 input form (its crops are the step\'s device sizes array): not with u8_input=False')
+            lib = model.generator._exec.lib
+            ws_bytes = lib.png_deflate_workspace_bytes(self.n, *self.out_hw, 3, 0)       # (raises for result slots whose row is beyond 65535 bytes)
+            self.png_slot = (lib.png_deflate_bound(*self.out_hw, 3, 0) + 15) & ~15
+            self.png_bytes = self.n * self.png_slot + 4 * self.n
+            self.png = [torch.zeros(self.png_bytes, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self.h_png = [torch.zeros(self.png_bytes, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
+            self.png_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)       # one: the steps of both parities run in order on one stream
+            self.h_u8 = None
+            self.d_out, self.h_out = self.png, self.h_png
+        else:
+            self.h_u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
+            self.d_out, self.h_out = self.u8, self.h_u8      # what the D2H branch (or the caller's gather) carries
         self.graphs = [None, None]
         self.span_events = None       # a list: launch() (mode 'host') appends (start, end) timing events around each step's compute
         self.done = [torch.cuda.Event() for _ in range(2)] if self.on_gpu else None
@@ -609,10 +669,36 @@ class HostFedStep:
         sz[j] = (h, w)
 
     def result(self, p: int) -> np.ndarray:
+        if self.encode_png:
+            raise L.LamaError('encode_png: the u8 results are not downloaded; result_png(p, j) is the j-th stream')
         return self.h_u8[p].numpy()
+
+    def result_png(self, p: int, j: int) -> memoryview:
+        """``encode_png``: the zlib stream of image j of host result set p (empty for an empty slot), a view of the pinned set."""
+        flat = self.h_png[p].numpy()
+        n = int(flat[self.n * self.png_slot:].view(np.int32)[j])
+        return memoryview(flat[j * self.png_slot:j * self.png_slot + n])
+
+    def crop_sizes(self, p: int) -> np.ndarray:
+        """(h, w) per image of the results computed from host input set p, as ``put`` recorded them: the scaled sizes with ``scale_factor``, the
+        source sizes with ``paste_back`` or without a factor.  Valid until that host set is filled again."""
+        return (self.h_dsizes if self.scale is not None and not self.paste_back else self.h_sizes)[p].numpy()
+
+    def _encode(self, p: int):
+        """``encode_png``: the two launches over u8[p], cropped by the device sizes array of the form."""
+        sizes = self.d_dsizes[p] if self.scale is not None and not self.paste_back else self.d_sizes[p]
+        stream = torch.cuda.current_stream(self.device).cuda_stream if self.on_gpu else 0
+        flat = self.png[p]
+        self.model.generator._exec.lib.png_deflate_u8(self.u8[p], sizes, flat[:self.n * self.png_slot], self.png_slot,
+                                                      flat[self.n * self.png_slot:].view(torch.int32), self.png_ws, self.n, stream=stream)
 
     # -- pieces ---------------------------------------------------------------------------------------------------
     def _compute(self, p: int):
+        self._compute_u8(p)
+        if self.encode_png:
+            self._encode(p)
+
+    def _compute_u8(self, p: int):
         lib = self.model.generator._exec.lib
         if self.u8_input:                                                                          # bin/predict.py:82-92 in two elementwise launches + the generator
             with torch.no_grad():
@@ -654,7 +740,7 @@ class HostFedStep:
         if not self.on_gpu:
             self._upload(q, False)
             if self.drain:
-                self.h_u8[q].copy_(self.u8[q])
+                self.h_out[q].copy_(self.d_out[q])
             self._compute(p)
             return
         main = torch.cuda.current_stream(self.device)
@@ -664,7 +750,7 @@ class HostFedStep:
         if self.drain:
             self.s_out.wait_stream(main)
             with torch.cuda.stream(self.s_out):
-                self.h_u8[q].copy_(self.u8[q], non_blocking=True)
+                self.h_out[q].copy_(self.d_out[q], non_blocking=True)
         self._compute(p)
         main.wait_stream(self.s_in)
         if self.drain:
@@ -732,7 +818,7 @@ class HostFedStep:
             self._h2d_issued[q] = True
             if self.drain:
                 with torch.cuda.stream(self.s_out):
-                    self.h_u8[q].copy_(self.u8[q], non_blocking=True)
+                    self.h_out[q].copy_(self.d_out[q], non_blocking=True)
                     self.d2h[q].record(self.s_out)
             self._launched[p] = True
             return
@@ -758,7 +844,7 @@ class HostFedStep:
     def flush(self, p: int):
         """D2H of u8[p] (the last launch's own result: nothing follows to carry it) and a host wait for it."""
         if self.drain:
-            self.h_u8[p].copy_(self.u8[p], non_blocking=self.on_gpu)
+            self.h_out[p].copy_(self.d_out[p], non_blocking=self.on_gpu)
         if self.on_gpu:
             torch.cuda.current_stream(self.device).synchronize()
             if self.mode == 'host':
@@ -772,12 +858,16 @@ class HostFedStep:
 
 def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[str, str]], indir: str, outdir: str, *,
             pad_mod: int = 8, batch_size: int = 8, out_ext: str = '.png', device='cuda', rank: int = 0, world: int = 1,
-            dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None, paste_back: bool = False) -> int:
+            dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None, paste_back: bool = False,
+            device_png: bool = False) -> int:
     """Run every (mask, image) pair through ``model`` and write the results (rank 0).  Returns the number of images written.
     ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled before the padding -- on the device, by
     the first launch of the step, which is fed with the decoded u8 originals (lama_resize_u8_fwd) -- and the results have the rescaled size.
     ``paste_back`` (with ``scale_factor``): the results have the SOURCE size instead -- the source image, with the pixels under the mask taken from
     the scaled prediction resampled bilinearly (lama_paste_back_u8_fwd; the reference has no such output).
+    ``device_png`` (``.png`` only, off by default): every step ends with the PNG's zlib stream made on the device (lama_png_deflate_u8_fwd); the D2H
+    and, with several ranks, the gather carry the compressed bytes, and the host only wraps them (png_from_zlib: one CRC) and writes.  The files
+    decode to the same pixels; their bytes differ from encode_png's.
 
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
@@ -788,14 +878,14 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
             try:
                 return _predict_once(model, items, indir, outdir, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext, device=device,
                                      rank=rank, world=world, dist=dist, io_threads=io_threads, out_key=out_key, scale_factor=scale_factor,
-                                     paste_back=paste_back)
+                                     paste_back=paste_back, device_png=device_png)
             except _RangeRestart:
                 continue                     # the generator switched to the 3-term bf16 split (every rank alike): all images again
         raise L.LamaError('range restart did not converge')
 
 
 def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, device, rank, world, dist, io_threads, out_key='inpainted', scale_factor=None,
-                  paste_back=False) -> int:
+                  paste_back=False, device_png=False) -> int:
     from PIL import Image
 
     def header_size(item):                   # padded shape from the IMAGE's PNG header only: every rank builds the same plan
@@ -805,6 +895,8 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
 
     if paste_back and scale_factor is None:
         raise L.LamaError('paste_back needs scale_factor: without one the result has the source size already')
+    if device_png and not out_ext.lower().endswith('.png'):
+        raise L.LamaError(f'device_png writes PNG files only, not {out_ext!r}')
     lib = model.generator._exec.lib
     pool = ThreadPoolExecutor(io_threads)
     # the copies into / out of the pinned sets are on the round loop's critical path (the next launch waits for them) and take 0.1-0.3 ms each: they
@@ -821,20 +913,22 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
         rounds = plan_rounds(shapes, batch_size, world)
         return _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext,
                                device=device, rank=rank, world=world, dist=dist, out_key=out_key, fast=fast, scale_factor=scale_factor,
-                               src_sizes=src_sizes, paste_back=paste_back)
+                               src_sizes=src_sizes, paste_back=paste_back, device_png=device_png)
     finally:
         fast.shutdown()
         pool.shutdown()                      # on every exit path (a raise out of a bucket included): no worker thread outlives the call
 
 
 def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pad_mod, batch_size, out_ext, device, rank, world, dist, out_key='inpainted', fast=None,
-                    scale_factor=None, src_sizes=None, paste_back=False) -> int:
+                    scale_factor=None, src_sizes=None, paste_back=False, device_png=False) -> int:
     """The rounds of one attempt.  Per bucket (padded shape) a ``HostFedStep``: round k computes from device input set k & 1 while the SAME graph
     launch uploads round k + 1's decoded images into the other set and (one rank) downloads round k - 1's u8 results; the host fills the
     pinned set of round k + 1 and queues round k - 2's PNG writes while round k runs.  Several ranks: the results go through the one
     collective -- ``gather_to_root`` of the u8 batch, on a side stream behind the step -- and rank 0 downloads the gathered rounds.
     ``paste_back``: the buckets stay keyed by the padded scaled size, but the u8 results (and the gathered rounds) are the bucket's source slots
-    and each PNG is the h x w crop of its SOURCE size."""
+    and each PNG is the h x w crop of its SOURCE size.
+    ``device_png``: a result set is the step's flat buffer (``batch_size`` stream slots, then their int32 lengths) per rank instead of the u8 images:
+    the snapshot job copies the stream's bytes out of the pinned set and releases the latch, the pool job wraps and writes."""
     futures, written = [], 0                 # futures of the snapshot jobs; each returns the future of its encode + write
     fast = fast if fast is not None else pool
     bucket_paths: List[str] = []             # the PNGs queued for the bucket whose range flag has not been read yet
@@ -854,6 +948,7 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             loads[r] = [pool.submit(load_item_u8, *items[i]) for i in rounds[r]['batches'][rank]]
 
     snapped = [_Latch(), _Latch()]           # per pinned result set: the workers that still copy their image out of it
+    png_slot = png_set = 0                   # device_png: bytes per stream slot / per rank's result buffer of the current bucket
     crops = src_sizes if paste_back else sizes
 
     def write_round(rd, host, pset):
@@ -861,6 +956,7 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
         set ``pset``; ``paste_back``: [ranks * batch_size, Hs, Ws, 3]).  The workers snapshot their image themselves (the main thread only queues); ``snapped[pset].wait()`` before that set is
         downloaded into again."""
         nonlocal written
+        host = host.reshape(-1) if device_png else host
         for r, idxs in enumerate(rd['batches']):
             for j, i in enumerate(idxs):
                 mask_path = items[i][0]
@@ -868,7 +964,15 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
                 rel = os.path.splitext(mask_path[len(indir):].lstrip(os.sep))[0] + out_ext      # bin/predict.py:69-72
                 bucket_paths.append(os.path.join(outdir, rel))
                 snapped[pset].add()
-                futures.append(fast.submit(_snap_and_write, bucket_paths[-1], host[r * batch_size + j, :h, :w], snapped[pset], pool))
+                if device_png:
+                    base = r * png_set + j * png_slot
+                    n = int(host[r * png_set + batch_size * png_slot:(r + 1) * png_set].view(np.int32)[j])
+                    if n <= 0:
+                        snapped[pset].done()
+                        raise L.LamaError(f'{mask_path}: the device encoder returned no stream for a {h}x{w} image')
+                    futures.append(fast.submit(_snap_and_wrap, bucket_paths[-1], host[base:base + n], h, w, snapped[pset], pool))
+                else:
+                    futures.append(fast.submit(_snap_and_write, bucket_paths[-1], host[r * batch_size + j, :h, :w], snapped[pset], pool))
                 written += 1
 
     submit_loads(0)
@@ -886,14 +990,17 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             members = [src_sizes[i] for rd in rounds[r0:r1] for b in rd['batches'] for i in b]
             src_hw = (max(h for h, _ in members), max(w for _, w in members))
         hs = HostFedStep(model, batch_size, Hp, Wp, device, drain=(world == 1), tune=(K >= TUNE_MIN_ROUNDS), capture=(K >= CAPTURE_MIN_ROUNDS), out_key=out_key,
-                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back)
+                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png)
+        if device_png:
+            png_slot, png_set = hs.png_slot, hs.png_bytes
         LOOP_TIMES['bucket_setup'] = LOOP_TIMES.get('bucket_setup', 0.0) + time.perf_counter() - t_
         if PROFILE_SPANS:
             hs.span_events = []
         gathered = h_out = None
         if world > 1 and rank == 0:
-            gathered = [torch.empty(world * batch_size, *hs.out_hw, 3, dtype=torch.uint8, device=device) for _ in range(2)]
-            h_out = [torch.zeros(world * batch_size, *hs.out_hw, 3, dtype=torch.uint8, **(dict(pin_memory=True) if on_gpu else {})) for _ in range(2)]
+            set_shape = (world * hs.png_bytes,) if device_png else (world * batch_size, *hs.out_hw, 3)      # device_png: every rank's flat result buffer
+            gathered = [torch.empty(*set_shape, dtype=torch.uint8, device=device) for _ in range(2)]
+            h_out = [torch.zeros(*set_shape, dtype=torch.uint8, **(dict(pin_memory=True) if on_gpu else {})) for _ in range(2)]
         works = [None, None]
         collected = [torch.cuda.Event() for _ in range(2)] if (on_gpu and world > 1) else None
 
@@ -917,13 +1024,13 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             if on_gpu:
                 with torch.cuda.stream(side):
                     side.wait_event(hs.done[pp])
-                    works[pp] = gather_to_root(dist, gathered[pp] if rank == 0 else None, hs.u8[pp], rank, world)
+                    works[pp] = gather_to_root(dist, gathered[pp] if rank == 0 else None, hs.d_out[pp], rank, world)
                     works[pp].wait()                                                  # the side stream waits for RCCL's stream
                     if rank == 0:
                         h_out[pp].copy_(gathered[pp], non_blocking=True)
                     collected[pp].record(side)
             else:
-                works[pp] = gather_to_root(dist, gathered[pp] if rank == 0 else None, hs.u8[pp], rank, world)
+                works[pp] = gather_to_root(dist, gathered[pp] if rank == 0 else None, hs.d_out[pp], rank, world)
                 works[pp].wait()
                 if rank == 0:
                     h_out[pp].copy_(gathered[pp])
@@ -958,7 +1065,7 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
                 LOOP_TIMES['wait_step'] = LOOP_TIMES.get('wait_step', 0.0) + time.perf_counter() - t_
                 if k >= 2:
                     t_ = time.perf_counter()
-                    write_round(rounds[r0 + k - 2], hs.result(pp), pp)
+                    write_round(rounds[r0 + k - 2], hs.h_out[pp].numpy(), pp)
                     LOOP_TIMES['queue_writes'] = LOOP_TIMES.get('queue_writes', 0.0) + time.perf_counter() - t_
         pl = (K - 1) & 1
         if world > 1:
@@ -969,10 +1076,10 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
         else:
             hs.wait(pl)
             if K >= 2:
-                write_round(rounds[r1 - 2], hs.result(1 - pl), 1 - pl)
+                write_round(rounds[r1 - 2], hs.h_out[1 - pl].numpy(), 1 - pl)
             snapped[pl].wait()
             hs.flush(pl)
-            write_round(rounds[r1 - 1], hs.result(pl), pl)
+            write_round(rounds[r1 - 1], hs.h_out[pl].numpy(), pl)
         if on_gpu:
             torch.cuda.current_stream(hs.device).synchronize()                      # every rank: the graphs / buffers below are idle now
             if hs.span_events:
@@ -1135,7 +1242,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     t0 = time.perf_counter()
     n = predict(model, items, indir, cfg['outdir'], pad_mod=int(cfg['dataset.pad_out_to_modulo']), batch_size=int(cfg['batch_size']),
                 out_ext=cfg['out_ext'], device=device, rank=rank, world=world, dist=dist, io_threads=int(cfg['io_threads']), out_key=cfg['out_key'],
-                scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']))
+                scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']), device_png=bool(cfg['device_png']))
     dt = time.perf_counter() - t0
     if rank == 0:
         # (the loop's own wall time: plan build + graph capture of every shape bucket, PNG decode, upload, compute, download, PNG encode + write)
