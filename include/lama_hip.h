@@ -635,6 +635,31 @@ int    lama_png_deflate_workspace_bytes(int32_t batch, int32_t Hs, int32_t Ws, i
 int    lama_png_deflate_u8_fwd(void* stream, const uint8_t* image_hwc, const int32_t* sizes, int32_t Hs, int32_t Ws, int32_t channels, int32_t batch,
                                int32_t chunk_bytes, uint8_t* out, size_t out_stride, int32_t* out_bytes, void* workspace, size_t workspace_bytes);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) the entropy-coded scan of a baseline JPEG, made on the device
+ * from u8 HWC RGB slots.  A JPEG encoder owes the decoder a conforming stream, not particular bytes: THE STREAM IS THIS ENGINE'S OWN DEFINITION,
+ * integer arithmetic throughout, pinned byte for byte by tests/jpeg_ref.py::scan_ref and stated in full at the head of csrc/jpeg.hip: JFIF YCbCr in
+ * 16-bit fixed point, edge replication out to the MCU grid, 4:2:0 chroma as (a + b + c + d + 2) >> 2, a separable integer DCT from a 2^13 table,
+ * the Annex K quantisation tables scaled by libjpeg's quality rule, the Annex K Huffman tables, one restart interval per MCU row (RSTm between the
+ * intervals, m = row mod 8), FF stuffed as FF 00.  image_hwc [batch][Hs][Ws][3] u8 slots, each image's h x w pixels in the top-left corner; sizes:
+ * device int32 [batch][2] = (h, w) -- the arrays lama_png_deflate_u8_fwd takes.  subsampling LAMA_JPEG_444 (MCU 8 x 8: Y, Cb, Cr) or LAMA_JPEG_420
+ * (MCU 16 x 16: four Y blocks in raster order, Cb, Cr); quality 1 .. 100.  The scan only: SOI .. SOS and EOI are the caller's
+ * (lama_amd.jpeg.jpeg_from_scan; DRI = the MCUs of one row).  Image j's scan starts at out + j * out_stride and has out_bytes[j] bytes; the bytes behind
+ * it are not touched.  A scan longer than out_stride gives out_bytes[j] = -(bytes needed) and writes nothing for that image; an empty slot (h or w < 1)
+ * and one whose sizes do not fit (h > Hs, w > Ws) give 0 and touch nothing else: the sizes are device data, nothing is read or written outside a slot.
+ * Three launches (per MCU row the exact byte count; per image the offsets; per MCU row the bytes), no global atomics, plain vector stores;
+ * asynchronous and hipGraph-capturable.  The same operands give the same bytes.
+ * lama_jpeg_scan_bound: the most bytes the scan of one h x w image can take (every block at its longest codes, every byte stuffed); 0 for refused arguments.
+ * lama_jpeg_scan_workspace_bytes: the workspace (16-byte aligned; 4 bytes per MCU row) of a call with these slots; *bytes is left alone on an error.
+ * LAMA_ERR_BAD_ARG: a null pointer; batch, Hs or Ws <= 0; quality outside 1 .. 100; an unknown subsampling; a workspace that is not 16-byte aligned,
+ * sizes / out_bytes that are not 4-byte aligned.  LAMA_ERR_UNSUPPORTED: more than 65535 pixels a side or MCUs per row; a slot whose bound is beyond
+ * 2^31 - 1 bytes; 2^30 MCU rows or more.  LAMA_ERR_WORKSPACE: a smaller workspace.  Nothing is launched on an error. */
+#define LAMA_JPEG_444 0
+#define LAMA_JPEG_420 1
+size_t lama_jpeg_scan_bound(int32_t h, int32_t w, int32_t subsampling);
+int    lama_jpeg_scan_workspace_bytes(int32_t batch, int32_t Hs, int32_t Ws, int32_t subsampling, size_t* bytes);
+int    lama_jpeg_scan_u8_fwd(void* stream, const uint8_t* image_hwc, const int32_t* sizes, int32_t Hs, int32_t Ws, int32_t batch, int32_t quality,
+                             int32_t subsampling, uint8_t* out, size_t out_stride, int32_t* out_bytes, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,7 @@ class LamaRangeError(LamaError):
 
 F16_MAX = 65504.0
 ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE = -1, -2, -3      # include/lama_hip.h LAMA_ERR_*
+JPEG_444, JPEG_420 = 0, 1      # include/lama_hip.h LAMA_JPEG_*
 FFT_KIND_WINO64, FFT_KIND_IP64, FFT_KIND_IP128, FFT_KIND_TRACE64, FFT_KIND_SEQ, FFT_KIND_SIZED, FFT_KIND_GENERIC = range(7)   # LAMA_FFT_KIND_*
 
 
@@ -205,6 +206,10 @@ class LamaLib:
         L.lama_png_deflate_workspace_bytes.restype, L.lama_png_deflate_workspace_bytes.argtypes = C.c_int, [i32] * 5 + [C.POINTER(sz)]
         L.lama_png_deflate_u8_fwd.restype = C.c_int
         L.lama_png_deflate_u8_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, sz]
+        L.lama_jpeg_scan_bound.restype, L.lama_jpeg_scan_bound.argtypes = sz, [i32] * 3
+        L.lama_jpeg_scan_workspace_bytes.restype, L.lama_jpeg_scan_workspace_bytes.argtypes = C.c_int, [i32] * 4 + [C.POINTER(sz)]
+        L.lama_jpeg_scan_u8_fwd.restype = C.c_int
+        L.lama_jpeg_scan_u8_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp, vp, sz]
         L.lama_eval_ingest_u8_fwd.restype = C.c_int
         L.lama_eval_ingest_u8_fwd.argtypes = [vp, vp, vp, vp, C.POINTER(i32), i32, i32, i32, i32, C.c_float, C.c_float, T, T, vp, i32]
         L.lama_affine_act_fwd.restype = C.c_int
@@ -643,6 +648,35 @@ class LamaLib:
         self.check(self._l.lama_png_deflate_u8_fwd(stream, image_hwc.data_ptr(), sizes.data_ptr(), int(image_hwc.shape[1]), int(image_hwc.shape[2]), c,
                                                    int(batch), int(chunk_bytes), out.data_ptr(), int(out_stride), out_bytes.data_ptr(),
                                                    workspace.data_ptr(), workspace.numel()), 'lama_png_deflate_u8_fwd')
+
+    def jpeg_scan_bound(self, h: int, w: int, subsampling: int = 1) -> int:
+        """lama_jpeg_scan_bound: the most bytes the scan of one h x w image can take (0: arguments the encoder refuses).  ``subsampling``:
+        JPEG_420 (1) or JPEG_444 (0)."""
+        return int(self._l.lama_jpeg_scan_bound(int(h), int(w), int(subsampling)))
+
+    def jpeg_scan_workspace_bytes(self, batch: int, Hs: int, Ws: int, subsampling: int = 1) -> int:
+        n = C.c_size_t(0)
+        self.check(self._l.lama_jpeg_scan_workspace_bytes(int(batch), int(Hs), int(Ws), int(subsampling), C.byref(n)), 'lama_jpeg_scan_workspace_bytes')
+        return int(n.value)
+
+    def jpeg_scan_u8(self, image_hwc: torch.Tensor, sizes: torch.Tensor, out: torch.Tensor, out_stride: int, out_bytes: torch.Tensor,
+                     workspace: torch.Tensor, batch: int, quality: int = 95, subsampling: int = 1, stream: int = 0):
+        """lama_jpeg_scan_u8_fwd: the entropy-coded scan of a baseline JPEG (integer DCT, Annex K tables, one restart interval per MCU row;
+        tests/jpeg_ref.py) of the h x w crop of every u8 slot of ``image_hwc`` [B,Hs,Ws,3], ``sizes`` = device int32 [B,2], into ``out`` (flat u8:
+        slot j starts at byte j * ``out_stride``) and its length into ``out_bytes`` (int32 [B]; 0 for an empty slot, -(bytes needed) for a scan
+        longer than ``out_stride``).  Three launches, asynchronous, capturable."""
+        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or image_hwc.shape[0] < batch:
+            raise LamaError(f'jpeg_scan_u8: image slots {tuple(image_hwc.shape)}: [B,Hs,Ws,3] u8')
+        for t, dt in ((image_hwc, torch.uint8), (out, torch.uint8), (workspace, torch.uint8), (sizes, torch.int32), (out_bytes, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise LamaError(f'jpeg_scan_u8: a contiguous {dt} tensor is needed, got {t.dtype}')
+            if not self.host_emulated and not t.is_cuda:
+                raise LamaError('jpeg_scan_u8: every operand is a device tensor')
+        if sizes.numel() < 2 * batch or out_bytes.numel() < batch or out.numel() < batch * int(out_stride):
+            raise LamaError('jpeg_scan_u8: sizes [B,2] / out_bytes [B] int32, out of batch * out_stride bytes')
+        self.check(self._l.lama_jpeg_scan_u8_fwd(stream, image_hwc.data_ptr(), sizes.data_ptr(), int(image_hwc.shape[1]), int(image_hwc.shape[2]),
+                                                 int(batch), int(quality), int(subsampling), out.data_ptr(), int(out_stride), out_bytes.data_ptr(),
+                                                 workspace.data_ptr(), workspace.numel()), 'lama_jpeg_scan_u8_fwd')
 
     def eval_ingest_u8(self, image_hwc: torch.Tensor, pred_hwc: torch.Tensor, mask: torch.Tensor, sizes, pad_mod: int,
                        out_image: Optional[torch.Tensor], out_pred: Optional[torch.Tensor], mask_sum: Optional[torch.Tensor], batch: int,

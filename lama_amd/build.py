@@ -20,7 +20,7 @@ LIB = os.path.join(LIBDIR, 'liblama_hip.so')
 # Same sources with -DLAMA_PROFILING: kernel-selection overrides, timing ablations and timeline tracers read from the environment.
 # Only tools/ and the forced-path GPU tests load it (tools/_toollib.py, bench.py --lib, LamaLib(path)); the product never does.
 LIB_PROF = os.path.join(LIBDIR, 'liblama_hip_prof.so')
-SOURCES = ['conv_mfma.hip', 'conv_bf16x3.hip', 'conv_f16x3.hip', 'conv_f16.hip', 'fft.hip', 'elementwise.hip', 'refine.hip', 'metrics.hip', 'inception.hip', 'range_stats.hip', 'lfu.hip', 'png.hip']
+SOURCES = ['conv_mfma.hip', 'conv_bf16x3.hip', 'conv_f16x3.hip', 'conv_f16.hip', 'fft.hip', 'elementwise.hip', 'refine.hip', 'metrics.hip', 'inception.hip', 'range_stats.hip', 'lfu.hip', 'png.hip', 'jpeg.hip']
 # Every translation unit is compiled WITHOUT packed-fp32 VALU instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32).
 # Measured on MI355X / ROCm 7.2 (the probes -- tools/race_probe1-9.py, overlap_stress.py -- are in the git history): a v_pk_*_f32 with an op_sel half-swizzle returns wrong
 # results while a wave of ANOTHER kernel executes MFMA instructions on the same SIMD (an inline-asm probe of that one instruction

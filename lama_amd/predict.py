@@ -3,7 +3,8 @@
 
     python -m lama_amd.predict model.path=<dir> indir=<dir> outdir=<dir> \
         [model.checkpoint=best.ckpt] [dataset.img_suffix=.png] [dataset.pad_out_to_modulo=8] [out_ext=.png] \
-        [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]] [device_png=true]
+        [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]] [device_png=true] \
+        [device_jpeg=true [jpeg_quality=95] [jpeg_subsampling=420|444]]
     python -m torch.distributed.run --nproc-per-node N -m lama_amd.predict ...        # one process per GPU
 
 Same on-disk contract as the reference: masks are ``**/*mask*.png`` (sorted, recursive), the image of a mask
@@ -34,13 +35,19 @@ import torch
 
 from . import _lib as L
 from . import config as lcfg
+from . import jpeg as ljpeg
 from . import trainers
 
 DEFAULTS = {'model.checkpoint': 'best.ckpt', 'dataset.img_suffix': '.png', 'dataset.pad_out_to_modulo': 8,
             'out_ext': '.png', 'out_key': 'inpainted', 'batch_size': 8, 'precision': 'f16x3',
             'io_threads': 8,   # configs/prediction/default.yaml (+ batch_size / precision / io_threads: this driver's own)
             'paste_back': False,   # extension, with dataset.scale_factor only: write the SOURCE image with the hole taken from the scaled prediction
-            'device_png': False}   # extension: the PNGs' zlib streams are made on the device (lama_png_deflate_u8_fwd), the host wraps and writes
+            'device_png': False,   # extension: the PNGs' zlib streams are made on the device (lama_png_deflate_u8_fwd), the host wraps and writes
+            # extension (out_ext .jpg / .jpeg): the JPEGs' entropy-coded scans are made on the device (lama_jpeg_scan_u8_fwd) at cv2.imwrite's
+            # quality 95 and libjpeg's 4:2:0, the host adds the headers and writes.  Off: PIL.Image.save at PIL's own defaults (quality 75)
+            'device_jpeg': False, 'jpeg_quality': 95, 'jpeg_subsampling': '420'}
+jpeg_from_scan = ljpeg.jpeg_from_scan
+JPEG_OUT_STRIDE = None      # test hook: bytes per scan slot of the device_jpeg steps (None: the slot's raw byte count)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -59,9 +66,9 @@ REFINER_DEFAULTS = {'refiner.gpu_ids': '0,', 'refiner.modulo': 8, 'refiner.n_ite
 # option types: paths, suffixes and names stay strings whatever they look like (indir=2024, model.checkpoint=100 are a directory and
 # a file name); everything else is a bool / int / float as in the YAML defaults
 STRING_KEYS = {'model.path', 'model.checkpoint', 'indir', 'outdir', 'device', 'dataset.kind', 'dataset.img_suffix', 'out_ext', 'out_key',
-               'precision', 'refiner.gpu_ids'}
-BOOL_KEYS = {'refine', 'profile', 'paste_back', 'device_png'}
-INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
+               'precision', 'refiner.gpu_ids', 'jpeg_subsampling'}
+BOOL_KEYS = {'refine', 'profile', 'paste_back', 'device_png', 'device_jpeg'}
+INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'jpeg_quality', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
             'refiner.px_budget', 'refiner.batch_size'}
 FLOAT_KEYS = {'refiner.lr', 'dataset.scale_factor'}
 
@@ -89,6 +96,7 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
     a drop-in)."""
     cfg = dict(DEFAULTS)
     cfg.update(REFINER_DEFAULTS)
+    given = set()
     for a in argv:
         if '=' not in a:
             raise SystemExit(f'expected key=value, got {a!r}')
@@ -96,6 +104,7 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
         if k not in KNOWN_KEYS:
             raise SystemExit(f'unknown option {k!r}; known: {sorted(KNOWN_KEYS)}')
         cfg[k] = _parse_value(k, v)
+        given.add(k)
     for need in ('model.path', 'indir', 'outdir'):
         if need not in cfg:
             raise SystemExit(f'missing {need}=...')
@@ -119,11 +128,26 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
         if cfg['out_key'] != 'inpainted':
             raise SystemExit(f"paste_back=true with out_key={cfg['out_key']!r} is not served: the pasted result is made from 'inpainted' "
                              f"('predicted_image' is undefined where the mask is 0)")
+    if cfg['device_png'] and cfg['device_jpeg']:
+        raise SystemExit('device_jpeg=true with device_png=true: a step ends with one encoder, and out_ext names one format')
     if cfg['device_png']:
         if not str(cfg['out_ext']).lower().endswith('.png'):
             raise SystemExit(f"device_png=true writes PNG files only: out_ext={cfg['out_ext']!r}")
         if cfg.get('refine', False):
             raise SystemExit('device_png=true with refine=true is not served: refinement writes from host tensors')
+    if not 1 <= cfg['jpeg_quality'] <= 100:
+        raise SystemExit(f"jpeg_quality={cfg['jpeg_quality']!r}: 1 .. 100")
+    if cfg['jpeg_subsampling'] not in ljpeg.SUBSAMPLING:
+        raise SystemExit(f"jpeg_subsampling={cfg['jpeg_subsampling']!r}: 420 or 444")
+    if cfg['device_jpeg']:
+        if not str(cfg['out_ext']).lower().endswith(('.jpg', '.jpeg')):
+            raise SystemExit(f"device_jpeg=true writes JPEG files only (out_ext=.jpg or .jpeg): out_ext={cfg['out_ext']!r}")
+        if cfg.get('refine', False):
+            raise SystemExit('device_jpeg=true with refine=true is not served: refinement writes from host tensors')
+    else:
+        for k in ('jpeg_quality', 'jpeg_subsampling'):
+            if k in given:
+                raise SystemExit(f'{k}= is an option of device_jpeg=true: without it a .jpg is written by PIL at PIL\'s defaults')
     return cfg
 
 
@@ -439,6 +463,46 @@ def _write_png_stream(path: str, h: int, w: int, data: bytes):
         f.write(png_from_zlib(h, w, 3, data))
 
 
+class JpegOverflow(L.LamaError):
+    """A device-encoded scan did not fit its slot (out_bytes = -(bytes needed)): nothing was written for that image."""
+
+    def __init__(self, what: str, needed: int, slot: int):
+        super().__init__(f'{what}: the JPEG scan needs {needed} bytes, its slot holds {slot}')
+        self.needed, self.slot = needed, slot
+
+
+def jpeg_stream_view(flat: np.ndarray, slot: int, len_at: int, j: int, what: str) -> np.ndarray:
+    """Scan j of one flat ``encode_jpeg`` result set (the scan slots of ``slot`` bytes, the int32 lengths from byte ``len_at`` on): a view, empty
+    for an empty slot; JpegOverflow (naming ``what``) for a negative length."""
+    n = int(flat[len_at:].view(np.int32)[j])
+    if n < 0:
+        raise JpegOverflow(what, -n, slot)
+    return flat[j * slot:j * slot + n]
+
+
+def _snap_and_wrap_jpeg(path: str, view: np.ndarray, h: int, w: int, quality: int, subsampling: int, latch: _Latch, pool):
+    """``fast`` pool job of ``device_jpeg``: copy the image's scan out of the pinned result set (then release the latch) and queue its headers +
+    write on ``pool``; returns that future."""
+    try:
+        data = view.tobytes()
+    finally:
+        latch.done()
+    return pool.submit(_write_jpeg_scan, path, h, w, quality, subsampling, data)
+
+
+def _write_jpeg_scan(path: str, h: int, w: int, quality: int, subsampling: int, data: bytes):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(jpeg_from_scan(h, w, quality, subsampling, data))
+
+
+def _write_jpeg_host(path: str, rgb: np.ndarray, quality: int, subsampling: int):
+    """The fallback of ``device_jpeg`` for an image whose scan overflowed its slot: libjpeg on the host at the same quality and subsampling."""
+    from PIL import Image
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    Image.fromarray(rgb).save(path, 'JPEG', quality=int(quality), subsampling=2 if subsampling else 0)
+
+
 def _write_png(path: str, rgb: np.ndarray):
     """bin/predict.py:93-94 (the reference converts RGB -> BGR only because cv2.imwrite expects BGR).  ``.png``: encode_png; any other
     extension goes through PIL, which picks the format from it as cv2.imwrite does."""
@@ -513,11 +577,18 @@ class HostFedStep:
     image's PNG (Sub filter, literal-only dynamic Huffman chunks: tests/png_ref.py), cropped by the sizes array of the form (the scaled sizes with
     ``scale_factor``, the source sizes with ``paste_back``).  The result sets are then ONE flat u8 buffer per parity, ``n`` stream slots of
     ``png_slot`` bytes followed by the ``n`` int32 lengths (``d_out`` on the device, ``h_out`` pinned): one D2H, or one gather, carries both, the u8
-    images are not downloaded (``h_u8`` is None) and ``result_png(p, j)`` is the j-th stream.  ``predict.png_from_zlib`` wraps it into the file."""
+    images are not downloaded (``h_u8`` is None) and ``result_png(p, j)`` is the j-th stream.  ``predict.png_from_zlib`` wraps it into the file.
+
+    ``encode_jpeg`` (off by default; the u8 input forms; not together with ``encode_png``): the step ends with lama_jpeg_scan_u8_fwd instead -- the
+    entropy-coded scan of every image's baseline JPEG at ``jpeg_quality`` and ``jpeg_subsampling`` ('420' / '444'; tests/jpeg_ref.py), cropped by the
+    same sizes array.  The result sets are laid out as the PNG ones: ``n`` scan slots of ``jpeg_slot`` = ``jpeg_out_stride`` bytes (default: the
+    slot's raw byte count Hs Ws 3), then, from byte ``jpeg_len_at`` on, the ``n`` int32 lengths.  ``result_jpeg(p, j)`` is the j-th scan;
+    a scan that did not fit its slot (a negative length: noise at quality 100) raises JpegOverflow.  ``predict.jpeg_from_scan`` adds the headers."""
 
     def __init__(self, model, batch_size: int, Hp: int, Wp: int, device, *, drain: bool = True, binarize: bool = True, mode: str = 'auto',
                  u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True, scale_factor: Optional[float] = None,
-                 src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False, encode_png: bool = False):
+                 src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False, encode_png: bool = False,
+                 encode_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420', jpeg_out_stride: Optional[int] = None):
         self.model, self.n, self.Hp, self.Wp = model, int(batch_size), int(Hp), int(Wp)
         # ``scale_factor`` (dataset.scale_factor, evaluation/data.py:74-77): the third input form -- the step is fed with the DECODED u8 originals in
         # source slots of ``src_hw`` = (Hs, Ws) pixels, and its first launch (lama_resize_u8_fwd) does / 255, the INTER_AREA / INTER_NEAREST
@@ -607,9 +678,31 @@ class HostFedStep:
             self.png_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)       # one: the steps of both parities run in order on one stream
             self.h_u8 = None
             self.d_out, self.h_out = self.png, self.h_png
-        else:
+        elif not encode_jpeg:
             self.h_u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
             self.d_out, self.h_out = self.u8, self.h_u8      # what the D2H branch (or the caller's gather) carries
+        self.encode_jpeg = bool(encode_jpeg)
+        if self.encode_jpeg:
+            # the step ends with lama_jpeg_scan_u8_fwd over u8[p]; the result set is laid out as the PNG one: n scan slots, then the n int32 lengths
+            if self.encode_png:
+                raise L.LamaError('encode_jpeg and encode_png exclude each other: a step ends with one encoder')
+            if self.d_sizes is None:
+                raise L.LamaError('encode_jpeg needs a u8 input form (its crops are the step\'s device sizes array): not with u8_input=False')
+            self.jpeg_quality, self.jpeg_subsampling = int(jpeg_quality), ljpeg.subsampling_code(jpeg_subsampling)
+            if not 1 <= self.jpeg_quality <= 100:
+                raise L.LamaError(f'jpeg_quality {jpeg_quality!r}: 1 .. 100')
+            lib = model.generator._exec.lib
+            ws_bytes = lib.jpeg_scan_workspace_bytes(self.n, *self.out_hw, self.jpeg_subsampling)      # (raises for slots beyond 65535 pixels a side)
+            self.jpeg_slot = int(jpeg_out_stride) if jpeg_out_stride is not None else self.out_hw[0] * self.out_hw[1] * 3
+            if self.jpeg_slot < 1:
+                raise L.LamaError(f'jpeg_out_stride {jpeg_out_stride!r}: at least one byte')
+            self.jpeg_len_at = (self.n * self.jpeg_slot + 15) & ~15
+            self.jpeg_bytes = self.jpeg_len_at + 4 * self.n
+            self.jpeg = [torch.zeros(self.jpeg_bytes, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self.h_jpeg = [torch.zeros(self.jpeg_bytes, dtype=torch.uint8, **pin) for _ in range(2)] if drain else None
+            self.jpeg_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)      # one: the steps of both parities run in order on one stream
+            self.h_u8 = None
+            self.d_out, self.h_out = self.jpeg, self.h_jpeg
         self.graphs = [None, None]
         self.span_events = None       # a list: launch() (mode 'host') appends (start, end) timing events around each step's compute
         self.done = [torch.cuda.Event() for _ in range(2)] if self.on_gpu else None
@@ -671,7 +764,14 @@ class HostFedStep:
     def result(self, p: int) -> np.ndarray:
         if self.encode_png:
             raise L.LamaError('encode_png: the u8 results are not downloaded; result_png(p, j) is the j-th stream')
+        if self.encode_jpeg:
+            raise L.LamaError('encode_jpeg: the u8 results are not downloaded; result_jpeg(p, j) is the j-th scan')
         return self.h_u8[p].numpy()
+
+    def result_jpeg(self, p: int, j: int) -> memoryview:
+        """``encode_jpeg``: the scan of image j of host result set p (empty for an empty slot), a view of the pinned set; JpegOverflow, naming the
+        image, where the scan did not fit its slot."""
+        return memoryview(jpeg_stream_view(self.h_jpeg[p].numpy(), self.jpeg_slot, self.jpeg_len_at, j, f'image {j} of result set {p}'))
 
     def result_png(self, p: int, j: int) -> memoryview:
         """``encode_png``: the zlib stream of image j of host result set p (empty for an empty slot), a view of the pinned set."""
@@ -685,9 +785,15 @@ class HostFedStep:
         return (self.h_dsizes if self.scale is not None and not self.paste_back else self.h_sizes)[p].numpy()
 
     def _encode(self, p: int):
-        """``encode_png``: the two launches over u8[p], cropped by the device sizes array of the form."""
+        """``encode_png`` / ``encode_jpeg``: the encoder's launches over u8[p], cropped by the device sizes array of the form."""
         sizes = self.d_dsizes[p] if self.scale is not None and not self.paste_back else self.d_sizes[p]
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.on_gpu else 0
+        if self.encode_jpeg:
+            flat = self.jpeg[p]
+            self.model.generator._exec.lib.jpeg_scan_u8(self.u8[p], sizes, flat[:self.n * self.jpeg_slot], self.jpeg_slot,
+                                                        flat[self.jpeg_len_at:].view(torch.int32), self.jpeg_ws, self.n, quality=self.jpeg_quality,
+                                                        subsampling=self.jpeg_subsampling, stream=stream)
+            return
         flat = self.png[p]
         self.model.generator._exec.lib.png_deflate_u8(self.u8[p], sizes, flat[:self.n * self.png_slot], self.png_slot,
                                                       flat[self.n * self.png_slot:].view(torch.int32), self.png_ws, self.n, stream=stream)
@@ -695,7 +801,7 @@ class HostFedStep:
     # -- pieces ---------------------------------------------------------------------------------------------------
     def _compute(self, p: int):
         self._compute_u8(p)
-        if self.encode_png:
+        if self.encode_png or self.encode_jpeg:
             self._encode(p)
 
     def _compute_u8(self, p: int):
@@ -859,7 +965,7 @@ class HostFedStep:
 def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[str, str]], indir: str, outdir: str, *,
             pad_mod: int = 8, batch_size: int = 8, out_ext: str = '.png', device='cuda', rank: int = 0, world: int = 1,
             dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None, paste_back: bool = False,
-            device_png: bool = False) -> int:
+            device_png: bool = False, device_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420') -> int:
     """Run every (mask, image) pair through ``model`` and write the results (rank 0).  Returns the number of images written.
     ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled before the padding -- on the device, by
     the first launch of the step, which is fed with the decoded u8 originals (lama_resize_u8_fwd) -- and the results have the rescaled size.
@@ -868,6 +974,10 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
     ``device_png`` (``.png`` only, off by default): every step ends with the PNG's zlib stream made on the device (lama_png_deflate_u8_fwd); the D2H
     and, with several ranks, the gather carry the compressed bytes, and the host only wraps them (png_from_zlib: one CRC) and writes.  The files
     decode to the same pixels; their bytes differ from encode_png's.
+    ``device_jpeg`` (``.jpg`` / ``.jpeg`` only, off by default, not with ``device_png``): every step ends with the JPEG's entropy-coded scan made on
+    the device (lama_jpeg_scan_u8_fwd) at ``jpeg_quality`` / ``jpeg_subsampling``; the copies carry the flat set of scan slots (as large as the u8 set at the default slot size: what is saved is the host's encode) and the host adds the headers
+    (jpeg_from_scan).  An image whose scan overflowed its slot is computed once more at the end of its bucket and encoded on the host.  With the
+    option off a ``.jpg`` is PIL's, at PIL's defaults (quality 75).
 
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
@@ -878,14 +988,15 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
             try:
                 return _predict_once(model, items, indir, outdir, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext, device=device,
                                      rank=rank, world=world, dist=dist, io_threads=io_threads, out_key=out_key, scale_factor=scale_factor,
-                                     paste_back=paste_back, device_png=device_png)
+                                     paste_back=paste_back, device_png=device_png,
+                                     device_jpeg=(int(jpeg_quality), ljpeg.subsampling_code(jpeg_subsampling)) if device_jpeg else None)
             except _RangeRestart:
                 continue                     # the generator switched to the 3-term bf16 split (every rank alike): all images again
         raise L.LamaError('range restart did not converge')
 
 
 def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, device, rank, world, dist, io_threads, out_key='inpainted', scale_factor=None,
-                  paste_back=False, device_png=False) -> int:
+                  paste_back=False, device_png=False, device_jpeg=None) -> int:
     from PIL import Image
 
     def header_size(item):                   # padded shape from the IMAGE's PNG header only: every rank builds the same plan
@@ -897,6 +1008,8 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
         raise L.LamaError('paste_back needs scale_factor: without one the result has the source size already')
     if device_png and not out_ext.lower().endswith('.png'):
         raise L.LamaError(f'device_png writes PNG files only, not {out_ext!r}')
+    if device_jpeg and (device_png or not out_ext.lower().endswith(('.jpg', '.jpeg'))):
+        raise L.LamaError(f'device_jpeg writes JPEG files only (not {out_ext!r}) and excludes device_png')
     lib = model.generator._exec.lib
     pool = ThreadPoolExecutor(io_threads)
     # the copies into / out of the pinned sets are on the round loop's critical path (the next launch waits for them) and take 0.1-0.3 ms each: they
@@ -913,14 +1026,14 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
         rounds = plan_rounds(shapes, batch_size, world)
         return _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext,
                                device=device, rank=rank, world=world, dist=dist, out_key=out_key, fast=fast, scale_factor=scale_factor,
-                               src_sizes=src_sizes, paste_back=paste_back, device_png=device_png)
+                               src_sizes=src_sizes, paste_back=paste_back, device_png=device_png, device_jpeg=device_jpeg)
     finally:
         fast.shutdown()
         pool.shutdown()                      # on every exit path (a raise out of a bucket included): no worker thread outlives the call
 
 
 def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pad_mod, batch_size, out_ext, device, rank, world, dist, out_key='inpainted', fast=None,
-                    scale_factor=None, src_sizes=None, paste_back=False, device_png=False) -> int:
+                    scale_factor=None, src_sizes=None, paste_back=False, device_png=False, device_jpeg=None) -> int:
     """The rounds of one attempt.  Per bucket (padded shape) a ``HostFedStep``: round k computes from device input set k & 1 while the SAME graph
     launch uploads round k + 1's decoded images into the other set and (one rank) downloads round k - 1's u8 results; the host fills the
     pinned set of round k + 1 and queues round k - 2's PNG writes while round k runs.  Several ranks: the results go through the one
@@ -928,7 +1041,9 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
     ``paste_back``: the buckets stay keyed by the padded scaled size, but the u8 results (and the gathered rounds) are the bucket's source slots
     and each PNG is the h x w crop of its SOURCE size.
     ``device_png``: a result set is the step's flat buffer (``batch_size`` stream slots, then their int32 lengths) per rank instead of the u8 images:
-    the snapshot job copies the stream's bytes out of the pinned set and releases the latch, the pool job wraps and writes."""
+    the snapshot job copies the stream's bytes out of the pinned set and releases the latch, the pool job wraps and writes.
+    ``device_jpeg`` = (quality, subsampling): the same with scans; an image whose scan did not fit its slot (JpegOverflow) is put aside, and at the
+    end of its bucket rank 0 computes it once more in a plain u8 step, downloads it and encodes it on the host."""
     futures, written = [], 0                 # futures of the snapshot jobs; each returns the future of its encode + write
     fast = fast if fast is not None else pool
     bucket_paths: List[str] = []             # the PNGs queued for the bucket whose range flag has not been read yet
@@ -948,7 +1063,9 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             loads[r] = [pool.submit(load_item_u8, *items[i]) for i in rounds[r]['batches'][rank]]
 
     snapped = [_Latch(), _Latch()]           # per pinned result set: the workers that still copy their image out of it
-    png_slot = png_set = 0                   # device_png: bytes per stream slot / per rank's result buffer of the current bucket
+    png_slot = png_set = png_len_at = 0      # device_png / device_jpeg: bytes per stream slot / per rank's result buffer / in front of its lengths (current bucket)
+    flat_sets = bool(device_png or device_jpeg)
+    overflowed: List[Tuple[int, str]] = []   # device_jpeg: (item, path) of the scans that did not fit their slot in the current bucket
     crops = src_sizes if paste_back else sizes
 
     def write_round(rd, host, pset):
@@ -956,7 +1073,7 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
         set ``pset``; ``paste_back``: [ranks * batch_size, Hs, Ws, 3]).  The workers snapshot their image themselves (the main thread only queues); ``snapped[pset].wait()`` before that set is
         downloaded into again."""
         nonlocal written
-        host = host.reshape(-1) if device_png else host
+        host = host.reshape(-1) if flat_sets else host
         for r, idxs in enumerate(rd['batches']):
             for j, i in enumerate(idxs):
                 mask_path = items[i][0]
@@ -964,9 +1081,21 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
                 rel = os.path.splitext(mask_path[len(indir):].lstrip(os.sep))[0] + out_ext      # bin/predict.py:69-72
                 bucket_paths.append(os.path.join(outdir, rel))
                 snapped[pset].add()
-                if device_png:
+                if device_jpeg:
+                    try:
+                        view = jpeg_stream_view(host[r * png_set:(r + 1) * png_set], png_slot, png_len_at, j, mask_path)
+                    except JpegOverflow:
+                        snapped[pset].done()
+                        overflowed.append((i, bucket_paths[-1]))
+                        written += 1
+                        continue
+                    if view.size == 0:
+                        snapped[pset].done()
+                        raise L.LamaError(f'{mask_path}: the device encoder returned no scan for a {h}x{w} image')
+                    futures.append(fast.submit(_snap_and_wrap_jpeg, bucket_paths[-1], view, h, w, *device_jpeg, snapped[pset], pool))
+                elif device_png:
                     base = r * png_set + j * png_slot
-                    n = int(host[r * png_set + batch_size * png_slot:(r + 1) * png_set].view(np.int32)[j])
+                    n = int(host[r * png_set + png_len_at:(r + 1) * png_set].view(np.int32)[j])
                     if n <= 0:
                         snapped[pset].done()
                         raise L.LamaError(f'{mask_path}: the device encoder returned no stream for a {h}x{w} image')
@@ -990,15 +1119,18 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             members = [src_sizes[i] for rd in rounds[r0:r1] for b in rd['batches'] for i in b]
             src_hw = (max(h for h, _ in members), max(w for _, w in members))
         hs = HostFedStep(model, batch_size, Hp, Wp, device, drain=(world == 1), tune=(K >= TUNE_MIN_ROUNDS), capture=(K >= CAPTURE_MIN_ROUNDS), out_key=out_key,
-                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png)
+                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png,
+                         **(dict(encode_jpeg=True, jpeg_quality=device_jpeg[0], jpeg_subsampling=device_jpeg[1], jpeg_out_stride=JPEG_OUT_STRIDE) if device_jpeg else {}))
         if device_png:
-            png_slot, png_set = hs.png_slot, hs.png_bytes
+            png_slot, png_set, png_len_at = hs.png_slot, hs.png_bytes, batch_size * hs.png_slot
+        if device_jpeg:
+            png_slot, png_set, png_len_at = hs.jpeg_slot, hs.jpeg_bytes, hs.jpeg_len_at
         LOOP_TIMES['bucket_setup'] = LOOP_TIMES.get('bucket_setup', 0.0) + time.perf_counter() - t_
         if PROFILE_SPANS:
             hs.span_events = []
         gathered = h_out = None
         if world > 1 and rank == 0:
-            set_shape = (world * hs.png_bytes,) if device_png else (world * batch_size, *hs.out_hw, 3)      # device_png: every rank's flat result buffer
+            set_shape = (world * png_set,) if flat_sets else (world * batch_size, *hs.out_hw, 3)      # device_png / device_jpeg: every rank's flat result buffer
             gathered = [torch.empty(*set_shape, dtype=torch.uint8, device=device) for _ in range(2)]
             h_out = [torch.zeros(*set_shape, dtype=torch.uint8, **(dict(pin_memory=True) if on_gpu else {})) for _ in range(2)]
         works = [None, None]
@@ -1088,6 +1220,22 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
                 LOOP_TIMES['gpu_first_start_to_last_end'] = LOOP_TIMES.get('gpu_first_start_to_last_end', 0.0) + ev[0][0].elapsed_time(ev[-1][1]) * 1e-3
                 LOOP_TIMES['steps'] = LOOP_TIMES.get('steps', 0.0) + len(ev)
 
+        if overflowed:                       # device_jpeg, rank 0: the images whose scan did not fit -- a plain u8 step, a download of their own, libjpeg
+            fb = HostFedStep(model, batch_size, Hp, Wp, device, drain=True, tune=False, capture=False, out_key=out_key, scale_factor=scale_factor,
+                             src_hw=src_hw, paste_back=paste_back)
+            for c0 in range(0, len(overflowed), batch_size):
+                part = overflowed[c0:c0 + batch_size]
+                for j in range(batch_size):
+                    fb.put(0, j, *(load_item_u8(*items[part[j][0]])[:2] if j < len(part) else (None, None)))
+                fb.prime(0)
+                fb.launch(0)
+                fb.wait(0)
+                fb.flush(0)
+                for j, (i, pth) in enumerate(part):
+                    h, w = crops[i]
+                    futures.append(fast.submit(pool.submit, _write_jpeg_host, pth, fb.result(0)[j, :h, :w].copy(), *device_jpeg))
+            overflowed.clear()
+            del fb
         # the bucket's ONE read-back of the fp16 split's range flag (the forwards above did not synchronise); all ranks decide alike
         def red(bad, _dev=hs.device):
             t = torch.tensor([1 if bad else 0], dtype=torch.int32, device=_dev)
@@ -1242,7 +1390,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     t0 = time.perf_counter()
     n = predict(model, items, indir, cfg['outdir'], pad_mod=int(cfg['dataset.pad_out_to_modulo']), batch_size=int(cfg['batch_size']),
                 out_ext=cfg['out_ext'], device=device, rank=rank, world=world, dist=dist, io_threads=int(cfg['io_threads']), out_key=cfg['out_key'],
-                scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']), device_png=bool(cfg['device_png']))
+                scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']), device_png=bool(cfg['device_png']),
+                device_jpeg=bool(cfg['device_jpeg']), jpeg_quality=cfg['jpeg_quality'], jpeg_subsampling=cfg['jpeg_subsampling'])
     dt = time.perf_counter() - t0
     if rank == 0:
         # (the loop's own wall time: plan build + graph capture of every shape bucket, PNG decode, upload, compute, download, PNG encode + write)
