@@ -607,6 +607,33 @@ int lama_lfu_tile_add_fwd(void* stream, const lama_tensor* a, const lama_tensor*
 int lama_paste_back_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes, int32_t Hs,
                            int32_t Ws, const lama_tensor* lowres, uint8_t* out_hwc, int32_t batch, int32_t binarize);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) crop_to_mask: the two ends of a u8 predict step whose
+ * generator sees only a WINDOW of each source slot.  THIS OUTPUT HAS NO COUNTERPART IN THE REFERENCE (a crop sees less context than the whole
+ * image): it is this engine's own definition -- the existing u8 step run on the cropped arrays, pasted by slicing -- pinned bit for bit by
+ * tests/crop_util.py against lama_mask_compose_u8_fwd / lama_blend_quantize_u8_fwd on host-cropped slots and against a numpy restatement.
+ * image_hwc [B][Hs][Ws][3], mask [B][Hs][Ws], out_hwc [B][Hs][Ws][3]: u8 source slots on the device, each image's own h x w pixels in the
+ * top-left corner; src_sizes: device int32 [B][2] = (h, w) (h = 0: an empty slot); rects: device int32 [B][4] = (y0, x0, ch, cw).
+ * For image b let C = image[b, y0:y0+ch, x0:x0+cw] and M = mask[b, y0:y0+ch, x0:x0+cw].
+ *   lama_crop_compose_u8_fwd: out fp32 [B,4,Hp,Wp] = what lama_mask_compose_u8_fwd writes for a slot batch holding C, M with sizes (ch, cw):
+ *     C / 255.f (IEEE fp32 division), np.pad(mode='symmetric') at the bottom / right up to (Hp, Wp) (periodic beyond 2 ch rows), m = mask > 0
+ *     (binarize != 0) or M / 255.f, out = cat(C * (1 - m), m).  4 bytes read and 16 written per pixel of the view.
+ *   lama_crop_paste_u8_fwd: out_hwc[b, :h, :w] = the source bytes, and inside the window the bytes lama_blend_quantize_u8_fwd gives for
+ *     (C, M, pred): clip((m * pred + (1 - m) * C / 255.f) * 255, 0, 255) truncated -- the source byte where the mask byte is 0; pred, fp32
+ *     [B,3,Hp,Wp] (any batch_stride >= 3 Hp Wp: channel-slice views work), is read only inside the window where the mask byte is not 0.  A NaN
+ *     quantises to 0.  Slot bytes outside h x w are written as 0.  7 bytes per source pixel (1 + 3 read, 3 written).
+ * A rect that does not fit -- ch or cw < 1, y0 or x0 < 0, y0 + ch > h, x0 + cw > w, ch > Hp, cw > Wp, h > Hs, w > Ws -- behaves as an empty slot:
+ * the compose writes zeros for that image, the paste writes the whole slot as 0.  Sizes and rects are device data: nothing is read or written
+ * out of bounds.  Dword accesses to the slots where Ws % 4 == 0 and the slot pointers are 4-byte aligned (the compose: and x0 % 4 == 0), float4
+ * stores to a view with Wp % 4 == 0, a 16-byte aligned pointer and batch_stride % 4 == 0; byte / scalar accesses otherwise.  No floating-point
+ * contraction in either kernel.  One launch each, no workspace, no atomics: asynchronous and hipGraph-capturable.
+ * LAMA_ERR_BAD_ARG: a null pointer; batch, Hs or Ws <= 0; a view that is not [., 4, H, W] (compose) / [., 3, H, W] (paste); batch_stride < C H W;
+ * a view pointer that is not 4-byte aligned; out_hwc == image_hwc.  LAMA_ERR_UNSUPPORTED: a view that is not fp32; 2^30 work items (of 4 pixels)
+ * or more per image; a view plane of 2^30 elements or more (paste).  Nothing is launched on an error. */
+int lama_crop_compose_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects, int32_t Hs,
+                             int32_t Ws, const lama_tensor* out, int32_t batch, int32_t binarize);
+int lama_crop_paste_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects, int32_t Hs,
+                           int32_t Ws, const lama_tensor* pred, uint8_t* out_hwc, int32_t batch, int32_t binarize);
+
 /* ---- (added to v112 without a version bump: new symbols only, nothing else changes) the zlib stream of a PNG's IDAT, made on the device from u8
  * HWC slots.  A PNG encoder owes the decoder the pixels, not particular bytes: THE STREAM IS THIS ENGINE'S OWN DEFINITION, pinned byte for byte by
  * tests/png_ref.py::deflate_ref.  image_hwc [batch][Hs][Ws][channels] u8 slots, each image's h x w pixels in the top-left corner; sizes: device int32

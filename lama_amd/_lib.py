@@ -202,6 +202,10 @@ class LamaLib:
         L.lama_resize_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_double, T, T, i32, i32]
         L.lama_paste_back_u8_fwd.restype = C.c_int
         L.lama_paste_back_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, vp, i32, i32]
+        L.lama_crop_compose_u8_fwd.restype = C.c_int
+        L.lama_crop_compose_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, i32, i32]
+        L.lama_crop_paste_u8_fwd.restype = C.c_int
+        L.lama_crop_paste_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, vp, i32, i32]
         L.lama_png_deflate_bound.restype, L.lama_png_deflate_bound.argtypes = sz, [i32] * 4
         L.lama_png_deflate_workspace_bytes.restype, L.lama_png_deflate_workspace_bytes.argtypes = C.c_int, [i32] * 5 + [C.POINTER(sz)]
         L.lama_png_deflate_u8_fwd.restype = C.c_int
@@ -619,6 +623,35 @@ class LamaLib:
         self.check(self._l.lama_paste_back_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
                                                   int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(lowres), out_hwc.data_ptr(), batch,
                                                   int(bool(binarize))), 'lama_paste_back_u8_fwd')
+
+    def _crop_operands(self, what: str, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, batch: int):
+        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
+            raise LamaError(f'{what}: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
+        for t, dt in ((image_hwc, torch.uint8), (mask, torch.uint8), (src_sizes, torch.int32), (rects, torch.int32)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise LamaError(f'{what}: a contiguous {dt} tensor is needed, got {t.dtype}')
+        if src_sizes.numel() < 2 * batch or rects.numel() < 4 * batch:
+            raise LamaError(f'{what}: src_sizes is [B,2] int32, rects [B,4] int32')
+
+    def crop_compose_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, out: Tensor4, batch: int,
+                        binarize: bool = True, stream: int = 0):
+        """lama_crop_compose_u8_fwd: the generator's input [B,4,Hp,Wp] fp32 from the window ``rects`` [B,4] = (y0, x0, ch, cw) of each u8 source slot
+        [B,Hs,Ws,3] / mask slot [B,Hs,Ws] -- what ``mask_compose_u8`` writes for the cropped arrays with sizes (ch, cw), bit for bit."""
+        self._crop_operands('crop_compose_u8', image_hwc, mask, src_sizes, rects, batch)
+        self.check(self._l.lama_crop_compose_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
+                                                    int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(out), batch, int(bool(binarize))),
+                   'lama_crop_compose_u8_fwd')
+
+    def crop_paste_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, pred: Tensor4,
+                      out_hwc: torch.Tensor, batch: int, binarize: bool = True, stream: int = 0):
+        """lama_crop_paste_u8_fwd: ``out_hwc`` [B,Hs,Ws,3] u8 (another buffer than ``image_hwc``) = the source slots with, inside each window, the
+        bytes ``blend_quantize_u8`` gives for the cropped arrays and the generator's output ``pred`` [B,3,Hp,Wp] of the window."""
+        self._crop_operands('crop_paste_u8', image_hwc, mask, src_sizes, rects, batch)
+        if tuple(out_hwc.shape) != tuple(image_hwc.shape) or out_hwc.dtype != torch.uint8 or not out_hwc.is_contiguous():
+            raise LamaError(f'crop_paste_u8: out slots {tuple(out_hwc.shape)} {out_hwc.dtype}: contiguous u8 slots like the image slots {tuple(image_hwc.shape)}')
+        self.check(self._l.lama_crop_paste_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
+                                                  int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(pred), out_hwc.data_ptr(), batch,
+                                                  int(bool(binarize))), 'lama_crop_paste_u8_fwd')
 
     def png_deflate_bound(self, h: int, w: int, channels: int = 3, chunk_bytes: int = 0) -> int:
         """lama_png_deflate_bound: the most bytes the stream of one h x w image can take (0: empty, or arguments the encoder refuses)."""

@@ -746,6 +746,219 @@ template <bool VEC, bool ROW> __global__ __launch_bounds__(PB_THREADS) void past
     }
 }
 
+// ---- crop_to_mask: the step's two ends when the generator sees only a WINDOW (y0, x0, ch, cw) of each image's source slot --
+//   crop_compose_u8_kernel = mask_compose_u8_kernel, crop_paste_u8_kernel = blend_quantize_u8_kernel on the slot batch that would hold
+//   C = image[y0:y0+ch, x0:x0+cw] and M = mask[y0:y0+ch, x0:x0+cw] with sizes (ch, cw) -- BIT FOR BIT (tests/crop_util.py holds both to those
+//   entries on host-cropped slots and to a numpy restatement), so the expressions below are theirs, with floating-point contraction OFF -- and
+//   the paste writes every source byte outside the window (and inside it where the mask byte is 0: (k / 255.f) * 255.f truncates to k) as it is.
+// Like paste_back this output has no counterpart in the reference.  Work items of 4 consecutive pixels of a row as in paste_back_u8_kernel: a
+// 256-thread workgroup takes CR_UNROLL * 256 items of ONE image (sizes, rect and their checks are uniform: scalar loads), every load of a lane
+// before its first store.  The compose writes 16 bytes per window pixel (a float4 per plane and item) for 4 read; the paste moves 7 bytes per
+// SOURCE pixel and reads the prediction only under the mask, inside the window.  No LDS, no atomics.
+#define CR_THREADS 256
+#define CR_UNROLL 4
+struct CropParams {
+    const uint8_t* img;          // [B][Hs][Ws][3], each image's h x w pixels in the top-left corner of its slot
+    const uint8_t* mask;         // [B][Hs][Ws]
+    const int32_t* src_sizes;    // [B][2] = (h, w); h = 0: an empty slot
+    const int32_t* rects;        // [B][4] = (y0, x0, ch, cw): the window
+    const float* pred;           // paste: [B,3,Hp,Wp]
+    long long pred_bs;
+    float* out;                  // compose: [B,4,Hp,Wp]
+    long long out_bs;
+    uint8_t* out_u8;             // paste: [B][Hs][Ws][3]
+    int Hs, Ws, Hp, Wp, binarize;
+    int qpr, chunks, ygroups;    // items per row (compose: of the padded window, paste: of the slot); workgroups per row (ROW) / per image; row groups (ROW)
+    int vec_ld, vec_st;          // compose: dword loads from the slots (Ws % 4 == 0, aligned pointers) / float4 stores (Wp % 4 == 0, aligned view)
+};
+struct CropRect {
+    int h, w, y0, x0, ch, cw;
+    bool ok;
+};
+// An empty slot, or a rect that does not fit its image, the slot or the view (device data: the host cannot see it without a synchronisation).
+// Every comparison is on values already known to be in range, so nothing overflows.
+__device__ __forceinline__ CropRect crop_rect_load(const CropParams& p, int b) {
+    CropRect r;
+    r.h = p.src_sizes[2 * b]; r.w = p.src_sizes[2 * b + 1];
+    r.y0 = p.rects[4 * b]; r.x0 = p.rects[4 * b + 1]; r.ch = p.rects[4 * b + 2]; r.cw = p.rects[4 * b + 3];
+    r.ok = r.h > 0 && r.w > 0 && r.h <= p.Hs && r.w <= p.Ws && r.ch >= 1 && r.cw >= 1 && r.ch <= p.Hp && r.cw <= p.Wp && r.ch <= r.h && r.cw <= r.w &&
+           r.y0 >= 0 && r.x0 >= 0 && r.y0 <= r.h - r.ch && r.x0 <= r.w - r.cw;
+    return r;
+}
+// masked_img = cat(C / 255 * (1 - m), m) with the symmetric padding of C up to (Hp, Wp): mask_compose_u8_kernel on the window
+__global__ __launch_bounds__(CR_THREADS) void crop_compose_u8_kernel(CropParams p) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x / p.chunks, chunk = blockIdx.x - b * p.chunks;
+    const int tid = threadIdx.x;
+    const CropRect r = crop_rect_load(p, b);
+    // (a rect that does not fit reads pixel (0, 0) of its slot and writes zeros)
+    const int y0 = r.ok ? r.y0 : 0, x0 = r.ok ? r.x0 : 0, ch = r.ok ? r.ch : 1, cw = r.ok ? r.cw : 1;
+    const long long slot = (long long)b * p.Hs * p.Ws;
+    const uint8_t* img = p.img + slot * 3;
+    const uint8_t* msk = p.mask + slot;
+    const long long hw = (long long)p.Hp * p.Wp;
+    float* out = p.out + b * p.out_bs;
+    const int nitems = p.Hp * p.qpr;
+    const bool vld = p.vec_ld && (x0 & 3) == 0;          // the window's rows start on a dword of the slot
+
+    int yy[CR_UNROLL], qq[CR_UNROLL];
+    bool valid[CR_UNROLL];
+    uint32_t m4[CR_UNROLL], d[CR_UNROLL][3];
+#pragma unroll
+    for (int k = 0; k < CR_UNROLL; ++k) {                 // the loads of every item (a lane past the end re-reads the last item and stores nothing)
+        const int v = (chunk * CR_UNROLL + k) * CR_THREADS + tid;
+        valid[k] = v < nitems;
+        const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
+        const int y = (int)(vc / (unsigned)p.qpr), q = (int)(vc - (unsigned)y * (unsigned)p.qpr);
+        yy[k] = y; qq[k] = q;
+        const long long row = (long long)(y0 + ew_symmetric(y, ch)) * p.Ws + x0;
+        if (vld && 4 * q + 4 <= cw) {                     // four pixels of the window itself: one dword of mask, three of RGB
+            const long long px = row + 4 * q;
+            m4[k] = *reinterpret_cast<const ei_u32*>(msk + px);
+            const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
+            d[k][0] = s[0]; d[k][1] = s[1]; d[k][2] = s[2];
+        } else {
+            m4[k] = d[k][0] = d[k][1] = d[k][2] = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                 // (a column past the view's edge re-reads the last one; it is never stored)
+                const int x = 4 * q + j < p.Wp ? 4 * q + j : p.Wp - 1;
+                const long long px = row + ew_symmetric(x, cw);
+                m4[k] |= (uint32_t)msk[px] << (8 * j);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) d[k][(3 * j + c) >> 2] |= (uint32_t)img[px * 3 + c] << (8 * ((3 * j + c) & 3));
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CR_UNROLL; ++k) {
+        if (!valid[k]) continue;
+        float v[4][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float rgb[3] = {0.f, 0.f, 0.f}, m = 0.f;
+            if (r.ok) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[c] = (float)((d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3))) & 255u) / 255.0f;
+                const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
+                m = p.binarize ? (mu > 0 ? 1.0f : 0.0f) : (float)mu / 255.0f;
+            }
+            const float km = 1.0f - m;
+            v[0][j] = rgb[0] * km; v[1][j] = rgb[1] * km; v[2][j] = rgb[2] * km; v[3][j] = m;
+        }
+        float* o = out + (long long)yy[k] * p.Wp + 4 * qq[k];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (p.vec_st) {
+                *reinterpret_cast<float4*>(o + c * hw) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (4 * qq[k] + j < p.Wp) o[c * hw + j] = v[c][j];
+            }
+        }
+    }
+}
+// out = the source bytes, with blend_quantize_u8_kernel's bytes for (C, M, pred) inside the window; zeros outside h x w.  The item walk, the
+// VEC / ROW forms and the load / store phases are paste_back_u8_kernel's.
+template <bool VEC, bool ROW> __global__ __launch_bounds__(CR_THREADS) void crop_paste_u8_kernel(CropParams p) {
+#pragma clang fp contract(off)
+    int blk = blockIdx.x;
+    const int chunk = blk % p.chunks; blk /= p.chunks;
+    const int yg = ROW ? blk % p.ygroups : 0, b = ROW ? blk / p.ygroups : blk;
+    const int tid = threadIdx.x;
+    const CropRect r = crop_rect_load(p, b);
+    const long long slot = (long long)b * p.Hs * p.Ws;
+    const uint8_t* img = p.img + slot * 3;
+    const uint8_t* msk = p.mask + slot;
+    uint8_t* out = p.out_u8 + slot * 3;
+    const char* pred = reinterpret_cast<const char*>(p.pred + (long long)b * p.pred_bs);
+    const long long plane = 4ll * p.Hp * p.Wp;           // bytes of one plane of the prediction, < 2^32
+    const int nitems = p.Hs * p.qpr;
+
+    int yy[CR_UNROLL], qq[CR_UNROLL];
+    bool valid[CR_UNROLL];
+    uint32_t m4[CR_UNROLL], d[CR_UNROLL][3];
+#pragma unroll
+    for (int k = 0; k < CR_UNROLL; ++k) {                 // the streaming loads of every item, none behind a branch
+        int y, q;
+        if (ROW) {
+            y = yg * CR_UNROLL + k; q = chunk * CR_THREADS + tid;
+            valid[k] = y < p.Hs && q < p.qpr;
+            y = y < p.Hs ? y : p.Hs - 1; q = q < p.qpr ? q : p.qpr - 1;
+        } else {
+            const int v = (chunk * CR_UNROLL + k) * CR_THREADS + tid;
+            valid[k] = v < nitems;
+            const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
+            y = (int)(vc / (unsigned)p.qpr); q = (int)(vc - (unsigned)y * (unsigned)p.qpr);
+        }
+        yy[k] = y; qq[k] = q;
+        const long long row = (long long)y * p.Ws;
+        if (VEC) {
+            const long long px = row + 4 * q;
+            m4[k] = *reinterpret_cast<const ei_u32*>(msk + px);
+            const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
+            d[k][0] = s[0]; d[k][1] = s[1]; d[k][2] = s[2];
+        } else {
+            m4[k] = d[k][0] = d[k][1] = d[k][2] = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                 // (a column past the slot's edge re-reads the last one; it is never stored)
+                const int x = 4 * q + j < p.Ws ? 4 * q + j : p.Ws - 1;
+                m4[k] |= (uint32_t)msk[row + x] << (8 * j);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) d[k][(3 * j + c) >> 2] |= (uint32_t)img[(row + x) * 3 + c] << (8 * ((3 * j + c) & 3));
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CR_UNROLL; ++k) {                 // the bytes to store, in place of the bytes loaded
+        uint32_t o[3] = {0u, 0u, 0u};
+        const int y = yy[k], xq = 4 * qq[k];
+        if (valid[k] && r.ok && y < r.h) {
+            const bool inrow = y >= r.y0 && y - r.y0 < r.ch;
+            // byte offset of the window row inside one plane in 32 bits (the entry has checked that it fits)
+            const unsigned prow = inrow ? 4u * (unsigned)(y - r.y0) * (unsigned)p.Wp : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = xq + j;
+                if (x < r.w) {
+                    const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
+                    uint32_t sb[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sb[c] = (d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3))) & 255u;
+                    if (mu != 0u && inrow && x >= r.x0 && x - r.x0 < r.cw) {       // the only lanes that read the prediction
+                        const unsigned off = prow + 4u * (unsigned)(x - r.x0);
+                        float pr[3];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) pr[c] = *reinterpret_cast<const float*>(pred + c * plane + off);
+                        const float m = p.binarize ? 1.0f : (float)mu / 255.0f, km = 1.0f - m;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) sb[c] = pb_quant(ew_blend(m, km, pr[c], (float)sb[c] / 255.0f));
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) o[(3 * j + c) >> 2] |= sb[c] << (8 * ((3 * j + c) & 3));
+                }
+            }
+        }
+        d[k][0] = o[0]; d[k][1] = o[1]; d[k][2] = o[2];
+    }
+#pragma unroll
+    for (int k = 0; k < CR_UNROLL; ++k) {
+        if (!valid[k]) continue;
+        const long long px = (long long)yy[k] * p.Ws + 4 * qq[k];
+        if (VEC) {
+            ei_u32* s = reinterpret_cast<ei_u32*>(out + px * 3);
+            s[0] = d[k][0]; s[1] = d[k][1]; s[2] = d[k][2];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * qq[k] + j < p.Ws) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) out[(px + j) * 3 + c] = (uint8_t)(d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3)));
+                }
+        }
+    }
+}
+
 struct AffineParams {
     const float* x;
     long long x_bs;
@@ -1074,6 +1287,70 @@ extern "C" int lama_paste_back_u8_fwd(void* stream, const uint8_t* image_hwc, co
     if (vec) { if (row) PB_LAUNCH(true, true); else PB_LAUNCH(true, false); }
     else { if (row) PB_LAUNCH(false, true); else PB_LAUNCH(false, false); }
 #undef PB_LAUNCH
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// crop_to_mask: the generator's input from a window of each source slot, and its result pasted into the source: see crop_compose_u8_kernel
+extern "C" int lama_crop_compose_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects,
+                                        int32_t Hs, int32_t Ws, const lama_tensor* out, int32_t batch, int32_t binarize) {
+    if (!image_hwc || !mask || !src_sizes || !rects || !out || !out->ptr) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0 || out->C != 4 || out->H <= 0 || out->W <= 0) return LAMA_ERR_BAD_ARG;
+    if (out->batch_stride < (int64_t)4 * out->H * out->W) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({out})) return LAMA_ERR_UNSUPPORTED;
+    if ((uintptr_t)out->ptr & 3) return LAMA_ERR_BAD_ARG;
+    CropParams p;
+    memset(&p, 0, sizeof(p));
+    p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.rects = rects;
+    p.out = (float*)out->ptr; p.out_bs = out->batch_stride;
+    p.Hs = Hs; p.Ws = Ws; p.Hp = out->H; p.Wp = out->W; p.binarize = binarize != 0;
+    p.qpr = (int)lama_ceil_div64(out->W, 4);                         // (64-bit: W + 3 may not fit an int)
+    const long long n = (long long)out->H * p.qpr;
+    if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;                // 32-bit item indices
+    p.chunks = (int)lama_ceil_div64(n, CR_THREADS * CR_UNROLL);
+    p.vec_ld = Ws % 4 == 0 && !(((uintptr_t)image_hwc | (uintptr_t)mask) & 3);
+    p.vec_st = out->W % 4 == 0 && out->batch_stride % 4 == 0 && !((uintptr_t)out->ptr & 15);
+    const long long nwg = (long long)batch * p.chunks;
+    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
+    hipLaunchKernelGGL(crop_compose_u8_kernel, dim3((unsigned)nwg), dim3(CR_THREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+extern "C" int lama_crop_paste_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects,
+                                      int32_t Hs, int32_t Ws, const lama_tensor* pred, uint8_t* out_hwc, int32_t batch, int32_t binarize) {
+    if (!image_hwc || !mask || !src_sizes || !rects || !pred || !pred->ptr || !out_hwc) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0 || pred->C != 3 || pred->H <= 0 || pred->W <= 0) return LAMA_ERR_BAD_ARG;
+    if (pred->batch_stride < (int64_t)3 * pred->H * pred->W || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({pred})) return LAMA_ERR_UNSUPPORTED;
+    if ((uintptr_t)pred->ptr & 3) return LAMA_ERR_BAD_ARG;
+    if ((long long)pred->H * pred->W > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;          // 32-bit byte offsets inside a plane of the prediction
+    CropParams p;
+    memset(&p, 0, sizeof(p));
+    p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.rects = rects;
+    p.pred = (const float*)pred->ptr; p.pred_bs = pred->batch_stride;
+    p.out_u8 = out_hwc;
+    p.Hs = Hs; p.Ws = Ws; p.Hp = pred->H; p.Wp = pred->W; p.binarize = binarize != 0;
+    p.qpr = (int)lama_ceil_div64(Ws, 4);                             // (64-bit here and below: Ws + 3, Hs + 3 may not fit an int)
+    const bool vec = Ws % 4 == 0 && !(((uintptr_t)image_hwc | (uintptr_t)mask | (uintptr_t)out_hwc) & 3);
+    const bool row = p.qpr >= PB_ROW_MIN_ITEMS;
+    long long nwg;
+    if (row) {
+        p.chunks = (int)lama_ceil_div64(p.qpr, CR_THREADS);
+        p.ygroups = (int)lama_ceil_div64(Hs, CR_UNROLL);
+        nwg = (long long)batch * p.ygroups * p.chunks;
+    } else {
+        const long long n = (long long)Hs * p.qpr;
+        if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;            // 32-bit item indices
+        p.chunks = (int)lama_ceil_div64(n, CR_THREADS * CR_UNROLL);
+        nwg = (long long)batch * p.chunks;
+    }
+    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
+    const dim3 grid((unsigned)nwg), block(CR_THREADS);
+#define CR_LAUNCH(V, R) hipLaunchKernelGGL((crop_paste_u8_kernel<V, R>), grid, block, 0, (hipStream_t)stream, p)
+    if (vec) { if (row) CR_LAUNCH(true, true); else CR_LAUNCH(true, false); }
+    else { if (row) CR_LAUNCH(false, true); else CR_LAUNCH(false, false); }
+#undef CR_LAUNCH
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }

@@ -4,6 +4,7 @@
     python -m lama_amd.predict model.path=<dir> indir=<dir> outdir=<dir> \
         [model.checkpoint=best.ckpt] [dataset.img_suffix=.png] [dataset.pad_out_to_modulo=8] [out_ext=.png] \
         [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]] [device_png=true] \
+        [crop_to_mask=true [crop_margin=128] [crop_step=128]] \
         [device_jpeg=true [jpeg_quality=95] [jpeg_subsampling=420|444]]
     python -m torch.distributed.run --nproc-per-node N -m lama_amd.predict ...        # one process per GPU
 
@@ -13,6 +14,8 @@ is ``<mask path up to '_mask'><img_suffix>`` (``evaluation/data.py:59-62``), the
 ``clip(inpainted*255, 0, 255).astype(uint8)`` cropped to the unpadded size (``bin/predict.py:86-94``).
 ``paste_back=true`` (with ``dataset.scale_factor`` only; an output of this driver's own, the reference has none like it) writes the SOURCE image
 with the pixels under the mask taken from the scaled prediction, resampled bilinearly on the device (lama_paste_back_u8_fwd).
+``crop_to_mask=true`` (another output of this driver's own) runs the generator on a window around each mask (``crop_rect``) at the source resolution
+and writes the SOURCE image with the window's inpainted pixels pasted in on the device (lama_crop_compose_u8_fwd / lama_crop_paste_u8_fwd).
 
 What differs from the reference's batch-1 Python loop: images are padded to ``pad_out_to_modulo`` and *bucketed by
 padded shape*, each bucket is cut into batches, batches are dealt round-robin to the ranks (one process per GPU,
@@ -26,6 +29,7 @@ import contextlib
 import glob
 import os
 import sys
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -45,7 +49,10 @@ DEFAULTS = {'model.checkpoint': 'best.ckpt', 'dataset.img_suffix': '.png', 'data
             'device_png': False,   # extension: the PNGs' zlib streams are made on the device (lama_png_deflate_u8_fwd), the host wraps and writes
             # extension (out_ext .jpg / .jpeg): the JPEGs' entropy-coded scans are made on the device (lama_jpeg_scan_u8_fwd) at cv2.imwrite's
             # quality 95 and libjpeg's 4:2:0, the host adds the headers and writes.  Off: PIL.Image.save at PIL's own defaults (quality 75)
-            'device_jpeg': False, 'jpeg_quality': 95, 'jpeg_subsampling': '420'}
+            'device_jpeg': False, 'jpeg_quality': 95, 'jpeg_subsampling': '420',
+            # extension: the generator runs on a window around each mask's bounding box (crop_rect: the box + crop_margin a side, rounded up to
+            # crop_step) at native resolution, and the result is pasted into the source image on the device (lama_crop_paste_u8_fwd)
+            'crop_to_mask': False, 'crop_margin': 128, 'crop_step': 128}
 jpeg_from_scan = ljpeg.jpeg_from_scan
 JPEG_OUT_STRIDE = None      # test hook: bytes per scan slot of the device_jpeg steps (None: the slot's raw byte count)
 
@@ -67,8 +74,8 @@ REFINER_DEFAULTS = {'refiner.gpu_ids': '0,', 'refiner.modulo': 8, 'refiner.n_ite
 # a file name); everything else is a bool / int / float as in the YAML defaults
 STRING_KEYS = {'model.path', 'model.checkpoint', 'indir', 'outdir', 'device', 'dataset.kind', 'dataset.img_suffix', 'out_ext', 'out_key',
                'precision', 'refiner.gpu_ids', 'jpeg_subsampling'}
-BOOL_KEYS = {'refine', 'profile', 'paste_back', 'device_png', 'device_jpeg'}
-INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'jpeg_quality', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
+BOOL_KEYS = {'refine', 'profile', 'paste_back', 'device_png', 'device_jpeg', 'crop_to_mask'}
+INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'jpeg_quality', 'crop_margin', 'crop_step', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
             'refiner.px_budget', 'refiner.batch_size'}
 FLOAT_KEYS = {'refiner.lr', 'dataset.scale_factor'}
 
@@ -128,6 +135,20 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
         if cfg['out_key'] != 'inpainted':
             raise SystemExit(f"paste_back=true with out_key={cfg['out_key']!r} is not served: the pasted result is made from 'inpainted' "
                              f"('predicted_image' is undefined where the mask is 0)")
+    if cfg['crop_to_mask']:
+        # the u8 step on a window around the mask, pasted into the source image (lama_crop_compose_u8_fwd / lama_crop_paste_u8_fwd): this driver's own
+        # output, the reference runs the generator on the whole image
+        if cfg.get('dataset.scale_factor') is not None:
+            raise SystemExit('crop_to_mask=true with dataset.scale_factor is not served: the window is inpainted at the source resolution')
+        if cfg.get('refine', False):
+            raise SystemExit('crop_to_mask=true with refine=true is not served: refinement works on the whole image')
+        if cfg['out_key'] != 'inpainted':
+            raise SystemExit(f"crop_to_mask=true with out_key={cfg['out_key']!r} is not served: the pasted result is made from 'inpainted' "
+                             f"(a rectangle of raw prediction inside the source image is not a result)")
+        try:
+            check_crop_options(cfg['crop_margin'], cfg['crop_step'], cfg['dataset.pad_out_to_modulo'])
+        except L.LamaError as e:
+            raise SystemExit(f'crop_to_mask=true: {e}')
     if cfg['device_png'] and cfg['device_jpeg']:
         raise SystemExit('device_jpeg=true with device_png=true: a step ends with one encoder, and out_ext names one format')
     if cfg['device_png']:
@@ -304,12 +325,14 @@ def scale_image(img: np.ndarray, factor: float, interpolation: str = 'area') -> 
     return out[None, ...] if out.ndim == 2 else np.transpose(out, (2, 0, 1))
 
 
-def load_item_u8(mask_path: str, img_path: str):
+def load_item_u8(mask_path: str, img_path: str, mask: Optional[np.ndarray] = None):
     """The same pair as it is on disk: (u8 image [H,W,3], u8 mask [H,W], (H, W)).  ``load_image``'s / 255, ``pad_img_to_modulo`` and
-    bin/predict.py:84's ``mask > 0`` happen on the device (lama_mask_compose_u8_fwd, ABI v110): the host only decodes."""
+    bin/predict.py:84's ``mask > 0`` happen on the device (lama_mask_compose_u8_fwd, ABI v110): the host only decodes.  ``mask``: the mask as
+    decoded already (the crop_to_mask pre-pass keeps what fits its budget), not decoded again."""
     from PIL import Image
     image = np.asarray(Image.open(img_path).convert('RGB'))
-    mask = np.asarray(Image.open(mask_path).convert('L'))
+    if mask is None:
+        mask = np.asarray(Image.open(mask_path).convert('L'))
     if tuple(mask.shape) != tuple(image.shape[:2]):
         raise L.LamaError(f'{mask_path}: mask is {mask.shape[1]}x{mask.shape[0]} but {img_path} is {image.shape[1]}x{image.shape[0]}')
     return image, mask, tuple(image.shape[:2])
@@ -329,6 +352,50 @@ def load_item(mask_path: str, img_path: str, pad_mod: int, scale_factor: Optiona
     if pad_mod and pad_mod > 1:
         image, mask = pad_img_to_modulo(image, pad_mod), pad_img_to_modulo(mask, pad_mod)
     return image, mask, hw
+
+
+# ---- crop_to_mask: the window of an image the generator sees (an option of this driver's own: the reference has none like it) ----------------------
+
+def check_crop_options(margin: int, step: int, pad_mod: int):
+    """``crop_margin`` >= 0 and ``crop_step`` a positive multiple of ``pad_out_to_modulo``: every window that does not span its axis is then a
+    padded size already."""
+    mod = int(pad_mod) if pad_mod and int(pad_mod) > 1 else 1
+    if int(margin) < 0:
+        raise L.LamaError(f'crop_margin={margin!r}: 0 or more pixels around the mask')
+    if int(step) < 1 or int(step) % mod:
+        raise L.LamaError(f'crop_step={step!r}: a positive multiple of dataset.pad_out_to_modulo={pad_mod!r}')
+
+
+def crop_rect(mask_u8: np.ndarray, margin: int, step: int, pad_mod: int) -> Tuple[int, int, int, int, int, int]:
+    """The window of an h x w image that ``crop_to_mask`` inpaints -> (y0, x0, ch, cw, Hp, Wp), integers only (every rank computes the same
+    window from the same file).  The box is the rows / columns where ``mask > 0`` (the raw bytes, whatever ``binarize`` says; an empty mask: the empty
+    box at the origin).  Per axis: want = extent + 2 margin; c = min(side, want rounded up to ``step``) (at least one pixel: an empty box with
+    margin 0 takes one step); the window is centred on the box and clamped into the image, o = clamp(lo - (c - extent) // 2, 0, side - c).
+    A window that spans its axis (c = side, o = 0) is padded as the whole image would be, ceil_modulo(side, pad_mod); any other is ``c``, a
+    multiple of ``step`` and so of ``pad_mod``."""
+    check_crop_options(margin, step, pad_mod)
+    if mask_u8.ndim != 2 or mask_u8.shape[0] < 1 or mask_u8.shape[1] < 1:
+        raise L.LamaError(f'crop_rect: a [h, w] mask of at least one pixel, got {tuple(mask_u8.shape)}')
+    margin, step = int(margin), int(step)
+    hole = mask_u8 > 0
+    out = []
+    for axis in (0, 1):
+        side = int(mask_u8.shape[axis])
+        hit = np.flatnonzero(hole.any(axis=1 - axis))
+        lo, extent = (int(hit[0]), int(hit[-1]) - int(hit[0]) + 1) if hit.size else (0, 0)
+        want = max(1, extent + 2 * margin)
+        c = min(side, (want + step - 1) // step * step)
+        o = min(max(lo - (c - extent) // 2, 0), side - c)
+        assert 0 <= o <= lo and lo + extent <= o + c <= side, (axis, side, lo, extent, o, c)           # inside the image, around the box
+        out.append((o, c, ceil_modulo(side, pad_mod) if c == side and pad_mod and pad_mod > 1 else c))
+    (y0, ch, Hp), (x0, cw, Wp) = out
+    return y0, x0, ch, cw, Hp, Wp
+
+
+def rect_fits(rect, h: int, w: int, Hs: int, Ws: int, Hp: int, Wp: int) -> bool:
+    """The conditions lama_crop_compose_u8_fwd / lama_crop_paste_u8_fwd put on a window (y0, x0, ch, cw) of an h x w image in an Hs x Ws slot."""
+    y0, x0, ch, cw = (int(v) for v in rect[:4])
+    return (ch >= 1 and cw >= 1 and y0 >= 0 and x0 >= 0 and y0 + ch <= h and x0 + cw <= w and ch <= Hp and cw <= Wp and 0 < h <= Hs and 0 < w <= Ws)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -365,6 +432,7 @@ def gather_to_root(dist, gathered: Optional[torch.Tensor], part: torch.Tensor, r
 PROFILE_SPANS = False                    # profile=true: HostFedStep records timing events around every step's compute
 LOOP_TIMES: Dict[str, float] = {}      # wall seconds of the main thread per phase of the round loop (python -m lama_amd.predict ... profile=true prints them)
 TUNE_MIN_ROUNDS = 1024    # buckets with fewer rounds skip the split-plan timing check: ~0.35 s for at most 5 % of the bucket's time (HostFedStep(tune=False))
+CROP_MASK_CACHE_BYTES = 512 << 20   # crop_to_mask: the decoded masks the pre-pass keeps for the loads of the round loop (the rest are decoded again)
 CAPTURE_MIN_ROUNDS = 32   # ... and with fewer than this also the graph capture: ~30 ms for ~8 % of a round's 10 ms (HostFedStep(capture=False): plain launches)
 
 
@@ -583,13 +651,33 @@ class HostFedStep:
     entropy-coded scan of every image's baseline JPEG at ``jpeg_quality`` and ``jpeg_subsampling`` ('420' / '444'; tests/jpeg_ref.py), cropped by the
     same sizes array.  The result sets are laid out as the PNG ones: ``n`` scan slots of ``jpeg_slot`` = ``jpeg_out_stride`` bytes (default: the
     slot's raw byte count Hs Ws 3), then, from byte ``jpeg_len_at`` on, the ``n`` int32 lengths.  ``result_jpeg(p, j)`` is the j-th scan;
-    a scan that did not fit its slot (a negative length: noise at quality 100) raises JpegOverflow.  ``predict.jpeg_from_scan`` adds the headers."""
+    a scan that did not fit its slot (a negative length: noise at quality 100) raises JpegOverflow.  ``predict.jpeg_from_scan`` adds the headers.
+
+    ``crop`` (crop_to_mask; not with ``scale_factor`` or out_key 'predicted_image'; no counterpart in the reference): source slots of ``src_hw``
+    pixels up and down as in the ``scale_factor`` + ``paste_back`` form, and ``put`` takes a window (y0, x0, ch, cw) per image beside them (a
+    pinned and a device ``rects`` array next to the sizes).  (Hp, Wp) is the padded size of the WINDOWS: the step is lama_crop_compose_u8_fwd, the
+    generator call of the u8 form at that shape, lama_crop_paste_u8_fwd (model.forward_u8_crop) -- the u8 step on the cropped arrays, pasted into
+    the source by slicing, byte for byte.  ``crop_sizes`` are the source sizes, so both encoders work on the pasted result unchanged."""
 
     def __init__(self, model, batch_size: int, Hp: int, Wp: int, device, *, drain: bool = True, binarize: bool = True, mode: str = 'auto',
                  u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True, scale_factor: Optional[float] = None,
                  src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False, encode_png: bool = False,
-                 encode_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420', jpeg_out_stride: Optional[int] = None):
+                 encode_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420', jpeg_out_stride: Optional[int] = None,
+                 crop: bool = False):
         self.model, self.n, self.Hp, self.Wp = model, int(batch_size), int(Hp), int(Wp)
+        # ``crop`` (crop_to_mask): the fourth input form -- the DECODED u8 originals in source slots of ``src_hw`` pixels plus a window per image;
+        # (Hp, Wp) is the padded size of the WINDOWS, and the results are source slots
+        self.crop = bool(crop)
+        if self.crop:
+            if scale_factor is not None:
+                raise L.LamaError('crop with scale_factor is not served: the window is inpainted at the source resolution')
+            if out_key != 'inpainted':
+                raise L.LamaError(f"crop with out_key {out_key!r}: the pasted result is made from 'inpainted'")
+            if not u8_input or not hasattr(model, 'forward_u8_crop'):
+                raise L.LamaError('crop is a u8 input form (model.forward_u8_crop): not with u8_input=False')
+            if src_hw is None or int(src_hw[0]) < 1 or int(src_hw[1]) < 1:
+                raise L.LamaError(f'crop: src_hw = (Hs, Ws), the source slot size, is needed (got {src_hw!r})')
+            self.Hs, self.Ws = int(src_hw[0]), int(src_hw[1])
         # ``scale_factor`` (dataset.scale_factor, evaluation/data.py:74-77): the third input form -- the step is fed with the DECODED u8 originals in
         # source slots of ``src_hw`` = (Hs, Ws) pixels, and its first launch (lama_resize_u8_fwd) does / 255, the INTER_AREA / INTER_NEAREST
         # rescale, the symmetric padding and mask > 0 on the device; (Hp, Wp) is the padded SCALED size
@@ -634,9 +722,19 @@ class HostFedStep:
         pin = dict(pin_memory=True) if self.on_gpu else {}
         # round 6: the step is fed with what is on disk -- u8 HWC image, u8 mask, (h, w) per image: 4 bytes per pixel over PCIe instead of 16, no
         # float conversion / padding on the host (forward_u8).  ``u8_input=False`` keeps the fp32 NCHW form of round 5 (A/B runs, callers with float data).
-        self.u8_input = bool(u8_input) and hasattr(model, 'forward_u8') and self.scale is None
+        self.u8_input = bool(u8_input) and hasattr(model, 'forward_u8') and self.scale is None and not self.crop
         self.h_dsizes = self.d_dsizes = None
-        if self.scale is not None:
+        self.h_rects = self.d_rects = None
+        if self.crop:
+            self.h_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, **pin) for _ in range(2)]
+            self.h_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, **pin) for _ in range(2)]
+            self.h_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, **pin) for _ in range(2)]           # (h, w) of each source image
+            self.h_rects = [torch.zeros(self.n, 4, dtype=torch.int32, **pin) for _ in range(2)]           # (y0, x0, ch, cw): its window
+            self.d_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self.d_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self.d_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, device=self.device) for _ in range(2)]
+            self.d_rects = [torch.zeros(self.n, 4, dtype=torch.int32, device=self.device) for _ in range(2)]
+        elif self.scale is not None:
             self.h_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, **pin) for _ in range(2)]
             self.h_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, **pin) for _ in range(2)]
             self.h_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, **pin) for _ in range(2)]           # (h, w) of each source image
@@ -661,7 +759,7 @@ class HostFedStep:
             self.d_img = [torch.zeros(self.n, 3, Hp, Wp, dtype=torch.float32, device=self.device) for _ in range(2)]
             self.d_mask = [torch.zeros(self.n, 1, Hp, Wp, dtype=torch.float32, device=self.device) for _ in range(2)]
             self.h_sizes = self.d_sizes = None
-        self.out_hw = (self.Hs, self.Ws) if self.paste_back else (self.Hp, self.Wp)       # paste_back: the results are source slots
+        self.out_hw = (self.Hs, self.Ws) if self.paste_back or self.crop else (self.Hp, self.Wp)       # paste_back / crop: the results are source slots
         self.encode_png = bool(encode_png)
         self.u8 = [torch.zeros(self.n, *self.out_hw, 3, dtype=torch.uint8, device=self.device) for _ in range(2)]
         if self.encode_png:
@@ -719,9 +817,25 @@ class HostFedStep:
         [n,Hs,Ws,3] / [n,Hs,Ws] (``scale_factor``) or fp32 NCHW."""
         return self.h_img[p].numpy(), self.h_mask[p].numpy()
 
-    def put(self, p: int, j: int, image: Optional[np.ndarray], mask: Optional[np.ndarray]):
+    def put(self, p: int, j: int, image: Optional[np.ndarray], mask: Optional[np.ndarray], rect=None):
         """``u8_input``: image j of host set p = a decoded u8 HWC image [h,w,3] + u8 mask [h,w] (top-left corner of the slot), or None: an empty
-        slot of a partial batch.  ``scale_factor``: the same pair, the decoded ORIGINAL, into its source slot."""
+        slot of a partial batch.  ``scale_factor``: the same pair, the decoded ORIGINAL, into its source slot.  ``crop``: the same, with ``rect`` =
+        (y0, x0, ch, cw), the window the generator sees (``crop_rect``); a window that does not fit is refused here."""
+        if self.crop:
+            sz, rc = self.h_sizes[p].numpy(), self.h_rects[p].numpy()
+            if image is None:
+                sz[j], rc[j] = (0, 0), (0, 0, 0, 0)
+                return
+            h, w = image.shape[:2]
+            if rect is None or len(rect) < 4 or not rect_fits(rect, h, w, self.Hs, self.Ws, self.Hp, self.Wp):       # (the kernels cannot report it)
+                raise L.LamaError(f'window {None if rect is None else tuple(int(v) for v in rect[:4])} of a {h}x{w} image does not fit it, the source '
+                                  f'slot {self.Hs}x{self.Ws} or the bucket {self.Hp}x{self.Wp}')
+            self.h_img[p].numpy()[j, :h, :w] = image
+            self.h_mask[p].numpy()[j, :h, :w] = mask
+            sz[j], rc[j] = (h, w), tuple(int(v) for v in rect[:4])
+            return
+        if rect is not None:
+            raise L.LamaError('put: a window is an operand of the crop form only')
         if self.scale is not None:
             sz, dz = self.h_sizes[p].numpy(), self.h_dsizes[p].numpy()
             if image is None:
@@ -806,6 +920,10 @@ class HostFedStep:
 
     def _compute_u8(self, p: int):
         lib = self.model.generator._exec.lib
+        if self.crop:                                                                              # the same step on each image's window, pasted into the source slots
+            with torch.no_grad():
+                self.model.forward_u8_crop(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.d_rects[p], self.u8[p], self.Hp, self.Wp, binarize=self.binarize)
+            return
         if self.u8_input:                                                                          # bin/predict.py:82-92 in two elementwise launches + the generator
             with torch.no_grad():
                 self.model.forward_u8(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.u8[p], binarize=self.binarize, out_key=self.out_key)
@@ -840,6 +958,8 @@ class HostFedStep:
             self.d_sizes[q].copy_(self.h_sizes[q], non_blocking=non_blocking)
         if self.d_dsizes is not None:
             self.d_dsizes[q].copy_(self.h_dsizes[q], non_blocking=non_blocking)
+        if self.d_rects is not None:
+            self.d_rects[q].copy_(self.h_rects[q], non_blocking=non_blocking)
 
     def _body(self, p: int):
         q = 1 - p
@@ -965,7 +1085,8 @@ class HostFedStep:
 def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[str, str]], indir: str, outdir: str, *,
             pad_mod: int = 8, batch_size: int = 8, out_ext: str = '.png', device='cuda', rank: int = 0, world: int = 1,
             dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None, paste_back: bool = False,
-            device_png: bool = False, device_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420') -> int:
+            device_png: bool = False, device_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420',
+            crop_to_mask: bool = False, crop_margin: int = 128, crop_step: int = 128) -> int:
     """Run every (mask, image) pair through ``model`` and write the results (rank 0).  Returns the number of images written.
     ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled before the padding -- on the device, by
     the first launch of the step, which is fed with the decoded u8 originals (lama_resize_u8_fwd) -- and the results have the rescaled size.
@@ -978,6 +1099,11 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
     the device (lama_jpeg_scan_u8_fwd) at ``jpeg_quality`` / ``jpeg_subsampling``; the copies carry the flat set of scan slots (as large as the u8 set at the default slot size: what is saved is the host's encode) and the host adds the headers
     (jpeg_from_scan).  An image whose scan overflowed its slot is computed once more at the end of its bucket and encoded on the host.  With the
     option off a ``.jpg`` is PIL's, at PIL's defaults (quality 75).
+    ``crop_to_mask`` (off by default; not with ``scale_factor`` or out_key 'predicted_image'; the reference has no such output): the generator runs
+    on a window around each mask's bounding box (``crop_rect``: the box + ``crop_margin`` a side, rounded up to ``crop_step``) at the source
+    resolution, and the results are the source images with the window's inpainted pixels pasted in on the device (lama_crop_paste_u8_fwd) -- the u8
+    step on the cropped arrays, pasted by slicing.  The windows need the masks' pixels, so a pre-pass decodes every mask on the I/O pool before the
+    buckets -- keyed by the windows' padded size -- are formed; every rank runs the whole pre-pass and so arrives at the same buckets.
 
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
@@ -989,14 +1115,15 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
                 return _predict_once(model, items, indir, outdir, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext, device=device,
                                      rank=rank, world=world, dist=dist, io_threads=io_threads, out_key=out_key, scale_factor=scale_factor,
                                      paste_back=paste_back, device_png=device_png,
-                                     device_jpeg=(int(jpeg_quality), ljpeg.subsampling_code(jpeg_subsampling)) if device_jpeg else None)
+                                     device_jpeg=(int(jpeg_quality), ljpeg.subsampling_code(jpeg_subsampling)) if device_jpeg else None,
+                                     crop=(int(crop_margin), int(crop_step)) if crop_to_mask else None)
             except _RangeRestart:
                 continue                     # the generator switched to the 3-term bf16 split (every rank alike): all images again
         raise L.LamaError('range restart did not converge')
 
 
 def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, device, rank, world, dist, io_threads, out_key='inpainted', scale_factor=None,
-                  paste_back=False, device_png=False, device_jpeg=None) -> int:
+                  paste_back=False, device_png=False, device_jpeg=None, crop=None) -> int:
     from PIL import Image
 
     def header_size(item):                   # padded shape from the IMAGE's PNG header only: every rank builds the same plan
@@ -1004,8 +1131,27 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
             w, h = im.size
         return (h, w)
 
+    masks: Dict[int, np.ndarray] = {}        # crop_to_mask: item -> its mask as the pre-pass decoded it, up to CROP_MASK_CACHE_BYTES in all
+    room = [CROP_MASK_CACHE_BYTES]
+    room_lock = threading.Lock()
+
+    def mask_rect(i):                        # crop_to_mask: the window from the MASK's pixels (integers only: every rank computes the same one)
+        mask = np.asarray(Image.open(items[i][0]).convert('L'))
+        with room_lock:
+            keep = room[0] >= mask.nbytes
+            if keep:
+                room[0] -= mask.nbytes
+        if keep:
+            masks[i] = mask
+        return tuple(mask.shape), crop_rect(mask, crop[0], crop[1], pad_mod)
+
     if paste_back and scale_factor is None:
         raise L.LamaError('paste_back needs scale_factor: without one the result has the source size already')
+    if crop is not None:
+        if scale_factor is not None or out_key != 'inpainted':
+            raise L.LamaError("crop_to_mask is not served with scale_factor or out_key 'predicted_image': the window is inpainted at the source "
+                              "resolution and pasted from 'inpainted'")
+        check_crop_options(crop[0], crop[1], pad_mod)
     if device_png and not out_ext.lower().endswith('.png'):
         raise L.LamaError(f'device_png writes PNG files only, not {out_ext!r}')
     if device_jpeg and (device_png or not out_ext.lower().endswith(('.jpg', '.jpeg'))):
@@ -1023,23 +1169,38 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
             if h <= 0 or w <= 0:
                 raise L.LamaError(f'scale_factor {scale_factor}: a {sw}x{sh} image scales to nothing')
         shapes = [(ceil_modulo(h, pad_mod), ceil_modulo(w, pad_mod)) if pad_mod and pad_mod > 1 else (h, w) for h, w in sizes]
+        rects = None
+        if crop is not None:
+            # the pre-pass: the windows need the masks' pixels, so every mask is decoded once here (on the I/O pool; every rank decodes them all and
+            # arrives at the same buckets without a collective) and the buckets are keyed by the windows' padded size.  The decoded masks are kept
+            # for the loads of the round loop as far as CROP_MASK_CACHE_BYTES goes; the others are decoded a second time there
+            t_ = time.perf_counter()
+            found = list(pool.map(mask_rect, range(len(items))))
+            for item, hw, (mhw, _) in zip(items, src_sizes, found):
+                if tuple(mhw) != tuple(hw):
+                    raise L.LamaError(f'{item[0]}: mask is {mhw[1]}x{mhw[0]} but {item[1]} is {hw[1]}x{hw[0]}')
+            rects = [r[:4] for _, r in found]
+            shapes = [r[4:] for _, r in found]
+            LOOP_TIMES['crop_prepass'] = LOOP_TIMES.get('crop_prepass', 0.0) + time.perf_counter() - t_
         rounds = plan_rounds(shapes, batch_size, world)
         return _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext,
                                device=device, rank=rank, world=world, dist=dist, out_key=out_key, fast=fast, scale_factor=scale_factor,
-                               src_sizes=src_sizes, paste_back=paste_back, device_png=device_png, device_jpeg=device_jpeg)
+                               src_sizes=src_sizes, paste_back=paste_back, device_png=device_png, device_jpeg=device_jpeg, rects=rects, masks=masks)
     finally:
         fast.shutdown()
         pool.shutdown()                      # on every exit path (a raise out of a bucket included): no worker thread outlives the call
 
 
 def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pad_mod, batch_size, out_ext, device, rank, world, dist, out_key='inpainted', fast=None,
-                    scale_factor=None, src_sizes=None, paste_back=False, device_png=False, device_jpeg=None) -> int:
+                    scale_factor=None, src_sizes=None, paste_back=False, device_png=False, device_jpeg=None, rects=None, masks=None) -> int:
     """The rounds of one attempt.  Per bucket (padded shape) a ``HostFedStep``: round k computes from device input set k & 1 while the SAME graph
     launch uploads round k + 1's decoded images into the other set and (one rank) downloads round k - 1's u8 results; the host fills the
     pinned set of round k + 1 and queues round k - 2's PNG writes while round k runs.  Several ranks: the results go through the one
     collective -- ``gather_to_root`` of the u8 batch, on a side stream behind the step -- and rank 0 downloads the gathered rounds.
     ``paste_back``: the buckets stay keyed by the padded scaled size, but the u8 results (and the gathered rounds) are the bucket's source slots
     and each PNG is the h x w crop of its SOURCE size.
+    ``rects`` (crop_to_mask: the window of every item): the buckets are keyed by the windows' padded size, the steps are ``HostFedStep(crop=True)`` over
+    source slots that hold the bucket's largest source image, and results, gathered rounds and crops are as with ``paste_back``.
     ``device_png``: a result set is the step's flat buffer (``batch_size`` stream slots, then their int32 lengths) per rank instead of the u8 images:
     the snapshot job copies the stream's bytes out of the pinned set and releases the latch, the pool job wraps and writes.
     ``device_jpeg`` = (quality, subsampling): the same with scans; an image whose scan did not fit its slot (JpegOverflow) is put aside, and at the
@@ -1060,13 +1221,13 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
     def submit_loads(r):
         if r < len(rounds) and r not in loads:
             # decode only: / 255, dataset.scale_factor's rescale, the padding and mask > 0 run on the device
-            loads[r] = [pool.submit(load_item_u8, *items[i]) for i in rounds[r]['batches'][rank]]
+            loads[r] = [pool.submit(load_item_u8, *items[i], masks.pop(i, None) if masks else None) for i in rounds[r]['batches'][rank]]
 
     snapped = [_Latch(), _Latch()]           # per pinned result set: the workers that still copy their image out of it
     png_slot = png_set = png_len_at = 0      # device_png / device_jpeg: bytes per stream slot / per rank's result buffer / in front of its lengths (current bucket)
     flat_sets = bool(device_png or device_jpeg)
     overflowed: List[Tuple[int, str]] = []   # device_jpeg: (item, path) of the scans that did not fit their slot in the current bucket
-    crops = src_sizes if paste_back else sizes
+    crops = src_sizes if paste_back or rects is not None else sizes
 
     def write_round(rd, host, pset):
         """Rank 0: queue the PNG writes of one round from its u8 results on the host (``host`` = [ranks * batch_size, Hp, Wp, 3] = pinned result
@@ -1115,11 +1276,11 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
         K = r1 - r0
         t_ = time.perf_counter()
         src_hw = None
-        if scale_factor is not None:             # the bucket's source slots hold its largest source image (every rank: the same plan, the same slots)
+        if scale_factor is not None or rects is not None:             # the bucket's source slots hold its largest source image (every rank: the same plan, the same slots)
             members = [src_sizes[i] for rd in rounds[r0:r1] for b in rd['batches'] for i in b]
             src_hw = (max(h for h, _ in members), max(w for _, w in members))
         hs = HostFedStep(model, batch_size, Hp, Wp, device, drain=(world == 1), tune=(K >= TUNE_MIN_ROUNDS), capture=(K >= CAPTURE_MIN_ROUNDS), out_key=out_key,
-                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png,
+                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png, crop=rects is not None,
                          **(dict(encode_jpeg=True, jpeg_quality=device_jpeg[0], jpeg_subsampling=device_jpeg[1], jpeg_out_stride=JPEG_OUT_STRIDE) if device_jpeg else {}))
         if device_png:
             png_slot, png_set, png_len_at = hs.png_slot, hs.png_bytes, batch_size * hs.png_slot
@@ -1139,12 +1300,13 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
         def fill(pp, r):
             t_ = time.perf_counter()
             loaded = [f.result() for f in loads.pop(r)]
+            mine = rounds[r]['batches'][rank]
             LOOP_TIMES['wait_decode'] = LOOP_TIMES.get('wait_decode', 0.0) + time.perf_counter() - t_
             t_ = time.perf_counter()
 
             def put(j):                                                               # partial (or, for a rank without a batch, empty) round: empty slots
                 if j < len(loaded):
-                    hs.put(pp, j, loaded[j][0], loaded[j][1])
+                    hs.put(pp, j, loaded[j][0], loaded[j][1], *(() if rects is None else (rects[mine[j]],)))
                 else:
                     hs.put(pp, j, None, None)
             list(fast.map(put, range(batch_size)))                                    # the copies into the pinned set, side by side (distinct slots)
@@ -1222,11 +1384,12 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
 
         if overflowed:                       # device_jpeg, rank 0: the images whose scan did not fit -- a plain u8 step, a download of their own, libjpeg
             fb = HostFedStep(model, batch_size, Hp, Wp, device, drain=True, tune=False, capture=False, out_key=out_key, scale_factor=scale_factor,
-                             src_hw=src_hw, paste_back=paste_back)
+                             src_hw=src_hw, paste_back=paste_back, crop=rects is not None)
             for c0 in range(0, len(overflowed), batch_size):
                 part = overflowed[c0:c0 + batch_size]
                 for j in range(batch_size):
-                    fb.put(0, j, *(load_item_u8(*items[part[j][0]])[:2] if j < len(part) else (None, None)))
+                    fb.put(0, j, *(load_item_u8(*items[part[j][0]])[:2] if j < len(part) else (None, None)),
+                           *((rects[part[j][0]],) if rects is not None and j < len(part) else ()))
                 fb.prime(0)
                 fb.launch(0)
                 fb.wait(0)
@@ -1391,11 +1554,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     n = predict(model, items, indir, cfg['outdir'], pad_mod=int(cfg['dataset.pad_out_to_modulo']), batch_size=int(cfg['batch_size']),
                 out_ext=cfg['out_ext'], device=device, rank=rank, world=world, dist=dist, io_threads=int(cfg['io_threads']), out_key=cfg['out_key'],
                 scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']), device_png=bool(cfg['device_png']),
-                device_jpeg=bool(cfg['device_jpeg']), jpeg_quality=cfg['jpeg_quality'], jpeg_subsampling=cfg['jpeg_subsampling'])
+                device_jpeg=bool(cfg['device_jpeg']), jpeg_quality=cfg['jpeg_quality'], jpeg_subsampling=cfg['jpeg_subsampling'],
+                crop_to_mask=bool(cfg['crop_to_mask']), crop_margin=int(cfg['crop_margin']), crop_step=int(cfg['crop_step']))
     dt = time.perf_counter() - t0
     if rank == 0:
         # (the loop's own wall time: plan build + graph capture of every shape bucket, PNG decode, upload, compute, download, PNG encode + write)
         print(f'wrote {n} images to {cfg["outdir"]} in {dt:.3f} s ({n / max(dt, 1e-9):.1f} images/s, {world} rank(s), io_threads={int(cfg["io_threads"])})')
+        if cfg['crop_to_mask']:
+            print(f'crop_to_mask pre-pass: {LOOP_TIMES.get("crop_prepass", 0.0):.3f} s of the {dt:.3f} s (every mask decoded once more, on the I/O pool, for its window)')
         if cfg.get('profile', False):
             print('main-thread seconds per phase of the round loop: ' + ', '.join(f'{k} {v:.3f}' for k, v in sorted(LOOP_TIMES.items())))
     if world > 1:

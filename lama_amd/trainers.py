@@ -134,6 +134,49 @@ class DefaultInpaintingTrainingModule(nn.Module):
             ex.lib.blend_quantize_u8(image_hwc, mask, sizes, L.view(pred), out_u8, B, binarize, st)
         return out_u8
 
+    def forward_u8_crop(self, image_hwc: torch.Tensor, mask: torch.Tensor, sizes: torch.Tensor, rects: torch.Tensor, out_u8: torch.Tensor,
+                        Hp: int, Wp: int, binarize: bool = True) -> torch.Tensor:
+        """``crop_to_mask`` (no counterpart in the reference): ``forward_u8`` on a WINDOW of every image.  ``image_hwc`` u8 [B,Hs,Ws,3] / ``mask`` u8
+        [B,Hs,Ws] are source slots (each image's h x w pixels in the top-left corner), ``sizes`` int32 [B,2] = (h, w) and ``rects`` int32 [B,4] =
+        (y0, x0, ch, cw) are on the device.  The first launch composes the generator's [B,4,Hp,Wp] input from the windows (lama_crop_compose_u8_fwd),
+        the generator call is the one ``forward_u8`` makes for that shape (plans, graph replay, sparse tail), and the last launch writes the source
+        image with the window's blended, quantised bytes pasted in (lama_crop_paste_u8_fwd) into ``out_u8`` [B,Hs,Ws,3] (returned): what
+        ``forward_u8`` gives for the cropped arrays, pasted by slicing, byte for byte."""
+        ex = self.generator._exec
+        if not ex.injected and not image_hwc.is_cuda:
+            raise L.LamaError('lama_amd runs on an MI355X only: input tensor is on ' + str(image_hwc.device) + ' (there is no CPU fallback)')
+        if image_hwc.dtype != torch.uint8 or mask.dtype != torch.uint8 or out_u8.dtype != torch.uint8:
+            raise L.LamaError('forward_u8_crop: uint8 image / mask / output tensors')
+        B, Hs, Ws, _ = image_hwc.shape
+        if tuple(mask.shape) != (B, Hs, Ws) or tuple(out_u8.shape) != (B, Hs, Ws, 3) or not (image_hwc.is_contiguous() and mask.is_contiguous() and out_u8.is_contiguous()):
+            raise L.LamaError(f'forward_u8_crop: image {tuple(image_hwc.shape)} / mask {tuple(mask.shape)} / out {tuple(out_u8.shape)}: contiguous [B,Hs,Ws,3], [B,Hs,Ws], [B,Hs,Ws,3]')
+        if int(Hp) < 1 or int(Wp) < 1:
+            raise L.LamaError(f'forward_u8_crop: a padded window of at least one pixel, got {Hp}x{Wp}')
+        if not self.concat_mask:
+            raise NotImplementedError('concat_mask=False is not used by big-lama')
+        st = ex.stream(image_hwc)
+        gen = self.generator
+        keep_sparse = getattr(gen, 'sparse_tail', None)      # the paste reads pred only under the mask, as the blend does: the sparse-tail plans
+        if keep_sparse is not None:
+            gen.sparse_tail = True
+        try:
+            shape = (B, 4, int(Hp), int(Wp))
+            masked = gen.input_buffer(shape, image_hwc.device) if hasattr(gen, 'input_buffer') else torch.empty(*shape, device=image_hwc.device)
+            ex.lib.crop_compose_u8(image_hwc, mask, sizes, rects, L.view(masked), B, binarize, st)
+            if hasattr(gen, 'clone_output'):
+                keep, gen.clone_output = gen.clone_output, False                   # the paste below consumes the plan's own output buffer at once
+                try:
+                    pred = gen(masked)
+                finally:
+                    gen.clone_output = keep
+            else:
+                pred = gen(masked)
+        finally:
+            if keep_sparse is not None:
+                gen.sparse_tail = keep_sparse
+        ex.lib.crop_paste_u8(image_hwc, mask, sizes, rects, L.view(pred), out_u8, B, binarize, st)
+        return out_u8
+
 
 def get_training_model_class(kind):
     if kind == 'default':
