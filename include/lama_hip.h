@@ -103,7 +103,13 @@ typedef struct lama_conv2d_args {
     /* Range watch of LAMA_PREC_F16X3 (ignored by the other precisions; NULL = off).  The fp16 split represents |x| <= 65504
      * only: a kernel that meets a larger activation (or a NaN) while splitting x / x2 ORs 1 into *range_flag (device
      * uint32, zeroed by the caller); its output is then garbage and the caller re-runs with LAMA_PREC_BF16X3 (fp32 exponent
-     * range, 16 mantissa bits) or LAMA_PREC_F32.  The weights are range-checked by the host at pack time instead. */
+     * range, 16 mantissa bits) or LAMA_PREC_F32.  The weights are range-checked by the host at pack time instead.
+     * Precision of an UNFLAGGED result: per output within c (|x| (*) |w scale|), c = 2^-20 (F16X3: 22 bits of each operand, lo * lo dropped) /
+     * 2^-14 (BF16X3), plus fp32 accumulation -- with one floor of the fp16 format: a packed (scale-folded) weight below 2^-3 has an fp16-SUBNORMAL
+     * lo part (grid 2^-24), i.e. an absolute error of up to 2^-25 however small it is, so a tap adds up to 2^-25 |x|.  Trained, folded weights are
+     * mostly below 2^-3, so this floor is the working precision of F16X3 weights: K taps of O(1) activations give at most K 2^-25 (1.4e-4 at
+     * K = 4608, 2e-6 with random signs), inside the 2e-4 every accuracy test holds; it grows linearly with |x| (2e-3 per tap at 65504) and stays a
+     * relative 2^-25 of the activation, below fp32's own rounding of it.  Asserted: tests/range_watch_util.py (bar_of). */
     uint32_t* range_flag;
     /* Optional fused second stage (NULL / ptr NULL = off): SpectralTransform.conv1 of the NEXT layer, ffc.py:128-133,145, i.e.
      *     fuse1_y = ReLU( W1 y + fuse1_bias ),  W1 [192, 384] 1x1,
@@ -174,7 +180,14 @@ int lama_conv2d_fwd(void* stream, const lama_conv2d_args* args);
  *     (|V| <= 2 max|r|) and is raised at 2 max|r| >= 65504, i.e. up to 2x EARLY against a real overflow of a transformed operand, and it
  *     is BLIND TO NaN inputs (fmaxf drops them).  Inside the generator the global-branch launch (lama_conv2d_fwd) reads the same state
  *     buffer in the same layer and raises the flag for NaN / |x| > 65504; a stand-alone caller that needs NaN detection must run its own
- *     check (or lama_conv2d_fwd) on x. */
+ *     check (or lama_conv2d_fwd) on x.
+ *   Precision: the split is applied to the TRANSFORMED operands U = G g G^T scale and V = B^T d B, so the rounding error of a result is relative
+ *     to |A^T| (sum_c |U| |V|) |A|, not to |x| (*) |w scale| as in lama_conv2d_fwd: one large element reaches up to nine entries of V and meets all
+ *     nine taps through U, so an output whose own tap is small carries its neighbours' rounding.  With one or a few large elements among O(1)
+ *     data single outputs pass c (|x| (*) |w scale|): F16X3, unflagged, two elements of +-1.6e4 in a tile: up to 1.23x; BF16X3 (16 bits, no watch), one
+ *     element of 3e4 / 7e4: up to 2x / 21x -- and stay below 0.25x / 0.1x of c |A^T| (sum |U| |V|) |A|, the bound that holds.  Safe inside the generator:
+ *     the error stays a relative 2^-20 / 2^-14 of the LARGE activation of the tile, and the layer's outputs feed a BatchNorm-folded
+ *     ReLU of the same scale.  Asserted: tests/range_watch_util.py (check_winograd). */
 int64_t lama_winograd_packed_weight_bytes(int32_t cout, int32_t cin, int32_t precision);
 int32_t lama_winograd_supported(int32_t cout, int32_t cin, int32_t H, int32_t W, int32_t precision);
 int32_t lama_winograd_preferred(int32_t batch, int32_t cout, int32_t cin, int32_t H, int32_t W, int32_t precision);
