@@ -590,18 +590,27 @@ class LamaLib:
         self.check(self._l.lama_blend_quantize_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), None if sizes is None else sizes.data_ptr(),
                                                       C.byref(pred), dst.data_ptr(), batch, int(bool(binarize))), 'lama_blend_quantize_u8_fwd')
 
+    @staticmethod
+    def _u8_slot_operands(what: str, image_hwc: torch.Tensor, mask: torch.Tensor, batch: int, int32_arrays, out_hwc=None):
+        """The operand checks of the entries that read a batch of u8 source slots: image slots [B,Hs,Ws,3] / mask slots [B,Hs,Ws], the
+        ``int32_arrays`` (name, tensor, values per image) and, where the entry writes slots, ``out_hwc`` like the image slots."""
+        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
+            raise LamaError(f'{what}: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
+        if out_hwc is not None and tuple(out_hwc.shape) != tuple(image_hwc.shape):
+            raise LamaError(f'{what}: out slots {tuple(out_hwc.shape)} != image slots {tuple(image_hwc.shape)}')
+        u8 = [image_hwc, mask] + ([] if out_hwc is None else [out_hwc])
+        for t, dt in [(t, torch.uint8) for t in u8] + [(t, torch.int32) for _, t, _ in int32_arrays]:
+            if t.dtype != dt or not t.is_contiguous():
+                raise LamaError(f'{what}: a contiguous {dt} tensor is needed, got {t.dtype}')
+        if any(t.numel() < n * batch for _, t, n in int32_arrays):
+            raise LamaError(f'{what}: ' + ', '.join(f'{name} is [B,{n}] int32' for name, _, n in int32_arrays))
+
     def resize_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, dst_sizes: torch.Tensor, factor: float,
                   out_image: Tensor4, out_mask: Tensor4, batch: int, binarize: bool = True, stream: int = 0):
         """lama_resize_u8_fwd: dataset.scale_factor on the device.  u8 HWC source slots [B,Hs,Ws,3] + u8 mask slots [B,Hs,Ws], int32 (h, w) per
         image of the source and of the scaled result [B,2] -> the loader's fp32 image [B,3,Hp,Wp] / mask [B,1,Hp,Wp] (/ 255, INTER_AREA /
         INTER_NEAREST, symmetric padding, mask > 0), bit-identical to ``predict.load_item``."""
-        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
-            raise LamaError(f'resize_u8: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
-        for t, dt in ((image_hwc, torch.uint8), (mask, torch.uint8), (src_sizes, torch.int32), (dst_sizes, torch.int32)):
-            if t.dtype != dt or not t.is_contiguous():
-                raise LamaError(f'resize_u8: a contiguous {dt} tensor is needed, got {t.dtype}')
-        if src_sizes.numel() < 2 * batch or dst_sizes.numel() < 2 * batch:
-            raise LamaError('resize_u8: src_sizes / dst_sizes are [B,2] int32')
+        self._u8_slot_operands('resize_u8', image_hwc, mask, batch, [('src_sizes', src_sizes, 2), ('dst_sizes', dst_sizes, 2)])
         self.check(self._l.lama_resize_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
                                               int(image_hwc.shape[1]), int(image_hwc.shape[2]), float(factor), C.byref(out_image), C.byref(out_mask),
                                               batch, int(bool(binarize))), 'lama_resize_u8_fwd')
@@ -611,33 +620,16 @@ class LamaLib:
         """lama_paste_back_u8_fwd: the fp32 result ``lowres`` [B,3,Hp,Wp] of a ``scale_factor`` step (valid in [:dh, :dw] per image) resampled
         bilinearly to each image's source grid and pasted into the u8 source slots [B,Hs,Ws,3] wherever the u8 mask [B,Hs,Ws] is not 0 ->
         ``out_hwc`` [B,Hs,Ws,3] u8 (another buffer than ``image_hwc``).  Source pixels pass through byte for byte where the mask is 0."""
-        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
-            raise LamaError(f'paste_back_u8: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
-        if tuple(out_hwc.shape) != tuple(image_hwc.shape):
-            raise LamaError(f'paste_back_u8: out slots {tuple(out_hwc.shape)} != image slots {tuple(image_hwc.shape)}')
-        for t, dt in ((image_hwc, torch.uint8), (mask, torch.uint8), (out_hwc, torch.uint8), (src_sizes, torch.int32), (dst_sizes, torch.int32)):
-            if t.dtype != dt or not t.is_contiguous():
-                raise LamaError(f'paste_back_u8: a contiguous {dt} tensor is needed, got {t.dtype}')
-        if src_sizes.numel() < 2 * batch or dst_sizes.numel() < 2 * batch:
-            raise LamaError('paste_back_u8: src_sizes / dst_sizes are [B,2] int32')
+        self._u8_slot_operands('paste_back_u8', image_hwc, mask, batch, [('src_sizes', src_sizes, 2), ('dst_sizes', dst_sizes, 2)], out_hwc)
         self.check(self._l.lama_paste_back_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), dst_sizes.data_ptr(),
                                                   int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(lowres), out_hwc.data_ptr(), batch,
                                                   int(bool(binarize))), 'lama_paste_back_u8_fwd')
-
-    def _crop_operands(self, what: str, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, batch: int):
-        if image_hwc.dim() != 4 or image_hwc.shape[3] != 3 or tuple(mask.shape) != tuple(image_hwc.shape[:3]) or image_hwc.shape[0] < batch:
-            raise LamaError(f'{what}: image slots {tuple(image_hwc.shape)} / mask slots {tuple(mask.shape)}: [B,Hs,Ws,3] / [B,Hs,Ws] u8')
-        for t, dt in ((image_hwc, torch.uint8), (mask, torch.uint8), (src_sizes, torch.int32), (rects, torch.int32)):
-            if t.dtype != dt or not t.is_contiguous():
-                raise LamaError(f'{what}: a contiguous {dt} tensor is needed, got {t.dtype}')
-        if src_sizes.numel() < 2 * batch or rects.numel() < 4 * batch:
-            raise LamaError(f'{what}: src_sizes is [B,2] int32, rects [B,4] int32')
 
     def crop_compose_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, out: Tensor4, batch: int,
                         binarize: bool = True, stream: int = 0):
         """lama_crop_compose_u8_fwd: the generator's input [B,4,Hp,Wp] fp32 from the window ``rects`` [B,4] = (y0, x0, ch, cw) of each u8 source slot
         [B,Hs,Ws,3] / mask slot [B,Hs,Ws] -- what ``mask_compose_u8`` writes for the cropped arrays with sizes (ch, cw), bit for bit."""
-        self._crop_operands('crop_compose_u8', image_hwc, mask, src_sizes, rects, batch)
+        self._u8_slot_operands('crop_compose_u8', image_hwc, mask, batch, [('src_sizes', src_sizes, 2), ('rects', rects, 4)])
         self.check(self._l.lama_crop_compose_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
                                                     int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(out), batch, int(bool(binarize))),
                    'lama_crop_compose_u8_fwd')
@@ -646,9 +638,7 @@ class LamaLib:
                       out_hwc: torch.Tensor, batch: int, binarize: bool = True, stream: int = 0):
         """lama_crop_paste_u8_fwd: ``out_hwc`` [B,Hs,Ws,3] u8 (another buffer than ``image_hwc``) = the source slots with, inside each window, the
         bytes ``blend_quantize_u8`` gives for the cropped arrays and the generator's output ``pred`` [B,3,Hp,Wp] of the window."""
-        self._crop_operands('crop_paste_u8', image_hwc, mask, src_sizes, rects, batch)
-        if tuple(out_hwc.shape) != tuple(image_hwc.shape) or out_hwc.dtype != torch.uint8 or not out_hwc.is_contiguous():
-            raise LamaError(f'crop_paste_u8: out slots {tuple(out_hwc.shape)} {out_hwc.dtype}: contiguous u8 slots like the image slots {tuple(image_hwc.shape)}')
+        self._u8_slot_operands('crop_paste_u8', image_hwc, mask, batch, [('src_sizes', src_sizes, 2), ('rects', rects, 4)], out_hwc)
         self.check(self._l.lama_crop_paste_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
                                                   int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(pred), out_hwc.data_ptr(), batch,
                                                   int(bool(binarize))), 'lama_crop_paste_u8_fwd')

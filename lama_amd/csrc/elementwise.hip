@@ -286,8 +286,31 @@ struct EvalIngestParams {
     int32_t sizes[LAMA_EI_MAX_BATCH][2];
 };
 typedef uint32_t __attribute__((may_alias)) ei_u32;
-// pixel j (0..3), channel c of 12 HWC bytes held in three little-endian dwords
-__device__ __forceinline__ float ei_byte(const uint32_t (&d)[3], int k) { return (float)((d[k >> 2] >> (8 * (k & 3))) & 255u) / 255.0f; }
+// Four HWC pixels are 12 bytes held in three little-endian dwords: byte k = 3 * j + c is channel c of pixel j (0..3).
+__device__ __forceinline__ uint32_t u8_get(const uint32_t (&d)[3], int k) { return (d[k >> 2] >> (8 * (k & 3))) & 255u; }
+__device__ __forceinline__ void u8_put(uint32_t (&d)[3], int k, uint32_t v) { d[k >> 2] |= v << (8 * (k & 3)); }   // (onto a zero byte)
+__device__ __forceinline__ float ei_byte(const uint32_t (&d)[3], int k) { return (float)u8_get(d, k) / 255.0f; }
+// The four pixels from column x0 of the slot row that starts at pixel `row`, and their mask bytes in m4.  vec: one dword of mask and three of RGB
+// at row + x0.  Otherwise byte by byte, pixel j from row + col(x) with x = x0 + j clamped to W - 1 (a column past the edge re-reads the last
+// one; it is never stored).  Every load is unconditional.
+template <class Col> __device__ __forceinline__ void u8_load4(const uint8_t* img, const uint8_t* msk, long long row, int x0, int W, bool vec, Col col,
+                                                              uint32_t& m4, uint32_t (&d)[3]) {
+    if (vec) {
+        const long long px = row + x0;
+        m4 = *reinterpret_cast<const ei_u32*>(msk + px);
+        const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
+        d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
+        return;
+    }
+    m4 = d[0] = d[1] = d[2] = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long long px = row + col(x0 + j < W ? x0 + j : W - 1);
+        m4 |= (uint32_t)msk[px] << (8 * j);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) u8_put(d, 3 * j + c, img[px * 3 + c]);
+    }
+}
 
 __device__ __forceinline__ void ei_load4(const uint8_t* src, long long row, int x0, int w, int Wp, bool vec, float (&v)[3][4]) {
     if (vec && x0 + 4 <= w) {
@@ -312,9 +335,10 @@ __device__ __forceinline__ void ei_load4(const uint8_t* src, long long row, int 
         }
     }
 }
-__device__ __forceinline__ void ei_store4(float* o, long long hw, int x0, int Wp, bool vec, const float (&v)[3][4]) {
+// four pixels of NP planes: one float4 per plane, or the columns below Wp one by one
+template <int NP> __device__ __forceinline__ void ei_store4(float* o, long long hw, int x0, int Wp, bool vec, const float (&v)[NP][4]) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < NP; ++c) {
         if (vec) {
             *reinterpret_cast<float4*>(o + c * hw) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
         } else {
@@ -577,33 +601,120 @@ __global__ __launch_bounds__(LAMA_NTHREADS) void resize_u8_kernel(ResizeParams p
     }
 }
 
+// ---- the item walk of the kernels that rewrite a batch of u8 source slots (paste_back_u8_kernel, crop_paste_u8_kernel) --
+// Streaming kernels: 7 bytes per source pixel (1 mask + 3 in + 3 out).  One work item = 4 consecutive pixels of a slot row: one dword of mask,
+// three dwords of RGB in, three out (VEC: dword accesses, where Ws % 4 == 0 and the pointers allow; byte accesses otherwise).  A 256-thread
+// workgroup takes U8_UNROLL * 256 items of ONE image, so what the policy loads per image is uniform (scalar loads, its divisions once per
+// workgroup) -- ROW: 256 consecutive items of U8_UNROLL consecutive rows (slots of U8_ROW_MIN_ITEMS items per row or more: the row and what
+// hangs on it are uniform too); otherwise consecutive items of the slot, a lane divides once per item by the items per row.  A lane has the
+// streaming loads of all its items in flight before the policy's own reads, and every load before its first store; the loads are unconditional
+// (a lane past the end re-reads the last item and stores nothing).  No LDS, no atomics.
+// A kernel is this walk and a policy:
+//   Policy(p, b)        the state of image b, loaded once per workgroup: ok (false: the slot becomes zeros), h, w (zeros outside h x w) and its own
+//   row(y)              what one row of the image shares
+//   pixel(r, x, mu, sb) the three bytes of pixel (y, x) in place of its source bytes sb, given its mask byte mu != 0: a pixel whose mask byte is 0
+//                       keeps its source bytes without a call, so nothing but the streams is read for it
+// Policies and their helpers do float arithmetic with contraction OFF (every operation rounded on its own); the walk itself does none.
+#define U8_THREADS 256
+#define U8_UNROLL 4
+#define U8_ROW_MIN_ITEMS 192
+struct U8WalkParams {
+    const uint8_t* img;          // [B][Hs][Ws][3], each image's h x w pixels in the top-left corner of its slot
+    const uint8_t* mask;         // [B][Hs][Ws]
+    const int32_t* src_sizes;    // [B][2] = (h, w); h = 0: an empty slot
+    uint8_t* out_u8;             // [B][Hs][Ws][3]: the slots the walk writes (crop_compose_u8_kernel: none)
+    int Hs, Ws, binarize;        // (the ints follow the pointers, a kernel's own ints come first in its struct: the arguments load in wide runs)
+    int qpr, chunks, ygroups;    // items per row; workgroups per row (ROW) / per image; groups of U8_UNROLL rows per slot (ROW)
+};
+// item k of a lane where a workgroup takes consecutive items of one image: (y, q) of the item, of the last one for a lane past the end (false)
+__device__ __forceinline__ bool u8_item(int chunk, int k, int tid, int nitems, int qpr, int& y, int& q) {
+    const int v = (chunk * U8_UNROLL + k) * U8_THREADS + tid;
+    const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
+    y = (int)(vc / (unsigned)qpr); q = (int)(vc - (unsigned)y * (unsigned)qpr);
+    return v < nitems;
+}
+template <bool VEC, bool ROW, class Policy> __device__ __forceinline__ void u8_slot_walk(const typename Policy::Params& p) {
+    int blk = blockIdx.x;
+    const int chunk = blk % p.chunks; blk /= p.chunks;
+    const int yg = ROW ? blk % p.ygroups : 0, b = ROW ? blk / p.ygroups : blk;
+    const int tid = threadIdx.x;
+    const Policy pol(p, b);
+    const long long slot = (long long)b * p.Hs * p.Ws;
+    const uint8_t* img = p.img + slot * 3;
+    const uint8_t* msk = p.mask + slot;
+    uint8_t* out = p.out_u8 + slot * 3;
+    const int nitems = p.Hs * p.qpr;
+
+    int yy[U8_UNROLL], qq[U8_UNROLL];
+    bool valid[U8_UNROLL];
+    uint32_t m4[U8_UNROLL], d[U8_UNROLL][3];
+#pragma unroll
+    for (int k = 0; k < U8_UNROLL; ++k) {                 // the streaming loads of every item, none behind a branch
+        int y, q;
+        if (ROW) {
+            y = yg * U8_UNROLL + k; q = chunk * U8_THREADS + tid;
+            valid[k] = y < p.Hs && q < p.qpr;
+            y = y < p.Hs ? y : p.Hs - 1; q = q < p.qpr ? q : p.qpr - 1;
+        } else {
+            valid[k] = u8_item(chunk, k, tid, nitems, p.qpr, y, q);
+        }
+        yy[k] = y; qq[k] = q;
+        u8_load4(img, msk, (long long)y * p.Ws, 4 * q, p.Ws, VEC, [](int x) { return x; }, m4[k], d[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < U8_UNROLL; ++k) {                 // the bytes to store, in place of the bytes loaded
+        uint32_t o[3] = {0u, 0u, 0u};
+        const int y = yy[k], x0 = 4 * qq[k];
+        if (valid[k] && pol.ok && y < pol.h) {
+            const typename Policy::Row r = pol.row(y);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x0 + j;
+                if (x < pol.w) {
+                    const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
+                    uint32_t sb[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sb[c] = u8_get(d[k], 3 * j + c);
+                    if (mu != 0u) pol.pixel(r, x, mu, sb);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) u8_put(o, 3 * j + c, sb[c]);
+                }
+            }
+        }
+        d[k][0] = o[0]; d[k][1] = o[1]; d[k][2] = o[2];
+    }
+#pragma unroll
+    for (int k = 0; k < U8_UNROLL; ++k) {
+        if (!valid[k]) continue;
+        const long long px = (long long)yy[k] * p.Ws + 4 * qq[k];
+        if (VEC) {
+            ei_u32* s = reinterpret_cast<ei_u32*>(out + px * 3);
+            s[0] = d[k][0]; s[1] = d[k][1]; s[2] = d[k][2];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (4 * qq[k] + j < p.Ws) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) out[(px + j) * 3 + c] = (uint8_t)u8_get(d[k], 3 * j + c);
+                }
+        }
+    }
+}
+
 // ---- paste_back: the scaled step's fp32 result resampled to the SOURCE grid and pasted into the decoded u8 original, in one launch --
 //   out = source pixel where the mask is 0; elsewhere F.interpolate(lowres[:, :dh, :dw], size=(h, w), mode='bilinear', align_corners=False)
 //   (index arithmetic of rf_bilin_src, csrc/refine.hip) blended as mask * v + (1 - mask) * image and quantised as clip(. * 255, 0, 255) truncated.
 // This output has no counterpart in the reference (which writes the scaled image): the contract is BYTE-IDENTITY with the numpy restatement
-// tests/paste_back_util.py::paste_back_ref -- every operation rounded on its own, so every function below switches floating-point contraction
-// OFF, as resize_u8_kernel does.  Where the mask byte is 0 both forms of the mask give the source byte back ((k / 255.f) * 255.f truncates to k
-// for all 256 values): those pixels are copied, and the low-resolution tensor is read only for pixels whose mask byte is not 0.
-// A streaming kernel: 7 bytes per source pixel (1 mask + 3 in + 3 out) against a low-resolution tensor of 1 / 16 of that at factor 0.25, which
-// stays in L2 / the Infinity Cache.  One work item = 4 consecutive pixels of a slot row: one dword of mask, three dwords of RGB in, three out
-// (dword accesses where Ws % 4 == 0 and the pointers allow, byte accesses otherwise).  A 256-thread workgroup takes PB_UNROLL * 256 items of ONE
-// image (its sizes and scales are uniform: scalar loads, one division per workgroup) -- ROW: 256 consecutive items of PB_UNROLL consecutive rows
-// (slots of 192 items per row or more: the row and its y taps are uniform too); otherwise consecutive items of the slot, a lane divides once per
-// item by the items per row.  A lane has the streaming loads of all its items in flight before the gather, and every load before its first
-// store; the loads are unconditional (a lane past the end re-reads the last item and stores nothing).  No LDS, no atomics.
-#define PB_THREADS 256
-#define PB_UNROLL 4
-#define PB_ROW_MIN_ITEMS 192
-struct PasteParams {
-    const uint8_t* img;          // [B][Hs][Ws][3], each image's h x w pixels in the top-left corner of its slot
-    const uint8_t* mask;         // [B][Hs][Ws]
-    const int32_t* src_sizes;    // [B][2] = (h, w); h = 0: an empty slot -> zeros
+// tests/paste_back_util.py::paste_back_ref -- every operation rounded on its own, as in resize_u8_kernel.  Where the mask byte is 0 both forms of
+// the mask give the source byte back ((k / 255.f) * 255.f truncates to k for all 256 values): those pixels are copied.
+// u8_slot_walk over the source slots; the policy is the bilinear gather from the low-resolution tensor, which is 1 / 16 of the streams at
+// factor 0.25 and stays in L2 / the Infinity Cache.  Sizes that do not fit the slot / the low-resolution view (the host cannot see them
+// without a synchronisation) make the slot zeros, as an empty slot is.
+struct PasteParams : U8WalkParams {
+    int LH, LW;
     const int32_t* dst_sizes;    // [B][2] = (dh, dw): the valid corner of lowres
     const float* low;            // [B,3,LH,LW]
     long long low_bs;
-    uint8_t* out;                // [B][Hs][Ws][3]
-    int Hs, Ws, LH, LW, binarize;
-    int qpr, chunks, ygroups;    // items per slot row; workgroups per row (ROW) / per slot; groups of PB_UNROLL rows per slot (ROW)
 };
 struct PbAxis {
     int i0, i1;
@@ -628,122 +739,64 @@ __device__ __forceinline__ uint32_t pb_quant(float r) {
     t = fminf(fmaxf(t, 0.0f), 255.0f);
     return (uint32_t)(uint8_t)t;
 }
-template <bool VEC, bool ROW> __global__ __launch_bounds__(PB_THREADS) void paste_back_u8_kernel(PasteParams p) {
+struct PastePolicy {
+    typedef PasteParams Params;
+    struct Row {                 // the y taps: byte offsets of their rows inside a plane, the weights
+        unsigned r0, r1;
+        float l, hl;
+    };
+    bool ok;
+    int h, w, dh, dw, binarize;
+    float sy, sx;
+    const char* low;
+    long long plane;             // bytes of one low-resolution plane, < 2^32
+    unsigned rowb;
+    __device__ __forceinline__ PastePolicy(const PasteParams& p, int b) {
 #pragma clang fp contract(off)
-    int blk = blockIdx.x;
-    const int chunk = blk % p.chunks; blk /= p.chunks;
-    const int yg = ROW ? blk % p.ygroups : 0, b = ROW ? blk / p.ygroups : blk;
-    const int tid = threadIdx.x;
-    const int h = p.src_sizes[2 * b], w = p.src_sizes[2 * b + 1], dh = p.dst_sizes[2 * b], dw = p.dst_sizes[2 * b + 1];
-    // an empty slot, or sizes that do not fit the slot / the low-resolution view (the host cannot see them without a synchronisation): zeros
-    const bool ok = h > 0 && w > 0 && dh > 0 && dw > 0 && h <= p.Hs && w <= p.Ws && dh <= p.LH && dw <= p.LW;
-    const float sy = ok ? (float)dh / (float)h : 0.0f, sx = ok ? (float)dw / (float)w : 0.0f;
-    const long long slot = (long long)b * p.Hs * p.Ws;
-    const uint8_t* img = p.img + slot * 3;
-    const uint8_t* msk = p.mask + slot;
-    uint8_t* out = p.out + slot * 3;
-    const char* low = reinterpret_cast<const char*>(p.low + (long long)b * p.low_bs);
-    const long long plane = 4ll * p.LH * p.LW;           // bytes of one low-resolution plane, < 2^32
-    const unsigned rowb = 4u * (unsigned)p.LW;
-    const int nitems = p.Hs * p.qpr;
-
-    int yy[PB_UNROLL], qq[PB_UNROLL];
-    bool valid[PB_UNROLL];
-    uint32_t m4[PB_UNROLL], d[PB_UNROLL][3];
+        h = p.src_sizes[2 * b]; w = p.src_sizes[2 * b + 1]; dh = p.dst_sizes[2 * b]; dw = p.dst_sizes[2 * b + 1];
+        ok = h > 0 && w > 0 && dh > 0 && dw > 0 && h <= p.Hs && w <= p.Ws && dh <= p.LH && dw <= p.LW;
+        sy = ok ? (float)dh / (float)h : 0.0f; sx = ok ? (float)dw / (float)w : 0.0f;
+        low = reinterpret_cast<const char*>(p.low + (long long)b * p.low_bs);
+        plane = 4ll * p.LH * p.LW;
+        rowb = 4u * (unsigned)p.LW;
+        binarize = p.binarize;
+    }
+    __device__ __forceinline__ Row row(int y) const {
+#pragma clang fp contract(off)
+        const PbAxis ay = pb_axis(y, sy, dh);
+        Row r;
+        r.r0 = (unsigned)ay.i0 * rowb; r.r1 = (unsigned)ay.i1 * rowb;
+        r.l = ay.l; r.hl = 1.0f - ay.l;
+        return r;
+    }
+    __device__ __forceinline__ void pixel(const Row& r, int x, uint32_t mu, uint32_t (&sb)[3]) const {
+#pragma clang fp contract(off)
+        const PbAxis ax = pb_axis(x, sx, dw);
+        const float hx = 1.0f - ax.l;
+        // byte offsets inside one plane in 32 bits (the entry has checked that they fit) on a plane pointer that is uniform
+        const unsigned c0 = 4u * (unsigned)ax.i0, c1 = 4u * (unsigned)ax.i1;
+        float t[3][4];                                    // the pixel's twelve taps in flight together, then the arithmetic
 #pragma unroll
-    for (int k = 0; k < PB_UNROLL; ++k) {                 // the streaming loads of every item, none behind a branch
-        int y, q;
-        if (ROW) {
-            y = yg * PB_UNROLL + k; q = chunk * PB_THREADS + tid;
-            valid[k] = y < p.Hs && q < p.qpr;
-            y = y < p.Hs ? y : p.Hs - 1; q = q < p.qpr ? q : p.qpr - 1;
-        } else {
-            const int v = (chunk * PB_UNROLL + k) * PB_THREADS + tid;
-            valid[k] = v < nitems;
-            const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
-            y = (int)(vc / (unsigned)p.qpr); q = (int)(vc - (unsigned)y * (unsigned)p.qpr);
+        for (int c = 0; c < 3; ++c) {
+            const char* pl = low + c * plane;
+            t[c][0] = *reinterpret_cast<const float*>(pl + (r.r0 + c0)); t[c][1] = *reinterpret_cast<const float*>(pl + (r.r0 + c1));
+            t[c][2] = *reinterpret_cast<const float*>(pl + (r.r1 + c0)); t[c][3] = *reinterpret_cast<const float*>(pl + (r.r1 + c1));
         }
-        yy[k] = y; qq[k] = q;
-        const long long row = (long long)y * p.Ws;
-        if (VEC) {
-            const long long px = row + 4 * q;
-            m4[k] = *reinterpret_cast<const ei_u32*>(msk + px);
-            const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
-            d[k][0] = s[0]; d[k][1] = s[1]; d[k][2] = s[2];
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = r.hl * (hx * t[c][0] + ax.l * t[c][1]) + r.l * (hx * t[c][2] + ax.l * t[c][3]);
+        if (binarize) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sb[c] = pb_quant(v[c]);
         } else {
-            m4[k] = d[k][0] = d[k][1] = d[k][2] = 0u;
+            const float m = (float)mu / 255.0f, km = 1.0f - m;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {                 // (a column past the slot's edge re-reads the last one; it is never stored)
-                const int x = 4 * q + j < p.Ws ? 4 * q + j : p.Ws - 1;
-                m4[k] |= (uint32_t)msk[row + x] << (8 * j);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) d[k][(3 * j + c) >> 2] |= (uint32_t)img[(row + x) * 3 + c] << (8 * ((3 * j + c) & 3));
-            }
+            for (int c = 0; c < 3; ++c) sb[c] = pb_quant(m * v[c] + km * ((float)sb[c] / 255.0f));
         }
     }
-#pragma unroll
-    for (int k = 0; k < PB_UNROLL; ++k) {                 // the bytes to store, in place of the bytes loaded
-        uint32_t o[3] = {0u, 0u, 0u};
-        const int y = yy[k], x0 = 4 * qq[k];
-        if (valid[k] && ok && y < h) {
-            const PbAxis ay = pb_axis(y, sy, dh);
-            const float hy = 1.0f - ay.l;
-            const unsigned r0 = (unsigned)ay.i0 * rowb, r1 = (unsigned)ay.i1 * rowb;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int x = x0 + j;
-                if (x < w) {
-                    const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
-                    uint32_t sb[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) sb[c] = (d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3))) & 255u;
-                    if (mu != 0u) {                       // the only lanes that read the low-resolution tensor
-                        const PbAxis ax = pb_axis(x, sx, dw);
-                        const float hx = 1.0f - ax.l;
-                        // byte offsets inside one plane in 32 bits (the entry has checked that they fit) on a plane pointer that is uniform
-                        const unsigned c0 = 4u * (unsigned)ax.i0, c1 = 4u * (unsigned)ax.i1;
-                        float t[3][4];                    // the pixel's twelve taps in flight together, then the arithmetic
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const char* pl = low + c * plane;
-                            t[c][0] = *reinterpret_cast<const float*>(pl + (r0 + c0)); t[c][1] = *reinterpret_cast<const float*>(pl + (r0 + c1));
-                            t[c][2] = *reinterpret_cast<const float*>(pl + (r1 + c0)); t[c][3] = *reinterpret_cast<const float*>(pl + (r1 + c1));
-                        }
-                        float v[3];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) v[c] = hy * (hx * t[c][0] + ax.l * t[c][1]) + ay.l * (hx * t[c][2] + ax.l * t[c][3]);
-                        if (p.binarize) {
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) sb[c] = pb_quant(v[c]);
-                        } else {
-                            const float m = (float)mu / 255.0f, km = 1.0f - m;
-#pragma unroll
-                            for (int c = 0; c < 3; ++c) sb[c] = pb_quant(m * v[c] + km * ((float)sb[c] / 255.0f));
-                        }
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) o[(3 * j + c) >> 2] |= sb[c] << (8 * ((3 * j + c) & 3));
-                }
-            }
-        }
-        d[k][0] = o[0]; d[k][1] = o[1]; d[k][2] = o[2];
-    }
-#pragma unroll
-    for (int k = 0; k < PB_UNROLL; ++k) {
-        if (!valid[k]) continue;
-        const long long px = (long long)yy[k] * p.Ws + 4 * qq[k];
-        if (VEC) {
-            ei_u32* s = reinterpret_cast<ei_u32*>(out + px * 3);
-            s[0] = d[k][0]; s[1] = d[k][1]; s[2] = d[k][2];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * qq[k] + j < p.Ws) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) out[(px + j) * 3 + c] = (uint8_t)(d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3)));
-                }
-        }
-    }
+};
+template <bool VEC, bool ROW> __global__ __launch_bounds__(U8_THREADS) void paste_back_u8_kernel(PasteParams p) {
+    u8_slot_walk<VEC, ROW, PastePolicy>(p);
 }
 
 // ---- crop_to_mask: the step's two ends when the generator sees only a WINDOW (y0, x0, ch, cw) of each image's source slot --
@@ -751,24 +804,17 @@ template <bool VEC, bool ROW> __global__ __launch_bounds__(PB_THREADS) void past
 //   C = image[y0:y0+ch, x0:x0+cw] and M = mask[y0:y0+ch, x0:x0+cw] with sizes (ch, cw) -- BIT FOR BIT (tests/crop_util.py holds both to those
 //   entries on host-cropped slots and to a numpy restatement), so the expressions below are theirs, with floating-point contraction OFF -- and
 //   the paste writes every source byte outside the window (and inside it where the mask byte is 0: (k / 255.f) * 255.f truncates to k) as it is.
-// Like paste_back this output has no counterpart in the reference.  Work items of 4 consecutive pixels of a row as in paste_back_u8_kernel: a
-// 256-thread workgroup takes CR_UNROLL * 256 items of ONE image (sizes, rect and their checks are uniform: scalar loads), every load of a lane
-// before its first store.  The compose writes 16 bytes per window pixel (a float4 per plane and item) for 4 read; the paste moves 7 bytes per
-// SOURCE pixel and reads the prediction only under the mask, inside the window.  No LDS, no atomics.
-#define CR_THREADS 256
-#define CR_UNROLL 4
-struct CropParams {
-    const uint8_t* img;          // [B][Hs][Ws][3], each image's h x w pixels in the top-left corner of its slot
-    const uint8_t* mask;         // [B][Hs][Ws]
-    const int32_t* src_sizes;    // [B][2] = (h, w); h = 0: an empty slot
+// Like paste_back this output has no counterpart in the reference.  The paste is u8_slot_walk over the source slots with the window test and the
+// blend as its policy: it reads the prediction only under the mask, inside the window.  The compose walks the PADDED WINDOW instead, in the same
+// items (u8_item, u8_load4: U8_UNROLL * 256 consecutive items of one image per workgroup, every load of a lane before its first store) and
+// writes 16 bytes per window pixel (a float4 per plane and item) for 4 read.  No LDS, no atomics.
+struct CropParams : U8WalkParams {   // (qpr, chunks: compose: of the padded window, paste: of the slot)
+    int Hp, Wp;
     const int32_t* rects;        // [B][4] = (y0, x0, ch, cw): the window
     const float* pred;           // paste: [B,3,Hp,Wp]
     long long pred_bs;
     float* out;                  // compose: [B,4,Hp,Wp]
     long long out_bs;
-    uint8_t* out_u8;             // paste: [B][Hs][Ws][3]
-    int Hs, Ws, Hp, Wp, binarize;
-    int qpr, chunks, ygroups;    // items per row (compose: of the padded window, paste: of the slot); workgroups per row (ROW) / per image; row groups (ROW)
     int vec_ld, vec_st;          // compose: dword loads from the slots (Ws % 4 == 0, aligned pointers) / float4 stores (Wp % 4 == 0, aligned view)
 };
 struct CropRect {
@@ -786,7 +832,7 @@ __device__ __forceinline__ CropRect crop_rect_load(const CropParams& p, int b) {
     return r;
 }
 // masked_img = cat(C / 255 * (1 - m), m) with the symmetric padding of C up to (Hp, Wp): mask_compose_u8_kernel on the window
-__global__ __launch_bounds__(CR_THREADS) void crop_compose_u8_kernel(CropParams p) {
+__global__ __launch_bounds__(U8_THREADS) void crop_compose_u8_kernel(CropParams p) {
 #pragma clang fp contract(off)
     const int b = blockIdx.x / p.chunks, chunk = blockIdx.x - b * p.chunks;
     const int tid = threadIdx.x;
@@ -801,36 +847,17 @@ __global__ __launch_bounds__(CR_THREADS) void crop_compose_u8_kernel(CropParams 
     const int nitems = p.Hp * p.qpr;
     const bool vld = p.vec_ld && (x0 & 3) == 0;          // the window's rows start on a dword of the slot
 
-    int yy[CR_UNROLL], qq[CR_UNROLL];
-    bool valid[CR_UNROLL];
-    uint32_t m4[CR_UNROLL], d[CR_UNROLL][3];
+    int yy[U8_UNROLL], qq[U8_UNROLL];
+    bool valid[U8_UNROLL];
+    uint32_t m4[U8_UNROLL], d[U8_UNROLL][3];
 #pragma unroll
-    for (int k = 0; k < CR_UNROLL; ++k) {                 // the loads of every item (a lane past the end re-reads the last item and stores nothing)
-        const int v = (chunk * CR_UNROLL + k) * CR_THREADS + tid;
-        valid[k] = v < nitems;
-        const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
-        const int y = (int)(vc / (unsigned)p.qpr), q = (int)(vc - (unsigned)y * (unsigned)p.qpr);
-        yy[k] = y; qq[k] = q;
-        const long long row = (long long)(y0 + ew_symmetric(y, ch)) * p.Ws + x0;
-        if (vld && 4 * q + 4 <= cw) {                     // four pixels of the window itself: one dword of mask, three of RGB
-            const long long px = row + 4 * q;
-            m4[k] = *reinterpret_cast<const ei_u32*>(msk + px);
-            const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
-            d[k][0] = s[0]; d[k][1] = s[1]; d[k][2] = s[2];
-        } else {
-            m4[k] = d[k][0] = d[k][1] = d[k][2] = 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                 // (a column past the view's edge re-reads the last one; it is never stored)
-                const int x = 4 * q + j < p.Wp ? 4 * q + j : p.Wp - 1;
-                const long long px = row + ew_symmetric(x, cw);
-                m4[k] |= (uint32_t)msk[px] << (8 * j);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) d[k][(3 * j + c) >> 2] |= (uint32_t)img[px * 3 + c] << (8 * ((3 * j + c) & 3));
-            }
-        }
+    for (int k = 0; k < U8_UNROLL; ++k) {                 // the loads of every item: dwords for four pixels of the window itself, else mirrored bytes
+        valid[k] = u8_item(chunk, k, tid, nitems, p.qpr, yy[k], qq[k]);
+        const long long row = (long long)(y0 + ew_symmetric(yy[k], ch)) * p.Ws + x0;
+        u8_load4(img, msk, row, 4 * qq[k], p.Wp, vld && 4 * qq[k] + 4 <= cw, [cw](int x) { return ew_symmetric(x, cw); }, m4[k], d[k]);
     }
 #pragma unroll
-    for (int k = 0; k < CR_UNROLL; ++k) {
+    for (int k = 0; k < U8_UNROLL; ++k) {
         if (!valid[k]) continue;
         float v[4][4];
 #pragma unroll
@@ -838,125 +865,51 @@ __global__ __launch_bounds__(CR_THREADS) void crop_compose_u8_kernel(CropParams 
             float rgb[3] = {0.f, 0.f, 0.f}, m = 0.f;
             if (r.ok) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) rgb[c] = (float)((d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3))) & 255u) / 255.0f;
+                for (int c = 0; c < 3; ++c) rgb[c] = ei_byte(d[k], 3 * j + c);
                 const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
                 m = p.binarize ? (mu > 0 ? 1.0f : 0.0f) : (float)mu / 255.0f;
             }
             const float km = 1.0f - m;
             v[0][j] = rgb[0] * km; v[1][j] = rgb[1] * km; v[2][j] = rgb[2] * km; v[3][j] = m;
         }
-        float* o = out + (long long)yy[k] * p.Wp + 4 * qq[k];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (p.vec_st) {
-                *reinterpret_cast<float4*>(o + c * hw) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (4 * qq[k] + j < p.Wp) o[c * hw + j] = v[c][j];
-            }
-        }
+        ei_store4(out + (long long)yy[k] * p.Wp + 4 * qq[k], hw, 4 * qq[k], p.Wp, p.vec_st != 0, v);
     }
 }
-// out = the source bytes, with blend_quantize_u8_kernel's bytes for (C, M, pred) inside the window; zeros outside h x w.  The item walk, the
-// VEC / ROW forms and the load / store phases are paste_back_u8_kernel's.
-template <bool VEC, bool ROW> __global__ __launch_bounds__(CR_THREADS) void crop_paste_u8_kernel(CropParams p) {
+// out = the source bytes, with blend_quantize_u8_kernel's bytes for (C, M, pred) inside the window; zeros outside h x w
+struct CropPastePolicy : CropRect {
+    typedef CropParams Params;
+    struct Row {
+        bool in;                 // the row crosses the window
+        unsigned off;            // byte offset of its window row inside one plane in 32 bits (the entry has checked that it fits)
+    };
+    const char* pred;
+    long long plane;             // bytes of one plane of the prediction, < 2^32
+    int Wp, binarize;
+    __device__ __forceinline__ CropPastePolicy(const CropParams& p, int b) : CropRect(crop_rect_load(p, b)) {
+        pred = reinterpret_cast<const char*>(p.pred + (long long)b * p.pred_bs);
+        plane = 4ll * p.Hp * p.Wp;
+        Wp = p.Wp; binarize = p.binarize;
+    }
+    __device__ __forceinline__ Row row(int y) const {
+        Row r;
+        r.in = y >= y0 && y - y0 < ch;
+        r.off = r.in ? 4u * (unsigned)(y - y0) * (unsigned)Wp : 0u;
+        return r;
+    }
+    __device__ __forceinline__ void pixel(const Row& r, int x, uint32_t mu, uint32_t (&sb)[3]) const {
 #pragma clang fp contract(off)
-    int blk = blockIdx.x;
-    const int chunk = blk % p.chunks; blk /= p.chunks;
-    const int yg = ROW ? blk % p.ygroups : 0, b = ROW ? blk / p.ygroups : blk;
-    const int tid = threadIdx.x;
-    const CropRect r = crop_rect_load(p, b);
-    const long long slot = (long long)b * p.Hs * p.Ws;
-    const uint8_t* img = p.img + slot * 3;
-    const uint8_t* msk = p.mask + slot;
-    uint8_t* out = p.out_u8 + slot * 3;
-    const char* pred = reinterpret_cast<const char*>(p.pred + (long long)b * p.pred_bs);
-    const long long plane = 4ll * p.Hp * p.Wp;           // bytes of one plane of the prediction, < 2^32
-    const int nitems = p.Hs * p.qpr;
-
-    int yy[CR_UNROLL], qq[CR_UNROLL];
-    bool valid[CR_UNROLL];
-    uint32_t m4[CR_UNROLL], d[CR_UNROLL][3];
+        if (!(r.in && x >= x0 && x - x0 < cw)) return;
+        const unsigned off = r.off + 4u * (unsigned)(x - x0);
+        float pr[3];
 #pragma unroll
-    for (int k = 0; k < CR_UNROLL; ++k) {                 // the streaming loads of every item, none behind a branch
-        int y, q;
-        if (ROW) {
-            y = yg * CR_UNROLL + k; q = chunk * CR_THREADS + tid;
-            valid[k] = y < p.Hs && q < p.qpr;
-            y = y < p.Hs ? y : p.Hs - 1; q = q < p.qpr ? q : p.qpr - 1;
-        } else {
-            const int v = (chunk * CR_UNROLL + k) * CR_THREADS + tid;
-            valid[k] = v < nitems;
-            const unsigned vc = (unsigned)(v < nitems ? v : nitems - 1);
-            y = (int)(vc / (unsigned)p.qpr); q = (int)(vc - (unsigned)y * (unsigned)p.qpr);
-        }
-        yy[k] = y; qq[k] = q;
-        const long long row = (long long)y * p.Ws;
-        if (VEC) {
-            const long long px = row + 4 * q;
-            m4[k] = *reinterpret_cast<const ei_u32*>(msk + px);
-            const ei_u32* s = reinterpret_cast<const ei_u32*>(img + px * 3);
-            d[k][0] = s[0]; d[k][1] = s[1]; d[k][2] = s[2];
-        } else {
-            m4[k] = d[k][0] = d[k][1] = d[k][2] = 0u;
+        for (int c = 0; c < 3; ++c) pr[c] = *reinterpret_cast<const float*>(pred + c * plane + off);
+        const float m = binarize ? 1.0f : (float)mu / 255.0f, km = 1.0f - m;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {                 // (a column past the slot's edge re-reads the last one; it is never stored)
-                const int x = 4 * q + j < p.Ws ? 4 * q + j : p.Ws - 1;
-                m4[k] |= (uint32_t)msk[row + x] << (8 * j);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) d[k][(3 * j + c) >> 2] |= (uint32_t)img[(row + x) * 3 + c] << (8 * ((3 * j + c) & 3));
-            }
-        }
+        for (int c = 0; c < 3; ++c) sb[c] = pb_quant(ew_blend(m, km, pr[c], (float)sb[c] / 255.0f));
     }
-#pragma unroll
-    for (int k = 0; k < CR_UNROLL; ++k) {                 // the bytes to store, in place of the bytes loaded
-        uint32_t o[3] = {0u, 0u, 0u};
-        const int y = yy[k], xq = 4 * qq[k];
-        if (valid[k] && r.ok && y < r.h) {
-            const bool inrow = y >= r.y0 && y - r.y0 < r.ch;
-            // byte offset of the window row inside one plane in 32 bits (the entry has checked that it fits)
-            const unsigned prow = inrow ? 4u * (unsigned)(y - r.y0) * (unsigned)p.Wp : 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int x = xq + j;
-                if (x < r.w) {
-                    const uint32_t mu = (m4[k] >> (8 * j)) & 255u;
-                    uint32_t sb[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) sb[c] = (d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3))) & 255u;
-                    if (mu != 0u && inrow && x >= r.x0 && x - r.x0 < r.cw) {       // the only lanes that read the prediction
-                        const unsigned off = prow + 4u * (unsigned)(x - r.x0);
-                        float pr[3];
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) pr[c] = *reinterpret_cast<const float*>(pred + c * plane + off);
-                        const float m = p.binarize ? 1.0f : (float)mu / 255.0f, km = 1.0f - m;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) sb[c] = pb_quant(ew_blend(m, km, pr[c], (float)sb[c] / 255.0f));
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) o[(3 * j + c) >> 2] |= sb[c] << (8 * ((3 * j + c) & 3));
-                }
-            }
-        }
-        d[k][0] = o[0]; d[k][1] = o[1]; d[k][2] = o[2];
-    }
-#pragma unroll
-    for (int k = 0; k < CR_UNROLL; ++k) {
-        if (!valid[k]) continue;
-        const long long px = (long long)yy[k] * p.Ws + 4 * qq[k];
-        if (VEC) {
-            ei_u32* s = reinterpret_cast<ei_u32*>(out + px * 3);
-            s[0] = d[k][0]; s[1] = d[k][1]; s[2] = d[k][2];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * qq[k] + j < p.Ws) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) out[(px + j) * 3 + c] = (uint8_t)(d[k][(3 * j + c) >> 2] >> (8 * ((3 * j + c) & 3)));
-                }
-        }
-    }
+};
+template <bool VEC, bool ROW> __global__ __launch_bounds__(U8_THREADS) void crop_paste_u8_kernel(CropParams p) {
+    u8_slot_walk<VEC, ROW, CropPastePolicy>(p);
 }
 
 struct AffineParams {
@@ -1252,41 +1205,63 @@ extern "C" int lama_resize_u8_fwd(void* stream, const uint8_t* image_hwc, const 
     return LAMA_OK;
 }
 
+// The launch plan of the u8 item kernels (see u8_slot_walk) for `batch` images of H x W pixels: fills p.qpr, p.chunks and -- with `rows`, where
+// a row has U8_ROW_MIN_ITEMS items or more -- p.ygroups.  vec: the slots (p.img, p.mask, p.out_u8 where there is one) take dword accesses.
+// 64-bit arithmetic throughout: W + 3, H + 3 may not fit an int.
+struct U8Plan {
+    bool vec, row;
+    unsigned nwg;
+};
+static int u8_walk_plan(U8WalkParams& p, int H, int W, int batch, bool rows, U8Plan& pl) {
+    p.qpr = (int)lama_ceil_div64(W, 4);
+    pl.vec = p.Ws % 4 == 0 && !(((uintptr_t)p.img | (uintptr_t)p.mask | (uintptr_t)p.out_u8) & 3);
+    pl.row = rows && p.qpr >= U8_ROW_MIN_ITEMS;
+    long long nwg;
+    if (pl.row) {
+        p.chunks = (int)lama_ceil_div64(p.qpr, U8_THREADS);
+        p.ygroups = (int)lama_ceil_div64(H, U8_UNROLL);
+        nwg = (long long)batch * p.ygroups * p.chunks;
+    } else {
+        const long long n = (long long)H * p.qpr;
+        if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;            // 32-bit item indices
+        p.chunks = (int)lama_ceil_div64(n, U8_THREADS * U8_UNROLL);
+        nwg = (long long)batch * p.chunks;
+    }
+    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
+    pl.nwg = (unsigned)nwg;
+    return LAMA_OK;
+}
+// the VEC x ROW instantiation of a walk kernel that a plan asks for
+#define U8_LAUNCH1(KERNEL, V, R, pl, stream, p) hipLaunchKernelGGL((KERNEL<V, R>), dim3((pl).nwg), dim3(U8_THREADS), 0, (hipStream_t)(stream), p)
+#define U8_LAUNCH(KERNEL, pl, stream, p)                                                                                            \
+    do {                                                                                                                            \
+        if ((pl).vec) { if ((pl).row) U8_LAUNCH1(KERNEL, true, true, pl, stream, p); else U8_LAUNCH1(KERNEL, true, false, pl, stream, p); } \
+        else { if ((pl).row) U8_LAUNCH1(KERNEL, false, true, pl, stream, p); else U8_LAUNCH1(KERNEL, false, false, pl, stream, p); } \
+    } while (0)
+// an fp32 view of three planes that a paste gathers from with 32-bit byte offsets inside a plane
+static int u8_check_rgb_view(const lama_tensor* t) {
+    if (!t || !t->ptr || t->C != 3 || t->H <= 0 || t->W <= 0 || t->batch_stride < (int64_t)3 * t->H * t->W) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({t})) return LAMA_ERR_UNSUPPORTED;
+    if ((uintptr_t)t->ptr & 3) return LAMA_ERR_BAD_ARG;
+    if ((long long)t->H * t->W > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;
+    return LAMA_OK;
+}
+
 // the scaled step's result pasted back into the source image: see paste_back_u8_kernel
 extern "C" int lama_paste_back_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* dst_sizes,
                                       int32_t Hs, int32_t Ws, const lama_tensor* lowres, uint8_t* out_hwc, int32_t batch, int32_t binarize) {
-    if (!image_hwc || !mask || !src_sizes || !dst_sizes || !lowres || !lowres->ptr || !out_hwc) return LAMA_ERR_BAD_ARG;
-    if (batch <= 0 || Hs <= 0 || Ws <= 0 || lowres->C != 3 || lowres->H <= 0 || lowres->W <= 0) return LAMA_ERR_BAD_ARG;
-    if (lowres->batch_stride < (int64_t)3 * lowres->H * lowres->W || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
-    if (!all_f32({lowres})) return LAMA_ERR_UNSUPPORTED;
-    if ((uintptr_t)lowres->ptr & 3) return LAMA_ERR_BAD_ARG;
-    if ((long long)lowres->H * lowres->W > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;      // 32-bit byte offsets inside a low-resolution plane
+    if (!image_hwc || !mask || !src_sizes || !dst_sizes || !out_hwc || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0) return LAMA_ERR_BAD_ARG;
+    if (const int e = u8_check_rgb_view(lowres)) return e;
     PasteParams p;
     memset(&p, 0, sizeof(p));
     p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.dst_sizes = dst_sizes;
     p.low = (const float*)lowres->ptr; p.low_bs = lowres->batch_stride;
-    p.out = out_hwc;
+    p.out_u8 = out_hwc;
     p.Hs = Hs; p.Ws = Ws; p.LH = lowres->H; p.LW = lowres->W; p.binarize = binarize != 0;
-    p.qpr = lama_ceil_div(Ws, 4);
-    const bool vec = Ws % 4 == 0 && !(((uintptr_t)image_hwc | (uintptr_t)mask | (uintptr_t)out_hwc) & 3);
-    const bool row = p.qpr >= PB_ROW_MIN_ITEMS;
-    long long nwg;
-    if (row) {
-        p.chunks = lama_ceil_div(p.qpr, PB_THREADS);
-        p.ygroups = lama_ceil_div(Hs, PB_UNROLL);
-        nwg = (long long)batch * p.ygroups * p.chunks;
-    } else {
-        const long long n = (long long)Hs * p.qpr;
-        if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;            // 32-bit item indices
-        p.chunks = (int)lama_ceil_div64(n, PB_THREADS * PB_UNROLL);
-        nwg = (long long)batch * p.chunks;
-    }
-    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
-    const dim3 grid((unsigned)nwg), block(PB_THREADS);
-#define PB_LAUNCH(V, R) hipLaunchKernelGGL((paste_back_u8_kernel<V, R>), grid, block, 0, (hipStream_t)stream, p)
-    if (vec) { if (row) PB_LAUNCH(true, true); else PB_LAUNCH(true, false); }
-    else { if (row) PB_LAUNCH(false, true); else PB_LAUNCH(false, false); }
-#undef PB_LAUNCH
+    U8Plan pl;
+    if (const int e = u8_walk_plan(p, Hs, Ws, batch, true, pl)) return e;
+    U8_LAUNCH(paste_back_u8_kernel, pl, stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }
@@ -1304,53 +1279,29 @@ extern "C" int lama_crop_compose_u8_fwd(void* stream, const uint8_t* image_hwc, 
     p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.rects = rects;
     p.out = (float*)out->ptr; p.out_bs = out->batch_stride;
     p.Hs = Hs; p.Ws = Ws; p.Hp = out->H; p.Wp = out->W; p.binarize = binarize != 0;
-    p.qpr = (int)lama_ceil_div64(out->W, 4);                         // (64-bit: W + 3 may not fit an int)
-    const long long n = (long long)out->H * p.qpr;
-    if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;                // 32-bit item indices
-    p.chunks = (int)lama_ceil_div64(n, CR_THREADS * CR_UNROLL);
-    p.vec_ld = Ws % 4 == 0 && !(((uintptr_t)image_hwc | (uintptr_t)mask) & 3);
+    U8Plan pl;                                                        // the items of the padded window, never by rows
+    if (const int e = u8_walk_plan(p, out->H, out->W, batch, false, pl)) return e;
+    p.vec_ld = pl.vec;
     p.vec_st = out->W % 4 == 0 && out->batch_stride % 4 == 0 && !((uintptr_t)out->ptr & 15);
-    const long long nwg = (long long)batch * p.chunks;
-    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
-    hipLaunchKernelGGL(crop_compose_u8_kernel, dim3((unsigned)nwg), dim3(CR_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(crop_compose_u8_kernel, dim3(pl.nwg), dim3(U8_THREADS), 0, (hipStream_t)stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }
 
 extern "C" int lama_crop_paste_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects,
                                       int32_t Hs, int32_t Ws, const lama_tensor* pred, uint8_t* out_hwc, int32_t batch, int32_t binarize) {
-    if (!image_hwc || !mask || !src_sizes || !rects || !pred || !pred->ptr || !out_hwc) return LAMA_ERR_BAD_ARG;
-    if (batch <= 0 || Hs <= 0 || Ws <= 0 || pred->C != 3 || pred->H <= 0 || pred->W <= 0) return LAMA_ERR_BAD_ARG;
-    if (pred->batch_stride < (int64_t)3 * pred->H * pred->W || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
-    if (!all_f32({pred})) return LAMA_ERR_UNSUPPORTED;
-    if ((uintptr_t)pred->ptr & 3) return LAMA_ERR_BAD_ARG;
-    if ((long long)pred->H * pred->W > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;          // 32-bit byte offsets inside a plane of the prediction
+    if (!image_hwc || !mask || !src_sizes || !rects || !out_hwc || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0) return LAMA_ERR_BAD_ARG;
+    if (const int e = u8_check_rgb_view(pred)) return e;
     CropParams p;
     memset(&p, 0, sizeof(p));
     p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.rects = rects;
     p.pred = (const float*)pred->ptr; p.pred_bs = pred->batch_stride;
     p.out_u8 = out_hwc;
     p.Hs = Hs; p.Ws = Ws; p.Hp = pred->H; p.Wp = pred->W; p.binarize = binarize != 0;
-    p.qpr = (int)lama_ceil_div64(Ws, 4);                             // (64-bit here and below: Ws + 3, Hs + 3 may not fit an int)
-    const bool vec = Ws % 4 == 0 && !(((uintptr_t)image_hwc | (uintptr_t)mask | (uintptr_t)out_hwc) & 3);
-    const bool row = p.qpr >= PB_ROW_MIN_ITEMS;
-    long long nwg;
-    if (row) {
-        p.chunks = (int)lama_ceil_div64(p.qpr, CR_THREADS);
-        p.ygroups = (int)lama_ceil_div64(Hs, CR_UNROLL);
-        nwg = (long long)batch * p.ygroups * p.chunks;
-    } else {
-        const long long n = (long long)Hs * p.qpr;
-        if (n > 0x3fffffffll) return LAMA_ERR_UNSUPPORTED;            // 32-bit item indices
-        p.chunks = (int)lama_ceil_div64(n, CR_THREADS * CR_UNROLL);
-        nwg = (long long)batch * p.chunks;
-    }
-    if (nwg > 0x7fffffffll) return LAMA_ERR_UNSUPPORTED;              // one grid dimension
-    const dim3 grid((unsigned)nwg), block(CR_THREADS);
-#define CR_LAUNCH(V, R) hipLaunchKernelGGL((crop_paste_u8_kernel<V, R>), grid, block, 0, (hipStream_t)stream, p)
-    if (vec) { if (row) CR_LAUNCH(true, true); else CR_LAUNCH(true, false); }
-    else { if (row) CR_LAUNCH(false, true); else CR_LAUNCH(false, false); }
-#undef CR_LAUNCH
+    U8Plan pl;
+    if (const int e = u8_walk_plan(p, Hs, Ws, batch, true, pl)) return e;
+    U8_LAUNCH(crop_paste_u8_kernel, pl, stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }

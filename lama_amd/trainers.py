@@ -85,6 +85,39 @@ class DefaultInpaintingTrainingModule(nn.Module):
         return batch
 
 
+    def _u8_operands(self, what: str, image_hwc: torch.Tensor, mask: torch.Tensor, out_u8: torch.Tensor):
+        """The operand checks of the u8 steps: contiguous u8 image / output slots [B,H,W,3] and mask slots [B,H,W] on the device.  Returns the
+        executor and the stream of the step."""
+        ex = self.generator._exec
+        if not ex.injected and not image_hwc.is_cuda:
+            raise L.LamaError('lama_amd runs on an MI355X only: input tensor is on ' + str(image_hwc.device) + ' (there is no CPU fallback)')
+        if image_hwc.dtype != torch.uint8 or mask.dtype != torch.uint8 or out_u8.dtype != torch.uint8:
+            raise L.LamaError(f'{what}: uint8 image / mask / output tensors')
+        B, H, W, _ = image_hwc.shape
+        if tuple(mask.shape) != (B, H, W) or tuple(out_u8.shape) != (B, H, W, 3) or not (image_hwc.is_contiguous() and mask.is_contiguous() and out_u8.is_contiguous()):
+            raise L.LamaError(f'{what}: image {tuple(image_hwc.shape)} / mask {tuple(mask.shape)} / out {tuple(out_u8.shape)}: contiguous [B,H,W,3], [B,H,W], [B,H,W,3]')
+        if not self.concat_mask:
+            raise NotImplementedError('concat_mask=False is not used by big-lama')
+        return ex, ex.stream(image_hwc)
+
+    def _generate_u8(self, shape, device, sparse_tail: bool, compose) -> torch.Tensor:
+        """``compose(masked)`` writes the generator's input of ``shape`` into the buffer its plan reads; the generator then runs on it with
+        ``sparse_tail`` as given (the sparse-tail plans of a shape are cached apart from the dense ones that forward(batch) and a bare
+        generator(x) take, and have an input buffer of their own) and ``clone_output = False``: the caller's last launch consumes the plan's own
+        output buffer at once.  Both attributes are restored."""
+        gen = self.generator
+        want = {'sparse_tail': bool(sparse_tail), 'clone_output': False}
+        keep = {k: getattr(gen, k) for k in want if getattr(gen, k, None) is not None}
+        try:
+            for k in keep:
+                setattr(gen, k, want[k])
+            masked = gen.input_buffer(shape, device) if hasattr(gen, 'input_buffer') else torch.empty(*shape, device=device)
+            compose(masked)
+            return gen(masked)
+        finally:
+            for k, v in keep.items():
+                setattr(gen, k, v)
+
     def forward_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, sizes, out_u8: torch.Tensor, binarize: bool = True,
                    out_key: str = 'inpainted') -> torch.Tensor:
         """The predict step of bin/predict.py:82-92 on what is on disk (round 6, ABI v110): ``image_hwc`` u8 [B,Hp,Wp,3] and ``mask`` u8 [B,Hp,Wp]
@@ -96,38 +129,12 @@ class DefaultInpaintingTrainingModule(nn.Module):
         the generator's output without the blend; the padding columns are cropped by the caller as predict.py:87-90 does)."""
         if out_key not in ('inpainted', 'predicted_image'):
             raise L.LamaError(f"out_key {out_key!r}: the predict_only forward produces 'inpainted' and 'predicted_image' (default.py:70-71)")
-        ex = self.generator._exec
-        if not ex.injected and not image_hwc.is_cuda:
-            raise L.LamaError('lama_amd runs on an MI355X only: input tensor is on ' + str(image_hwc.device) + ' (there is no CPU fallback)')
-        if image_hwc.dtype != torch.uint8 or mask.dtype != torch.uint8 or out_u8.dtype != torch.uint8:
-            raise L.LamaError('forward_u8: uint8 image / mask / output tensors')
+        ex, st = self._u8_operands('forward_u8', image_hwc, mask, out_u8)
         B, H, W, _ = image_hwc.shape
-        if tuple(mask.shape) != (B, H, W) or tuple(out_u8.shape) != (B, H, W, 3) or not (image_hwc.is_contiguous() and mask.is_contiguous() and out_u8.is_contiguous()):
-            raise L.LamaError(f'forward_u8: image {tuple(image_hwc.shape)} / mask {tuple(mask.shape)} / out {tuple(out_u8.shape)}: contiguous [B,H,W,3], [B,H,W], [B,H,W,3]')
-        if not self.concat_mask:
-            raise NotImplementedError('concat_mask=False is not used by big-lama')
-        st = ex.stream(image_hwc)
-        gen = self.generator
         # 'inpainted' keeps mask * pred + (1 - mask) * image: the blend below never reads pred where the mask is 0, so the generator may leave those
-        # pixels unwritten -- the sparse-tail plans of this shape (generator.sparse_tail; cached apart from the dense ones that 'predicted_image',
-        # forward(batch) and a bare generator(x) take)
-        keep_sparse = getattr(gen, 'sparse_tail', None)
-        if keep_sparse is not None:
-            gen.sparse_tail = out_key == 'inpainted'
-        try:
-            masked = gen.input_buffer((B, 4, H, W), image_hwc.device) if hasattr(gen, 'input_buffer') else torch.empty(B, 4, H, W, device=image_hwc.device)
-            ex.lib.mask_compose_u8(image_hwc, mask, sizes, L.view(masked), B, binarize, st)
-            if hasattr(gen, 'clone_output'):
-                keep, gen.clone_output = gen.clone_output, False                   # the blend below consumes the plan's own output buffer at once
-                try:
-                    pred = gen(masked)
-                finally:
-                    gen.clone_output = keep
-            else:
-                pred = gen(masked)
-        finally:
-            if keep_sparse is not None:
-                gen.sparse_tail = keep_sparse
+        # pixels unwritten (generator.sparse_tail); 'predicted_image' needs every pixel
+        pred = self._generate_u8((B, 4, H, W), image_hwc.device, out_key == 'inpainted',
+                                 lambda masked: ex.lib.mask_compose_u8(image_hwc, mask, sizes, L.view(masked), B, binarize, st))
         if out_key == 'predicted_image':
             ex.lib.quantize_u8_hwc(L.view(pred), out_u8, B, H, W, st)              # predict.py:92 on batch['predicted_image']
         else:
@@ -142,38 +149,13 @@ class DefaultInpaintingTrainingModule(nn.Module):
         the generator call is the one ``forward_u8`` makes for that shape (plans, graph replay, sparse tail), and the last launch writes the source
         image with the window's blended, quantised bytes pasted in (lama_crop_paste_u8_fwd) into ``out_u8`` [B,Hs,Ws,3] (returned): what
         ``forward_u8`` gives for the cropped arrays, pasted by slicing, byte for byte."""
-        ex = self.generator._exec
-        if not ex.injected and not image_hwc.is_cuda:
-            raise L.LamaError('lama_amd runs on an MI355X only: input tensor is on ' + str(image_hwc.device) + ' (there is no CPU fallback)')
-        if image_hwc.dtype != torch.uint8 or mask.dtype != torch.uint8 or out_u8.dtype != torch.uint8:
-            raise L.LamaError('forward_u8_crop: uint8 image / mask / output tensors')
-        B, Hs, Ws, _ = image_hwc.shape
-        if tuple(mask.shape) != (B, Hs, Ws) or tuple(out_u8.shape) != (B, Hs, Ws, 3) or not (image_hwc.is_contiguous() and mask.is_contiguous() and out_u8.is_contiguous()):
-            raise L.LamaError(f'forward_u8_crop: image {tuple(image_hwc.shape)} / mask {tuple(mask.shape)} / out {tuple(out_u8.shape)}: contiguous [B,Hs,Ws,3], [B,Hs,Ws], [B,Hs,Ws,3]')
+        ex, st = self._u8_operands('forward_u8_crop', image_hwc, mask, out_u8)
         if int(Hp) < 1 or int(Wp) < 1:
             raise L.LamaError(f'forward_u8_crop: a padded window of at least one pixel, got {Hp}x{Wp}')
-        if not self.concat_mask:
-            raise NotImplementedError('concat_mask=False is not used by big-lama')
-        st = ex.stream(image_hwc)
-        gen = self.generator
-        keep_sparse = getattr(gen, 'sparse_tail', None)      # the paste reads pred only under the mask, as the blend does: the sparse-tail plans
-        if keep_sparse is not None:
-            gen.sparse_tail = True
-        try:
-            shape = (B, 4, int(Hp), int(Wp))
-            masked = gen.input_buffer(shape, image_hwc.device) if hasattr(gen, 'input_buffer') else torch.empty(*shape, device=image_hwc.device)
-            ex.lib.crop_compose_u8(image_hwc, mask, sizes, rects, L.view(masked), B, binarize, st)
-            if hasattr(gen, 'clone_output'):
-                keep, gen.clone_output = gen.clone_output, False                   # the paste below consumes the plan's own output buffer at once
-                try:
-                    pred = gen(masked)
-                finally:
-                    gen.clone_output = keep
-            else:
-                pred = gen(masked)
-        finally:
-            if keep_sparse is not None:
-                gen.sparse_tail = keep_sparse
+        B = image_hwc.shape[0]
+        # the paste reads pred only under the mask, as the blend does: the sparse-tail plans
+        pred = self._generate_u8((B, 4, int(Hp), int(Wp)), image_hwc.device, True,
+                                 lambda masked: ex.lib.crop_compose_u8(image_hwc, mask, sizes, rects, L.view(masked), B, binarize, st))
         ex.lib.crop_paste_u8(image_hwc, mask, sizes, rects, L.view(pred), out_u8, B, binarize, st)
         return out_u8
 

@@ -107,6 +107,10 @@ CASES = {
     'rows-1030x1028': (1030, 1028, [(1030, 1028, 258, 257)]),
     # (beyond the issue's table) the byte path of the row-wise form: a row of more than one workgroup whose last work item is partial
     'rows-bytes-13x1027': (13, 1027, [(13, 1027, 4, 257)]),
+    # the row-wise form's workgroup decode (chunk / row group / image) on a batch: 193 items per row, two row groups per slot (the second one
+    # partial), an empty slot between two images, the last image smaller than its slot -- in the dword form and, at Ws = 771, in the byte form
+    'rows-batch-one-empty': (6, 772, [(6, 772, 3, 386), None, (5, 770, 2, 385)]),
+    'rows-bytes-batch-one-empty': (6, 771, [(6, 771, 3, 386), None, (5, 770, 2, 385)]),
 }
 MASKS = ('random', 'zero', 'full')
 LAYOUTS = ('plain', 'view')
