@@ -647,6 +647,34 @@ int lama_crop_compose_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8
 int lama_crop_paste_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects, int32_t Hs,
                            int32_t Ws, const lama_tensor* pred, uint8_t* out_hwc, int32_t batch, int32_t binarize);
 
+/* ---- (added to v112 without a version bump: new symbols only, nothing else changes) crop_max_side: the two ends of a crop_to_mask step whose
+ * window is SHRUNK by a per-image integer k for the generator.  THIS OUTPUT HAS NO COUNTERPART IN THE REFERENCE: it is this engine's own
+ * definition, restated in numpy and pinned bit for bit / byte for byte by tests/crop_shrink_util.py (and, where k divides the window, against
+ * lama_resize_u8_fwd with factor 1 / k and lama_paste_back_u8_fwd on host-cropped slots).
+ * Slots, src_sizes and rects [B][4] = (y0, x0, ch, cw) are those of lama_crop_*_u8_fwd; shrinks: device int32 [B] = k, 1 .. 16.  For image b let
+ * C, M be the window, dh = ceil(ch / k), dw = ceil(cw / k).
+ *   lama_crop_shrink_compose_u8_fwd: out fp32 [B,4,Hp,Wp] = cat(S * (1 - m), m) after np.pad(mode='symmetric') of the dh x dw planes at the
+ *     bottom / right up to (Hp, Wp) (periodic).  S[y, x] is the integer shrink of lama_resize_u8_fwd on C: each byte / 255.f; a whole k x k box
+ *     summed in row-major order, four at a time as acc + (((a + b) + c) + d), the remainder one by one, times (float)(1.0 / (k * k)); a box cut
+ *     by the window's bottom or right edge is the row-major sum of the pixels inside it / (float)count.  The MASK is the MAX of the box's bytes,
+ *     cut boxes included: mu = max, m = mu > 0 (binarize != 0) or mu / 255.f.  This differs from dataset.scale_factor's INTER_NEAREST on
+ *     purpose: a one-pixel stroke must not vanish from the generator's mask while the paste still replaces it -- which is also why dh is a
+ *     ceiling: every window pixel lies in a box.  The window is read once, 16 bytes are written per pixel of the view.
+ *   lama_crop_shrink_paste_u8_fwd: out_hwc[b, :h, :w] = the source bytes, and inside the window, where the mask byte is not 0, the bytes
+ *     lama_paste_back_u8_fwd gives for (C, M, lowres[b], (dh, dw)) on window coordinates (y - y0, x - x0), sy = (float)dh / (float)ch: THE
+ *     PIXELS UNDER THE MASK ARE A k-FOLD BILINEAR UPSAMPLING OF THE PREDICTION.  lowres, fp32 [B,3,Hp,Wp], is read only inside [:dh, :dw] and
+ *     only for such pixels.  Slot bytes outside h x w are written as 0.
+ * A rect that does not fit -- the conditions of lama_crop_*_u8_fwd with dh > Hp, dw > Wp in place of ch > Hp, cw > Wp -- or a k outside 1 .. 16
+ * behaves as an empty slot in both entries.  Everything is device data: nothing is read or written out of bounds.  Dword accesses to the slots
+ * where Ws % 4 == 0 and the slot pointers are 4-byte aligned (any x0), float4 stores to a view as for lama_crop_compose_u8_fwd; byte / scalar
+ * accesses otherwise.  No floating-point contraction.  One launch each, no workspace, no atomics, no LDS: asynchronous and hipGraph-capturable.
+ * Errors as for lama_crop_*_u8_fwd, and LAMA_ERR_BAD_ARG for a null shrinks.  Nothing is launched on an error. */
+int lama_crop_shrink_compose_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects,
+                                    const int32_t* shrinks, int32_t Hs, int32_t Ws, const lama_tensor* out, int32_t batch, int32_t binarize);
+int lama_crop_shrink_paste_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects,
+                                  const int32_t* shrinks, int32_t Hs, int32_t Ws, const lama_tensor* lowres, uint8_t* out_hwc, int32_t batch,
+                                  int32_t binarize);
+
 /* ---- (added to v112 without a version bump: new symbols only, nothing else changes) the zlib stream of a PNG's IDAT, made on the device from u8
  * HWC slots.  A PNG encoder owes the decoder the pixels, not particular bytes: THE STREAM IS THIS ENGINE'S OWN DEFINITION, pinned byte for byte by
  * tests/png_ref.py::deflate_ref.  image_hwc [batch][Hs][Ws][channels] u8 slots, each image's h x w pixels in the top-left corner; sizes: device int32

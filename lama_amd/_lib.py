@@ -206,6 +206,10 @@ class LamaLib:
         L.lama_crop_compose_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, i32, i32]
         L.lama_crop_paste_u8_fwd.restype = C.c_int
         L.lama_crop_paste_u8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, T, vp, i32, i32]
+        L.lama_crop_shrink_compose_u8_fwd.restype = C.c_int
+        L.lama_crop_shrink_compose_u8_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, T, i32, i32]
+        L.lama_crop_shrink_paste_u8_fwd.restype = C.c_int
+        L.lama_crop_shrink_paste_u8_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, T, vp, i32, i32]
         L.lama_png_deflate_bound.restype, L.lama_png_deflate_bound.argtypes = sz, [i32] * 4
         L.lama_png_deflate_workspace_bytes.restype, L.lama_png_deflate_workspace_bytes.argtypes = C.c_int, [i32] * 5 + [C.POINTER(sz)]
         L.lama_png_deflate_u8_fwd.restype = C.c_int
@@ -642,6 +646,27 @@ class LamaLib:
         self.check(self._l.lama_crop_paste_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
                                                   int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(pred), out_hwc.data_ptr(), batch,
                                                   int(bool(binarize))), 'lama_crop_paste_u8_fwd')
+
+    def crop_shrink_compose_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, shrinks: torch.Tensor,
+                               out: Tensor4, batch: int, binarize: bool = True, stream: int = 0):
+        """lama_crop_shrink_compose_u8_fwd (no counterpart in the reference): the generator's input [B,4,Hp,Wp] fp32 from the window ``rects`` of each
+        u8 source slot, shrunk by the integer ``shrinks`` [B] = k (1 .. 16): k x k box means of the image (resize_u8's integer-shrink arithmetic),
+        the MAX of each box's mask bytes, symmetric padding of the ceil(ch / k) x ceil(cw / k) planes."""
+        self._u8_slot_operands('crop_shrink_compose_u8', image_hwc, mask, batch, [('src_sizes', src_sizes, 2), ('rects', rects, 4), ('shrinks', shrinks, 1)])
+        self.check(self._l.lama_crop_shrink_compose_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
+                                                           shrinks.data_ptr(), int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(out), batch,
+                                                           int(bool(binarize))), 'lama_crop_shrink_compose_u8_fwd')
+
+    def crop_shrink_paste_u8(self, image_hwc: torch.Tensor, mask: torch.Tensor, src_sizes: torch.Tensor, rects: torch.Tensor, shrinks: torch.Tensor,
+                             lowres: Tensor4, out_hwc: torch.Tensor, batch: int, binarize: bool = True, stream: int = 0):
+        """lama_crop_shrink_paste_u8_fwd: ``out_hwc`` [B,Hs,Ws,3] u8 (another buffer than ``image_hwc``) = the source slots with, inside each window
+        and under the mask, the bytes ``paste_back_u8`` gives for the cropped arrays and ``lowres`` [B,3,Hp,Wp] (valid in [:ceil(ch / k),
+        :ceil(cw / k)]): a k-fold bilinear upsampling of the generator's output."""
+        self._u8_slot_operands('crop_shrink_paste_u8', image_hwc, mask, batch, [('src_sizes', src_sizes, 2), ('rects', rects, 4), ('shrinks', shrinks, 1)],
+                               out_hwc)
+        self.check(self._l.lama_crop_shrink_paste_u8_fwd(stream, image_hwc.data_ptr(), mask.data_ptr(), src_sizes.data_ptr(), rects.data_ptr(),
+                                                         shrinks.data_ptr(), int(image_hwc.shape[1]), int(image_hwc.shape[2]), C.byref(lowres),
+                                                         out_hwc.data_ptr(), batch, int(bool(binarize))), 'lama_crop_shrink_paste_u8_fwd')
 
     def png_deflate_bound(self, h: int, w: int, channels: int = 3, chunk_bytes: int = 0) -> int:
         """lama_png_deflate_bound: the most bytes the stream of one h x w image can take (0: empty, or arguments the encoder refuses)."""

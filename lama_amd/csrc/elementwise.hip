@@ -751,6 +751,7 @@ struct PastePolicy {
     const char* low;
     long long plane;             // bytes of one low-resolution plane, < 2^32
     unsigned rowb;
+    __device__ __forceinline__ PastePolicy() {}          // (ShrinkPastePolicy fills the state from a window)
     __device__ __forceinline__ PastePolicy(const PasteParams& p, int b) {
 #pragma clang fp contract(off)
         h = p.src_sizes[2 * b]; w = p.src_sizes[2 * b + 1]; dh = p.dst_sizes[2 * b]; dw = p.dst_sizes[2 * b + 1];
@@ -910,6 +911,203 @@ struct CropPastePolicy : CropRect {
 };
 template <bool VEC, bool ROW> __global__ __launch_bounds__(U8_THREADS) void crop_paste_u8_kernel(CropParams p) {
     u8_slot_walk<VEC, ROW, CropPastePolicy>(p);
+}
+
+// ---- crop_max_side: the two ends of a crop_to_mask step whose window is SHRUNK by a per-image integer k (1 .. LAMA_SHRINK_MAX) for the generator --
+// THIS OUTPUT HAS NO COUNTERPART IN THE REFERENCE: it is this engine's own definition (tests/crop_shrink_util.py restates it in numpy).  With
+// C, M the window of image b, dh = ceil(ch / k), dw = ceil(cw / k):
+//   crop_shrink_compose_u8_kernel  out = cat(S * (1 - m), m) after the symmetric padding of the dh x dw planes up to (Hp, Wp).  S is the integer
+//     shrink of resize_u8_kernel on C, the same operations in the same order: a whole k x k box is summed row-major, four pixels at a time as
+//     acc + (((a + b) + c) + d), the rest one by one, times float32(1 / k^2); a box cut by the window's bottom / right edge is that kernel's
+//     border loop, the row-major sum of the pixels inside over their count.  The MASK is the MAX of the box's bytes, cut boxes included (not
+//     INTER_NEAREST as dataset.scale_factor: a one-pixel stroke must stay a hole for the generator while the paste still replaces it; dh is a
+//     ceiling so that every window pixel lies in a box); m = max > 0 (binarize) or max / 255.f.
+//   crop_shrink_paste_u8_kernel    paste_back_u8_kernel's bytes for (C, M, lowres, (dh, dw)) on window coordinates (y - y0, x - x0), the source
+//     bytes everywhere else: the pixels under the mask are a k-fold bilinear UPSAMPLING of the generator's output.  u8_slot_walk with the window
+//     test in front of PastePolicy's gather.
+// A work item of the compose is four consecutive pixels of a row of the padded low-resolution view (u8_item, a float4 store per plane): its four
+// boxes are one run of 12 k bytes per source row, neighbouring lanes read neighbouring runs, the window is read once and nothing goes through an
+// fp32 image / mask in memory.  Where the slots take dword accesses the run is read as aligned dwords, whatever x0 is (ShrinkDwords); byte by
+// byte otherwise.  k is uniform in a workgroup.  No LDS, no atomics, no workspace.
+#define LAMA_SHRINK_MAX 16       // (1.0 / (1.0 / k) == k in fp64 up to 48: the pin against the host's resize with factor 1 / k relies on it)
+struct ShrinkParams : CropParams {   // (pred: the low-resolution result [B,3,Hp,Wp]; Hp, Wp: the padded LOW-RESOLUTION view)
+    const int32_t* shrinks;      // [B] = k
+    float inv_area[LAMA_SHRINK_MAX + 1];   // float32(1.0 / (k * k)), rounded once from fp64 on the host as resize_u8's inv_area is
+};
+struct ShrinkRect : CropRect {
+    int k, dh, dw;
+};
+// crop_rect_load's conditions with the low-resolution size in place of the window's, and k in 1 .. LAMA_SHRINK_MAX
+__device__ __forceinline__ ShrinkRect shrink_rect_load(const ShrinkParams& p, int b) {
+    ShrinkRect r;
+    r.h = p.src_sizes[2 * b]; r.w = p.src_sizes[2 * b + 1];
+    r.y0 = p.rects[4 * b]; r.x0 = p.rects[4 * b + 1]; r.ch = p.rects[4 * b + 2]; r.cw = p.rects[4 * b + 3];
+    r.k = p.shrinks[b];
+    r.ok = r.h > 0 && r.w > 0 && r.h <= p.Hs && r.w <= p.Ws && r.ch >= 1 && r.cw >= 1 && r.ch <= r.h && r.cw <= r.w && r.y0 >= 0 && r.x0 >= 0 &&
+           r.y0 <= r.h - r.ch && r.x0 <= r.w - r.cw && r.k >= 1 && r.k <= LAMA_SHRINK_MAX;
+    r.dh = r.ok ? (r.ch - 1) / r.k + 1 : 0; r.dw = r.ok ? (r.cw - 1) / r.k + 1 : 0;
+    r.ok = r.ok && r.dh <= p.Hp && r.dw <= p.Wp;
+    return r;
+}
+// The source pixels of one box row in x order, byte by byte ...
+struct ShrinkBytes {
+    const uint8_t* pi;
+    const uint8_t* pm;
+    __device__ __forceinline__ void row(const uint8_t* img, const uint8_t* msk, long long px) { pi = img + px * 3; pm = msk + px; }
+    __device__ __forceinline__ void next(float (&t)[3], uint32_t& mu) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c] = rz_px(pi + c);
+        const uint32_t m = *pm;
+        mu = mu > m ? mu : m;
+        pi += 3; ++pm;
+    }
+};
+// ... and from the aligned dwords that hold them (the slots take dword accesses, so every dword that holds a byte of a slot lies inside it): a
+// row starts `skip` bytes into its first dword, a dword is loaded only when the next pixel needs a byte of it.  Lanes of one j differ by
+// multiples of 12 k bytes (4 k of mask), so a wave refills in step.
+struct ShrinkDwords {
+    const ei_u32* wi;
+    const ei_u32* wm;
+    unsigned si, sm, vi, vm;     // bytes to skip in the next dword / bytes held
+    uint64_t bi;
+    uint32_t bm;
+    __device__ __forceinline__ void row(const uint8_t* img, const uint8_t* msk, long long px) {
+        const uint8_t* a = img + px * 3;
+        const uint8_t* m = msk + px;
+        si = (unsigned)(reinterpret_cast<uintptr_t>(a) & 3); sm = (unsigned)(reinterpret_cast<uintptr_t>(m) & 3);
+        wi = reinterpret_cast<const ei_u32*>(a - si); wm = reinterpret_cast<const ei_u32*>(m - sm);
+        vi = vm = 0u; bi = 0ull; bm = 0u;
+    }
+    __device__ __forceinline__ void next(float (&t)[3], uint32_t& mu) {
+        while (vi < 3u) {
+            const uint64_t w = (uint64_t)(*wi++) >> (8u * si);
+            bi |= w << (8u * vi);
+            vi += 4u - si; si = 0u;
+        }
+        if (vm == 0u) {
+            bm = *wm++ >> (8u * sm);
+            vm = 4u - sm; sm = 0u;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c] = (float)(uint32_t)((bi >> (8 * c)) & 255u) / 255.0f;
+        const uint32_t m = bm & 255u;
+        mu = mu > m ? mu : m;
+        bi >>= 24; vi -= 3u; bm >>= 8; --vm;
+    }
+};
+// S and the mask's max of the box of bh x bw pixels (k x k: whole) whose top-left pixel is `base`; rs: pixels per slot row
+template <class Stream> __device__ __forceinline__ void shrink_box(const uint8_t* img, const uint8_t* msk, long long base, long long rs, int bh, int bw, int k,
+                                                                   float inv_area, float (&v)[3], uint32_t& mu) {
+#pragma clang fp contract(off)
+    Stream st;
+    v[0] = v[1] = v[2] = 0.0f;
+    mu = 0u;
+    st.row(img, msk, base);
+    if (bh == k && bw == k) {                             // resizeAreaFast: the box sy-major, four at a time, * float32(1 / area)
+        const int area = k * k;
+        int n = 0, sx = 0;
+        float t[4][3];
+        for (; n <= area - 4; n += 4) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                st.next(t[j], mu);
+                if (++sx == k) { sx = 0; base += rs; st.row(img, msk, base); }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = v[c] + (((t[0][c] + t[1][c]) + t[2][c]) + t[3][c]);
+        }
+        for (; n < area; ++n) {
+            st.next(t[0], mu);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = v[c] + t[0][c];
+            if (++sx == k) { sx = 0; base += rs; st.row(img, msk, base); }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = v[c] * inv_area;
+    } else {                                              // its border loop: row-major sum of the pixels inside the window / their count
+        float t[3];
+        for (int yy = 0; yy < bh; ++yy) {
+            for (int xx = 0; xx < bw; ++xx) {
+                st.next(t, mu);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] = v[c] + t[c];
+            }
+            base += rs;
+            st.row(img, msk, base);
+        }
+        const float cnt = (float)(bh * bw);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = v[c] / cnt;
+    }
+}
+template <bool VEC> __global__ __launch_bounds__(U8_THREADS) void crop_shrink_compose_u8_kernel(ShrinkParams p) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x / p.chunks, chunk = blockIdx.x - b * p.chunks;
+    const int tid = threadIdx.x;
+    const ShrinkRect r = shrink_rect_load(p, b);
+    // (a rect that does not fit reads pixel (0, 0) of its slot and writes zeros)
+    const int k = r.ok ? r.k : 1, y0 = r.ok ? r.y0 : 0, x0 = r.ok ? r.x0 : 0, ch = r.ok ? r.ch : 1, cw = r.ok ? r.cw : 1;
+    const int dh = r.ok ? r.dh : 1, dw = r.ok ? r.dw : 1;
+    const float inv_area = p.inv_area[k];
+    const long long slot = (long long)b * p.Hs * p.Ws;
+    const uint8_t* img = p.img + slot * 3;
+    const uint8_t* msk = p.mask + slot;
+    const long long hw = (long long)p.Hp * p.Wp;
+    float* out = p.out + b * p.out_bs;
+    const int nitems = p.Hp * p.qpr;
+#pragma unroll 1
+    for (int it = 0; it < U8_UNROLL; ++it) {
+        int y, q;
+        if (!u8_item(chunk, it, tid, nitems, p.qpr, y, q)) continue;
+        const int by = ew_symmetric(y, dh) * k, bh = k < ch - by ? k : ch - by;
+        const long long row = (long long)(y0 + by) * p.Ws + x0;
+        float v[4][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = 4 * q + j < p.Wp ? 4 * q + j : p.Wp - 1;                   // (a column past the view repeats the last one; it is never stored)
+            const int bx = ew_symmetric(x, dw) * k, bw = k < cw - bx ? k : cw - bx;
+            float s[3], m = 0.0f;
+            uint32_t mu;
+            if (VEC) shrink_box<ShrinkDwords>(img, msk, row + bx, p.Ws, bh, bw, k, inv_area, s, mu);
+            else shrink_box<ShrinkBytes>(img, msk, row + bx, p.Ws, bh, bw, k, inv_area, s, mu);
+            if (r.ok) m = p.binarize ? (mu > 0u ? 1.0f : 0.0f) : (float)mu / 255.0f;
+            else s[0] = s[1] = s[2] = 0.0f;
+            const float km = 1.0f - m;
+            v[0][j] = s[0] * km; v[1][j] = s[1] * km; v[2][j] = s[2] * km; v[3][j] = m;
+        }
+        ei_store4(out + (long long)y * p.Wp + 4 * q, hw, 4 * q, p.Wp, p.vec_st != 0, v);
+    }
+}
+// out = the source bytes, with paste_back_u8_kernel's bytes for (C, M, lowres, (dh, dw)) inside the window; zeros outside h x w
+struct ShrinkPastePolicy : PastePolicy {
+    typedef ShrinkParams Params;
+    struct Row : PastePolicy::Row {
+        bool in;                 // the row crosses the window
+    };
+    int y0, x0, ch, cw;
+    __device__ __forceinline__ ShrinkPastePolicy(const ShrinkParams& p, int b) {
+#pragma clang fp contract(off)
+        const ShrinkRect r = shrink_rect_load(p, b);
+        ok = r.ok; h = r.h; w = r.w; dh = r.dh; dw = r.dw;
+        y0 = r.y0; x0 = r.x0; ch = r.ch; cw = r.cw;
+        sy = ok ? (float)dh / (float)ch : 0.0f; sx = ok ? (float)dw / (float)cw : 0.0f;
+        low = reinterpret_cast<const char*>(p.pred + (long long)b * p.pred_bs);
+        plane = 4ll * p.Hp * p.Wp;
+        rowb = 4u * (unsigned)p.Wp;
+        binarize = p.binarize;
+    }
+    __device__ __forceinline__ Row row(int y) const {
+        Row r;
+        r.in = y >= y0 && y - y0 < ch;
+        static_cast<PastePolicy::Row&>(r) = PastePolicy::row(r.in ? y - y0 : 0);
+        return r;
+    }
+    __device__ __forceinline__ void pixel(const Row& r, int x, uint32_t mu, uint32_t (&sb)[3]) const {
+        if (r.in && x >= x0 && x - x0 < cw) PastePolicy::pixel(r, x - x0, mu, sb);
+    }
+};
+template <bool VEC, bool ROW> __global__ __launch_bounds__(U8_THREADS) void crop_shrink_paste_u8_kernel(ShrinkParams p) {
+    u8_slot_walk<VEC, ROW, ShrinkPastePolicy>(p);
 }
 
 struct AffineParams {
@@ -1302,6 +1500,52 @@ extern "C" int lama_crop_paste_u8_fwd(void* stream, const uint8_t* image_hwc, co
     U8Plan pl;
     if (const int e = u8_walk_plan(p, Hs, Ws, batch, true, pl)) return e;
     U8_LAUNCH(crop_paste_u8_kernel, pl, stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+// crop_max_side: the same two ends with the window shrunk by shrinks[b] for the generator: see crop_shrink_compose_u8_kernel
+static void shrink_params(ShrinkParams& p, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes, const int32_t* rects,
+                          const int32_t* shrinks, int32_t Hs, int32_t Ws, const lama_tensor* view, int32_t binarize) {
+    memset(&p, 0, sizeof(p));
+    p.img = image_hwc; p.mask = mask; p.src_sizes = src_sizes; p.rects = rects; p.shrinks = shrinks;
+    p.Hs = Hs; p.Ws = Ws; p.Hp = view->H; p.Wp = view->W; p.binarize = binarize != 0;
+    for (int k = 1; k <= LAMA_SHRINK_MAX; ++k) p.inv_area[k] = (float)(1.0 / ((double)k * k));
+}
+extern "C" int lama_crop_shrink_compose_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes,
+                                               const int32_t* rects, const int32_t* shrinks, int32_t Hs, int32_t Ws, const lama_tensor* out,
+                                               int32_t batch, int32_t binarize) {
+    if (!image_hwc || !mask || !src_sizes || !rects || !shrinks || !out || !out->ptr) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0 || out->C != 4 || out->H <= 0 || out->W <= 0) return LAMA_ERR_BAD_ARG;
+    if (out->batch_stride < (int64_t)4 * out->H * out->W) return LAMA_ERR_BAD_ARG;
+    if (!all_f32({out})) return LAMA_ERR_UNSUPPORTED;
+    if ((uintptr_t)out->ptr & 3) return LAMA_ERR_BAD_ARG;
+    ShrinkParams p;
+    shrink_params(p, image_hwc, mask, src_sizes, rects, shrinks, Hs, Ws, out, binarize);
+    p.out = (float*)out->ptr; p.out_bs = out->batch_stride;
+    U8Plan pl;                                                        // the items of the padded low-resolution view, never by rows
+    if (const int e = u8_walk_plan(p, out->H, out->W, batch, false, pl)) return e;
+    p.vec_ld = pl.vec;
+    p.vec_st = out->W % 4 == 0 && out->batch_stride % 4 == 0 && !((uintptr_t)out->ptr & 15);
+    if (pl.vec) hipLaunchKernelGGL(crop_shrink_compose_u8_kernel<true>, dim3(pl.nwg), dim3(U8_THREADS), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(crop_shrink_compose_u8_kernel<false>, dim3(pl.nwg), dim3(U8_THREADS), 0, (hipStream_t)stream, p);
+    LAMA_CHECK_LAUNCH();
+    return LAMA_OK;
+}
+
+extern "C" int lama_crop_shrink_paste_u8_fwd(void* stream, const uint8_t* image_hwc, const uint8_t* mask, const int32_t* src_sizes,
+                                             const int32_t* rects, const int32_t* shrinks, int32_t Hs, int32_t Ws, const lama_tensor* lowres,
+                                             uint8_t* out_hwc, int32_t batch, int32_t binarize) {
+    if (!image_hwc || !mask || !src_sizes || !rects || !shrinks || !out_hwc || out_hwc == image_hwc) return LAMA_ERR_BAD_ARG;
+    if (batch <= 0 || Hs <= 0 || Ws <= 0) return LAMA_ERR_BAD_ARG;
+    if (const int e = u8_check_rgb_view(lowres)) return e;
+    ShrinkParams p;
+    shrink_params(p, image_hwc, mask, src_sizes, rects, shrinks, Hs, Ws, lowres, binarize);
+    p.pred = (const float*)lowres->ptr; p.pred_bs = lowres->batch_stride;
+    p.out_u8 = out_hwc;
+    U8Plan pl;
+    if (const int e = u8_walk_plan(p, Hs, Ws, batch, true, pl)) return e;
+    U8_LAUNCH(crop_shrink_paste_u8_kernel, pl, stream, p);
     LAMA_CHECK_LAUNCH();
     return LAMA_OK;
 }

@@ -4,7 +4,7 @@
     python -m lama_amd.predict model.path=<dir> indir=<dir> outdir=<dir> \
         [model.checkpoint=best.ckpt] [dataset.img_suffix=.png] [dataset.pad_out_to_modulo=8] [out_ext=.png] \
         [batch_size=8] [precision=f16x3|bf16x3|f32] [io_threads=8] [dataset.scale_factor=F [paste_back=true]] [device_png=true] \
-        [crop_to_mask=true [crop_margin=128] [crop_step=128]] \
+        [crop_to_mask=true [crop_margin=128] [crop_step=128] [crop_max_side=512]] \
         [device_jpeg=true [jpeg_quality=95] [jpeg_subsampling=420|444]]
     python -m torch.distributed.run --nproc-per-node N -m lama_amd.predict ...        # one process per GPU
 
@@ -16,6 +16,9 @@ is ``<mask path up to '_mask'><img_suffix>`` (``evaluation/data.py:59-62``), the
 with the pixels under the mask taken from the scaled prediction, resampled bilinearly on the device (lama_paste_back_u8_fwd).
 ``crop_to_mask=true`` (another output of this driver's own) runs the generator on a window around each mask (``crop_rect``) at the source resolution
 and writes the SOURCE image with the window's inpainted pixels pasted in on the device (lama_crop_compose_u8_fwd / lama_crop_paste_u8_fwd).
+``crop_max_side=N`` (with ``crop_to_mask``; 0 = off; this driver's own too) shrinks a window whose padded size would exceed N pixels a side by the
+smallest integer k that makes it fit (``crop_rect_limited``: box means of the image, the MAX of each box's mask bytes) and pastes the k-fold
+bilinear upsampling of the prediction under the mask (lama_crop_shrink_compose_u8_fwd / lama_crop_shrink_paste_u8_fwd); windows that fit are served as without it.
 
 What differs from the reference's batch-1 Python loop: images are padded to ``pad_out_to_modulo`` and *bucketed by
 padded shape*, each bucket is cut into batches, batches are dealt round-robin to the ranks (one process per GPU,
@@ -52,7 +55,10 @@ DEFAULTS = {'model.checkpoint': 'best.ckpt', 'dataset.img_suffix': '.png', 'data
             'device_jpeg': False, 'jpeg_quality': 95, 'jpeg_subsampling': '420',
             # extension: the generator runs on a window around each mask's bounding box (crop_rect: the box + crop_margin a side, rounded up to
             # crop_step) at native resolution, and the result is pasted into the source image on the device (lama_crop_paste_u8_fwd)
-            'crop_to_mask': False, 'crop_margin': 128, 'crop_step': 128}
+            'crop_to_mask': False, 'crop_margin': 128, 'crop_step': 128,
+            # extension (with crop_to_mask): a window whose padded size exceeds crop_max_side is shrunk by the smallest integer k that fits
+            # (crop_rect_limited) for the generator and the prediction is upsampled under the mask (lama_crop_shrink_*_u8_fwd); 0: no limit
+            'crop_max_side': 0}
 jpeg_from_scan = ljpeg.jpeg_from_scan
 JPEG_OUT_STRIDE = None      # test hook: bytes per scan slot of the device_jpeg steps (None: the slot's raw byte count)
 
@@ -75,7 +81,7 @@ REFINER_DEFAULTS = {'refiner.gpu_ids': '0,', 'refiner.modulo': 8, 'refiner.n_ite
 STRING_KEYS = {'model.path', 'model.checkpoint', 'indir', 'outdir', 'device', 'dataset.kind', 'dataset.img_suffix', 'out_ext', 'out_key',
                'precision', 'refiner.gpu_ids', 'jpeg_subsampling'}
 BOOL_KEYS = {'refine', 'profile', 'paste_back', 'device_png', 'device_jpeg', 'crop_to_mask'}
-INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'jpeg_quality', 'crop_margin', 'crop_step', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
+INT_KEYS = {'dataset.pad_out_to_modulo', 'batch_size', 'io_threads', 'jpeg_quality', 'crop_margin', 'crop_step', 'crop_max_side', 'refiner.modulo', 'refiner.n_iters', 'refiner.min_side', 'refiner.max_scales',
             'refiner.px_budget', 'refiner.batch_size'}
 FLOAT_KEYS = {'refiner.lr', 'dataset.scale_factor'}
 
@@ -147,8 +153,11 @@ def parse_overrides(argv: Sequence[str]) -> Dict[str, object]:
                              f"(a rectangle of raw prediction inside the source image is not a result)")
         try:
             check_crop_options(cfg['crop_margin'], cfg['crop_step'], cfg['dataset.pad_out_to_modulo'])
+            check_crop_max_side(cfg['crop_max_side'], cfg['crop_margin'], cfg['crop_step'], cfg['dataset.pad_out_to_modulo'])
         except L.LamaError as e:
             raise SystemExit(f'crop_to_mask=true: {e}')
+    elif cfg['crop_max_side']:
+        raise SystemExit(f"crop_max_side={cfg['crop_max_side']!r} needs crop_to_mask=true: it limits the window that option inpaints")
     if cfg['device_png'] and cfg['device_jpeg']:
         raise SystemExit('device_jpeg=true with device_png=true: a step ends with one encoder, and out_ext names one format')
     if cfg['device_png']:
@@ -396,6 +405,52 @@ def rect_fits(rect, h: int, w: int, Hs: int, Ws: int, Hp: int, Wp: int) -> bool:
     """The conditions lama_crop_compose_u8_fwd / lama_crop_paste_u8_fwd put on a window (y0, x0, ch, cw) of an h x w image in an Hs x Ws slot."""
     y0, x0, ch, cw = (int(v) for v in rect[:4])
     return (ch >= 1 and cw >= 1 and y0 >= 0 and x0 >= 0 and y0 + ch <= h and x0 + cw <= w and ch <= Hp and cw <= Wp and 0 < h <= Hs and 0 < w <= Ws)
+
+
+# ---- crop_max_side: a window too large for the generator is shrunk by an integer k (this driver's own too) ------------------------------------------
+CROP_SHRINK_MAX = 16     # the kernels' largest k (1.0 / (1.0 / k) == k holds in fp64 up to 48: the pin against the host's resize relies on it)
+
+
+def check_crop_max_side(max_side: int, margin: int, step: int, pad_mod: int):
+    """``crop_max_side`` is 0 (no limit) or a multiple of ``pad_out_to_modulo`` of at least 2 ``crop_margin`` + ``crop_step`` rounded up to
+    ``crop_step``: below that no shrink k can ever make a window fit (margin and step are measured in generator pixels)."""
+    mod = int(pad_mod) if pad_mod and int(pad_mod) > 1 else 1
+    max_side, margin, step = int(max_side), int(margin), int(step)
+    if max_side == 0:
+        return
+    least = (2 * margin + step + step - 1) // step * step
+    if max_side < 0 or max_side % mod or max_side < least:
+        raise L.LamaError(f'crop_max_side={max_side!r}: 0 (off) or a multiple of dataset.pad_out_to_modulo={pad_mod!r} of at least {least} '
+                          f'(2 crop_margin + crop_step, rounded up to crop_step)')
+
+
+def crop_rect_limited(mask_u8: np.ndarray, margin: int, step: int, pad_mod: int, max_side: int,
+                      kmax: int = CROP_SHRINK_MAX) -> Tuple[int, int, int, int, int, int, int, int, int]:
+    """The window of ``crop_to_mask`` under ``crop_max_side`` -> (y0, x0, ch, cw, k, dh, dw, Hp, Wp), integers only: for k = 1, 2, ... ``kmax`` the
+    window is ``crop_rect(mask, margin k, step k, pad_mod)`` (margin and step in generator pixels), the generator sees dh x dw = ceil(ch / k) x
+    ceil(cw / k) pixels padded to (Hp, Wp), and the first k with Hp, Wp <= ``max_side`` is taken -- k = 1: ``crop_rect``'s own window."""
+    check_crop_options(margin, step, pad_mod)
+    check_crop_max_side(max_side, margin, step, pad_mod)
+    margin, step, max_side, kmax = int(margin), int(step), int(max_side), int(kmax)
+    if max_side < 1 or not 1 <= kmax <= CROP_SHRINK_MAX:
+        raise L.LamaError(f'crop_rect_limited: crop_max_side={max_side!r} (a positive limit) and kmax={kmax!r} (1 .. {CROP_SHRINK_MAX})')
+    padded = (lambda n: ceil_modulo(n, pad_mod)) if pad_mod and pad_mod > 1 else (lambda n: n)
+    for k in range(1, kmax + 1):
+        y0, x0, ch, cw, _, _ = crop_rect(mask_u8, margin * k, step * k, pad_mod)
+        dh, dw = (ch + k - 1) // k, (cw + k - 1) // k
+        Hp, Wp = padded(dh), padded(dw)                   # (k = 1: crop_rect's own padded size)
+        if Hp <= max_side and Wp <= max_side:
+            return y0, x0, ch, cw, k, dh, dw, Hp, Wp
+    raise L.LamaError(f'crop_rect_limited: the {cw}x{ch} window of a {mask_u8.shape[1]}x{mask_u8.shape[0]} image is still {Wp}x{Hp} at the largest '
+                      f'shrink k={kmax}: larger than crop_max_side={max_side}')
+
+
+def shrink_rect_fits(rect, h: int, w: int, Hs: int, Ws: int, Hp: int, Wp: int) -> bool:
+    """The conditions lama_crop_shrink_compose_u8_fwd / lama_crop_shrink_paste_u8_fwd put on (y0, x0, ch, cw, k) of an h x w image in an Hs x Ws
+    slot with an (Hp, Wp) low-resolution view."""
+    y0, x0, ch, cw, k = (int(v) for v in rect[:5])
+    return (1 <= k <= CROP_SHRINK_MAX and ch >= 1 and cw >= 1 and y0 >= 0 and x0 >= 0 and y0 + ch <= h and x0 + cw <= w and
+            (ch + k - 1) // k <= Hp and (cw + k - 1) // k <= Wp and 0 < h <= Hs and 0 < w <= Ws)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -657,17 +712,28 @@ class HostFedStep:
     pixels up and down as in the ``scale_factor`` + ``paste_back`` form, and ``put`` takes a window (y0, x0, ch, cw) per image beside them (a
     pinned and a device ``rects`` array next to the sizes).  (Hp, Wp) is the padded size of the WINDOWS: the step is lama_crop_compose_u8_fwd, the
     generator call of the u8 form at that shape, lama_crop_paste_u8_fwd (model.forward_u8_crop) -- the u8 step on the cropped arrays, pasted into
-    the source by slicing, byte for byte.  ``crop_sizes`` are the source sizes, so both encoders work on the pasted result unchanged."""
+    the source by slicing, byte for byte.  ``crop_sizes`` are the source sizes, so both encoders work on the pasted result unchanged.
+
+    ``crop_shrink`` (crop_max_side; with ``crop``; no counterpart in the reference): ``put`` takes (y0, x0, ch, cw, k), and (Hp, Wp) is the padded size
+    of the windows SHRUNK by their k (ceil(ch / k) x ceil(cw / k)): the step is lama_crop_shrink_compose_u8_fwd (k x k box means, the max of each
+    box's mask bytes), the generator at that shape with its dense tail, lama_crop_shrink_paste_u8_fwd (model.forward_u8_crop_shrink): under the
+    mask the results hold the k-fold bilinear upsampling of the prediction.  Everything else is as with ``crop``."""
 
     def __init__(self, model, batch_size: int, Hp: int, Wp: int, device, *, drain: bool = True, binarize: bool = True, mode: str = 'auto',
                  u8_input: bool = True, tune: bool = True, out_key: str = 'inpainted', capture: bool = True, scale_factor: Optional[float] = None,
                  src_hw: Optional[Tuple[int, int]] = None, paste_back: bool = False, encode_png: bool = False,
                  encode_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420', jpeg_out_stride: Optional[int] = None,
-                 crop: bool = False):
+                 crop: bool = False, crop_shrink: bool = False):
         self.model, self.n, self.Hp, self.Wp = model, int(batch_size), int(Hp), int(Wp)
         # ``crop`` (crop_to_mask): the fourth input form -- the DECODED u8 originals in source slots of ``src_hw`` pixels plus a window per image;
         # (Hp, Wp) is the padded size of the WINDOWS, and the results are source slots
         self.crop = bool(crop)
+        # ``crop_shrink`` (crop_max_side): the crop form with a shrink k per window -- (Hp, Wp) is the padded LOW-RESOLUTION size of the windows
+        self.crop_shrink = bool(crop_shrink)
+        if self.crop_shrink and not self.crop:
+            raise L.LamaError('crop_shrink is a variant of the crop form: crop=True is needed')
+        if self.crop_shrink and not hasattr(model, 'forward_u8_crop_shrink'):
+            raise L.LamaError('crop_shrink needs model.forward_u8_crop_shrink')
         if self.crop:
             if scale_factor is not None:
                 raise L.LamaError('crop with scale_factor is not served: the window is inpainted at the source resolution')
@@ -725,6 +791,7 @@ class HostFedStep:
         self.u8_input = bool(u8_input) and hasattr(model, 'forward_u8') and self.scale is None and not self.crop
         self.h_dsizes = self.d_dsizes = None
         self.h_rects = self.d_rects = None
+        self.h_shrinks = self.d_shrinks = None
         if self.crop:
             self.h_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, **pin) for _ in range(2)]
             self.h_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, **pin) for _ in range(2)]
@@ -734,6 +801,9 @@ class HostFedStep:
             self.d_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, device=self.device) for _ in range(2)]
             self.d_sizes = [torch.zeros(self.n, 2, dtype=torch.int32, device=self.device) for _ in range(2)]
             self.d_rects = [torch.zeros(self.n, 4, dtype=torch.int32, device=self.device) for _ in range(2)]
+            if self.crop_shrink:
+                self.h_shrinks = [torch.zeros(self.n, dtype=torch.int32, **pin) for _ in range(2)]        # k: its window's shrink
+                self.d_shrinks = [torch.zeros(self.n, dtype=torch.int32, device=self.device) for _ in range(2)]
         elif self.scale is not None:
             self.h_img = [torch.zeros(self.n, self.Hs, self.Ws, 3, dtype=torch.uint8, **pin) for _ in range(2)]
             self.h_mask = [torch.zeros(self.n, self.Hs, self.Ws, dtype=torch.uint8, **pin) for _ in range(2)]
@@ -825,9 +895,16 @@ class HostFedStep:
             sz, rc = self.h_sizes[p].numpy(), self.h_rects[p].numpy()
             if image is None:
                 sz[j], rc[j] = (0, 0), (0, 0, 0, 0)
+                if self.crop_shrink:
+                    self.h_shrinks[p].numpy()[j] = 0
                 return
             h, w = image.shape[:2]
-            if rect is None or len(rect) < 4 or not rect_fits(rect, h, w, self.Hs, self.Ws, self.Hp, self.Wp):       # (the kernels cannot report it)
+            if self.crop_shrink:                                                                    # ``crop_shrink``: rect = (y0, x0, ch, cw, k)
+                if rect is None or len(rect) < 5 or not shrink_rect_fits(rect, h, w, self.Hs, self.Ws, self.Hp, self.Wp):
+                    raise L.LamaError(f'window and shrink {None if rect is None else tuple(int(v) for v in rect[:5])} of a {h}x{w} image do not fit it, '
+                                      f'the source slot {self.Hs}x{self.Ws} or the low-resolution bucket {self.Hp}x{self.Wp}')
+                self.h_shrinks[p].numpy()[j] = int(rect[4])
+            elif rect is None or len(rect) < 4 or not rect_fits(rect, h, w, self.Hs, self.Ws, self.Hp, self.Wp):     # (the kernels cannot report it)
                 raise L.LamaError(f'window {None if rect is None else tuple(int(v) for v in rect[:4])} of a {h}x{w} image does not fit it, the source '
                                   f'slot {self.Hs}x{self.Ws} or the bucket {self.Hp}x{self.Wp}')
             self.h_img[p].numpy()[j, :h, :w] = image
@@ -922,6 +999,10 @@ class HostFedStep:
         lib = self.model.generator._exec.lib
         if self.crop:                                                                              # the same step on each image's window, pasted into the source slots
             with torch.no_grad():
+                if self.crop_shrink:                                                               # ... shrunk by k for the generator, upsampled under the mask
+                    self.model.forward_u8_crop_shrink(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.d_rects[p], self.d_shrinks[p], self.u8[p],
+                                                      self.Hp, self.Wp, binarize=self.binarize)
+                    return
                 self.model.forward_u8_crop(self.d_img[p], self.d_mask[p], self.d_sizes[p], self.d_rects[p], self.u8[p], self.Hp, self.Wp, binarize=self.binarize)
             return
         if self.u8_input:                                                                          # bin/predict.py:82-92 in two elementwise launches + the generator
@@ -960,6 +1041,8 @@ class HostFedStep:
             self.d_dsizes[q].copy_(self.h_dsizes[q], non_blocking=non_blocking)
         if self.d_rects is not None:
             self.d_rects[q].copy_(self.h_rects[q], non_blocking=non_blocking)
+        if self.d_shrinks is not None:
+            self.d_shrinks[q].copy_(self.h_shrinks[q], non_blocking=non_blocking)
 
     def _body(self, p: int):
         q = 1 - p
@@ -1086,7 +1169,7 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
             pad_mod: int = 8, batch_size: int = 8, out_ext: str = '.png', device='cuda', rank: int = 0, world: int = 1,
             dist=None, io_threads: int = 8, out_key: str = 'inpainted', scale_factor: Optional[float] = None, paste_back: bool = False,
             device_png: bool = False, device_jpeg: bool = False, jpeg_quality: int = 95, jpeg_subsampling='420',
-            crop_to_mask: bool = False, crop_margin: int = 128, crop_step: int = 128) -> int:
+            crop_to_mask: bool = False, crop_margin: int = 128, crop_step: int = 128, crop_max_side: int = 0) -> int:
     """Run every (mask, image) pair through ``model`` and write the results (rank 0).  Returns the number of images written.
     ``scale_factor`` = ``dataset.scale_factor`` (evaluation/data.py:74-77): every image / mask is rescaled before the padding -- on the device, by
     the first launch of the step, which is fed with the decoded u8 originals (lama_resize_u8_fwd) -- and the results have the rescaled size.
@@ -1104,6 +1187,10 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
     resolution, and the results are the source images with the window's inpainted pixels pasted in on the device (lama_crop_paste_u8_fwd) -- the u8
     step on the cropped arrays, pasted by slicing.  The windows need the masks' pixels, so a pre-pass decodes every mask on the I/O pool before the
     buckets -- keyed by the windows' padded size -- are formed; every rank runs the whole pre-pass and so arrives at the same buckets.
+    ``crop_max_side`` (with ``crop_to_mask``; 0 = off; no such output in the reference either): the pre-pass computes ``crop_rect_limited``; a window
+    whose padded size exceeds the limit is shrunk by the smallest integer k that fits (box means of the image, the MAX of each box's mask bytes),
+    the pixels under the mask are the k-fold bilinear upsampling of the prediction (lama_crop_shrink_compose_u8_fwd / lama_crop_shrink_paste_u8_fwd),
+    and such windows form buckets of their own, keyed by their padded low-resolution size.  A window that fits (k = 1) is served as without the key.
 
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
@@ -1116,7 +1203,7 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
                                      rank=rank, world=world, dist=dist, io_threads=io_threads, out_key=out_key, scale_factor=scale_factor,
                                      paste_back=paste_back, device_png=device_png,
                                      device_jpeg=(int(jpeg_quality), ljpeg.subsampling_code(jpeg_subsampling)) if device_jpeg else None,
-                                     crop=(int(crop_margin), int(crop_step)) if crop_to_mask else None)
+                                     crop=(int(crop_margin), int(crop_step), int(crop_max_side)) if crop_to_mask else None)
             except _RangeRestart:
                 continue                     # the generator switched to the 3-term bf16 split (every rank alike): all images again
         raise L.LamaError('range restart did not converge')
@@ -1143,7 +1230,13 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
                 room[0] -= mask.nbytes
         if keep:
             masks[i] = mask
-        return tuple(mask.shape), crop_rect(mask, crop[0], crop[1], pad_mod)
+        if not crop[2]:
+            return tuple(mask.shape), crop_rect(mask, crop[0], crop[1], pad_mod)
+        try:                                 # crop_max_side: (y0, x0, ch, cw[, k]) and the bucket key (Hp, Wp[, 1]) -- k = 1: as without the limit
+            y0, x0, ch, cw, k, _, _, Hp, Wp = crop_rect_limited(mask, crop[0], crop[1], pad_mod, crop[2])
+        except L.LamaError as e:
+            raise L.LamaError(f'{items[i][0]}: {e}; raise crop_max_side or use dataset.scale_factor with paste_back=true for this directory')
+        return tuple(mask.shape), ((y0, x0, ch, cw, Hp, Wp) if k == 1 else (y0, x0, ch, cw, k, Hp, Wp, 1))
 
     if paste_back and scale_factor is None:
         raise L.LamaError('paste_back needs scale_factor: without one the result has the source size already')
@@ -1152,6 +1245,7 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
             raise L.LamaError("crop_to_mask is not served with scale_factor or out_key 'predicted_image': the window is inpainted at the source "
                               "resolution and pasted from 'inpainted'")
         check_crop_options(crop[0], crop[1], pad_mod)
+        check_crop_max_side(crop[2], crop[0], crop[1], pad_mod)
     if device_png and not out_ext.lower().endswith('.png'):
         raise L.LamaError(f'device_png writes PNG files only, not {out_ext!r}')
     if device_jpeg and (device_png or not out_ext.lower().endswith(('.jpg', '.jpeg'))):
@@ -1179,8 +1273,8 @@ def _predict_once(model, items, indir, outdir, *, pad_mod, batch_size, out_ext, 
             for item, hw, (mhw, _) in zip(items, src_sizes, found):
                 if tuple(mhw) != tuple(hw):
                     raise L.LamaError(f'{item[0]}: mask is {mhw[1]}x{mhw[0]} but {item[1]} is {hw[1]}x{hw[0]}')
-            rects = [r[:4] for _, r in found]
-            shapes = [r[4:] for _, r in found]
+            rects = [r[:4] if len(r) == 6 else r[:5] for _, r in found]         # (a fifth value: the shrink k > 1 of crop_max_side)
+            shapes = [r[4:] if len(r) == 6 else r[5:] for _, r in found]         # (a third value: the bucket of the shrunk windows of that size)
             LOOP_TIMES['crop_prepass'] = LOOP_TIMES.get('crop_prepass', 0.0) + time.perf_counter() - t_
         rounds = plan_rounds(shapes, batch_size, world)
         return _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, pad_mod=pad_mod, batch_size=batch_size, out_ext=out_ext,
@@ -1200,7 +1294,8 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
     ``paste_back``: the buckets stay keyed by the padded scaled size, but the u8 results (and the gathered rounds) are the bucket's source slots
     and each PNG is the h x w crop of its SOURCE size.
     ``rects`` (crop_to_mask: the window of every item): the buckets are keyed by the windows' padded size, the steps are ``HostFedStep(crop=True)`` over
-    source slots that hold the bucket's largest source image, and results, gathered rounds and crops are as with ``paste_back``.
+    source slots that hold the bucket's largest source image, and results, gathered rounds and crops are as with ``paste_back``.  A round whose
+    shape carries a third value (crop_max_side) belongs to a bucket of SHRUNK windows: its rects carry their k, its step has ``crop_shrink=True``.
     ``device_png``: a result set is the step's flat buffer (``batch_size`` stream slots, then their int32 lengths) per rank instead of the u8 images:
     the snapshot job copies the stream's bytes out of the pinned set and releases the latch, the pool job wraps and writes.
     ``device_jpeg`` = (quality, subsampling): the same with scans; an image whose scan did not fit its slot (JpegOverflow) is put aside, and at the
@@ -1269,9 +1364,11 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
     submit_loads(1)
     r0 = 0
     while r0 < len(rounds):
-        Hp, Wp = rounds[r0]['shape']
+        shape = rounds[r0]['shape']
+        Hp, Wp = shape[:2]
+        shrink = len(shape) > 2              # crop_max_side: the bucket of the windows shrunk to (Hp, Wp)
         r1 = r0
-        while r1 < len(rounds) and rounds[r1]['shape'] == (Hp, Wp):
+        while r1 < len(rounds) and rounds[r1]['shape'] == shape:
             r1 += 1
         K = r1 - r0
         t_ = time.perf_counter()
@@ -1280,7 +1377,7 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
             members = [src_sizes[i] for rd in rounds[r0:r1] for b in rd['batches'] for i in b]
             src_hw = (max(h for h, _ in members), max(w for _, w in members))
         hs = HostFedStep(model, batch_size, Hp, Wp, device, drain=(world == 1), tune=(K >= TUNE_MIN_ROUNDS), capture=(K >= CAPTURE_MIN_ROUNDS), out_key=out_key,
-                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png, crop=rects is not None,
+                         scale_factor=scale_factor, src_hw=src_hw, paste_back=paste_back, encode_png=device_png, crop=rects is not None, crop_shrink=shrink,
                          **(dict(encode_jpeg=True, jpeg_quality=device_jpeg[0], jpeg_subsampling=device_jpeg[1], jpeg_out_stride=JPEG_OUT_STRIDE) if device_jpeg else {}))
         if device_png:
             png_slot, png_set, png_len_at = hs.png_slot, hs.png_bytes, batch_size * hs.png_slot
@@ -1384,7 +1481,7 @@ def _predict_rounds(model, items, indir, outdir, rounds, sizes, pool, lib, *, pa
 
         if overflowed:                       # device_jpeg, rank 0: the images whose scan did not fit -- a plain u8 step, a download of their own, libjpeg
             fb = HostFedStep(model, batch_size, Hp, Wp, device, drain=True, tune=False, capture=False, out_key=out_key, scale_factor=scale_factor,
-                             src_hw=src_hw, paste_back=paste_back, crop=rects is not None)
+                             src_hw=src_hw, paste_back=paste_back, crop=rects is not None, crop_shrink=shrink)
             for c0 in range(0, len(overflowed), batch_size):
                 part = overflowed[c0:c0 + batch_size]
                 for j in range(batch_size):
@@ -1555,7 +1652,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 out_ext=cfg['out_ext'], device=device, rank=rank, world=world, dist=dist, io_threads=int(cfg['io_threads']), out_key=cfg['out_key'],
                 scale_factor=cfg.get('dataset.scale_factor'), paste_back=bool(cfg['paste_back']), device_png=bool(cfg['device_png']),
                 device_jpeg=bool(cfg['device_jpeg']), jpeg_quality=cfg['jpeg_quality'], jpeg_subsampling=cfg['jpeg_subsampling'],
-                crop_to_mask=bool(cfg['crop_to_mask']), crop_margin=int(cfg['crop_margin']), crop_step=int(cfg['crop_step']))
+                crop_to_mask=bool(cfg['crop_to_mask']), crop_margin=int(cfg['crop_margin']), crop_step=int(cfg['crop_step']),
+                crop_max_side=int(cfg['crop_max_side']))
     dt = time.perf_counter() - t0
     if rank == 0:
         # (the loop's own wall time: plan build + graph capture of every shape bucket, PNG decode, upload, compute, download, PNG encode + write)

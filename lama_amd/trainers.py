@@ -159,6 +159,23 @@ class DefaultInpaintingTrainingModule(nn.Module):
         ex.lib.crop_paste_u8(image_hwc, mask, sizes, rects, L.view(pred), out_u8, B, binarize, st)
         return out_u8
 
+    def forward_u8_crop_shrink(self, image_hwc: torch.Tensor, mask: torch.Tensor, sizes: torch.Tensor, rects: torch.Tensor, shrinks: torch.Tensor,
+                               out_u8: torch.Tensor, Hp: int, Wp: int, binarize: bool = True) -> torch.Tensor:
+        """``crop_max_side`` (no counterpart in the reference): ``forward_u8_crop`` with every window shrunk by its integer ``shrinks`` [B] = k for the
+        generator.  The first launch composes the [B,4,Hp,Wp] input from the k x k box means of each window and the MAX of each box's mask bytes
+        (lama_crop_shrink_compose_u8_fwd), (Hp, Wp) being the padded LOW-RESOLUTION size; the generator call is the one ``forward_u8`` makes for that
+        shape; the last launch writes the source image with, under the mask inside the window, the bilinear k-fold upsampling of the generator's
+        output (lama_crop_shrink_paste_u8_fwd: ``paste_back_u8`` on window coordinates) into ``out_u8`` [B,Hs,Ws,3] (returned)."""
+        ex, st = self._u8_operands('forward_u8_crop_shrink', image_hwc, mask, out_u8)
+        if int(Hp) < 1 or int(Wp) < 1:
+            raise L.LamaError(f'forward_u8_crop_shrink: a padded low-resolution window of at least one pixel, got {Hp}x{Wp}')
+        B = image_hwc.shape[0]
+        # the paste gathers from up to four neighbours of a pixel, some of them where the low-resolution mask is 0: the generator writes every pixel
+        pred = self._generate_u8((B, 4, int(Hp), int(Wp)), image_hwc.device, False,
+                                 lambda masked: ex.lib.crop_shrink_compose_u8(image_hwc, mask, sizes, rects, shrinks, L.view(masked), B, binarize, st))
+        ex.lib.crop_shrink_paste_u8(image_hwc, mask, sizes, rects, shrinks, L.view(pred), out_u8, B, binarize, st)
+        return out_u8
+
 
 def get_training_model_class(kind):
     if kind == 'default':
