@@ -1195,6 +1195,8 @@ def predict(model: trainers.DefaultInpaintingTrainingModule, items: List[Tuple[s
     Host pipeline: the PNGs of round r + 1 are decoded / padded on the thread pool while round r computes, results are
     written on the same pool; a partial last batch of a bucket is zero-padded to ``batch_size`` so that it replays the bucket's
     captured plan instead of building (and capturing) a second one, and a bucket's plan is dropped when the bucket is done."""
+    if crop_max_side and not crop_to_mask:     # as the CLI and the step (crop_shrink without crop) refuse it: the limit is not dropped silently
+        raise L.LamaError(f'crop_max_side={crop_max_side!r} needs crop_to_mask: it limits the window that option inpaints')
     # no host synchronisation per forward: the fp16 split's range flag is read once per bucket, where every rank synchronises anyway
     with _settings(model.generator, defer_range_check=True):
         for _attempt in range(2):

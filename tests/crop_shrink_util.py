@@ -455,11 +455,11 @@ PAIRS = [((40, 56), (10, 20, 8, 12)),     # box + 8 = 16 x 20 -> 16 x 32 at k = 
 WINDOWS = [(6, 10, 16, 32, 1, 16, 32, 16, 32), (3, 0, 64, 64, 2, 32, 32, 32, 32), (0, 0, 96, 96, 3, 32, 32, 32, 32)]
 
 
-def write_pairs(root, seed=3):
-    """The three PNG pairs; each mask is a box of 255 with one pixel of 1 in its corner and zeros."""
+def write_pairs(root, seed=3, pairs=None):
+    """The three PNG pairs (or those of ``pairs``); each mask is a box of 255 with one pixel of 1 in its corner and zeros."""
     from PIL import Image
     os.makedirs(root, exist_ok=True)
-    for i, ((h, w), (by, bx, bh, bw)) in enumerate(PAIRS):
+    for i, ((h, w), (by, bx, bh, bw)) in enumerate(PAIRS if pairs is None else pairs):
         mask = np.zeros((h, w), np.uint8)
         mask[by:by + bh, bx:bx + bw] = 255
         mask[by, bx] = 1
@@ -468,31 +468,32 @@ def write_pairs(root, seed=3):
     return P.list_dataset(root if root.endswith(os.sep) else root + os.sep, '.png')
 
 
-def item_windows(items):
-    wins = [P.crop_rect_limited(P.load_item_u8(*it)[1], MARGIN, STEP, PAD_MOD, MAX_SIDE) for it in items]
-    assert wins == WINDOWS, wins
+def item_windows(items, windows=None, max_side=MAX_SIDE):
+    wins = [P.crop_rect_limited(P.load_item_u8(*it)[1], MARGIN, STEP, PAD_MOD, max_side) for it in items]
+    assert wins == (WINDOWS if windows is None else windows), wins
     return wins
 
 
-def batches_of(wins, batch_size, shrink_k1=False):
+def batches_of(wins, batch_size, shrink_k1=False, pairs=None):
     """[(Hp, Wp), shrunk?, source slot (Hs, Ws), item indices] per batch in the order of the loop: buckets keyed by the padded size and by
     whether k > 1 (``shrink_k1``: the k = 1 windows take the shrink step too, as the step tests run them)."""
     shapes = [(w[7], w[8]) if w[4] == 1 and not shrink_k1 else (w[7], w[8], 1) for w in wins]
+    pairs = PAIRS if pairs is None else pairs
     out = []
     for rd in P.plan_rounds(shapes, batch_size, 1):
         members = [i for i, s in enumerate(shapes) if s == rd['shape']]
-        src_hw = (max(PAIRS[i][0][0] for i in members), max(PAIRS[i][0][1] for i in members))
+        src_hw = (max(pairs[i][0][0] for i in members), max(pairs[i][0][1] for i in members))
         out.append((rd['shape'][:2], len(rd['shape']) > 2, src_hw, rd['batches'][0]))
     return out
 
 
-def definition_want(model, items, wins, device, batch_size):
+def definition_want(model, items, wins, device, batch_size, shrink_k1=False, pairs=None):
     """The definition, per batch of the loop: the numpy-cropped and -shrunk arrays (zeros in the empty slots) -> lama_mask_compose_fwd -> the
     generator call of the step (its dense tail) -> ``paste_back_ref``, pasted by slicing.  k = 1: S = C / 255 and the gather at scale 1 returns
     the sample, which is the crop step's result."""
     lib = model.generator._exec.lib
     want = [None] * len(items)
-    for (Hp, Wp), _, _, batch in batches_of(wins, batch_size):
+    for (Hp, Wp), _, _, batch in batches_of(wins, batch_size, shrink_k1=shrink_k1, pairs=pairs):
         f_img = torch.zeros(batch_size, 3, Hp, Wp, dtype=torch.float32)
         f_msk = torch.zeros(batch_size, 1, Hp, Wp, dtype=torch.float32)
         u8 = [P.load_item_u8(*items[i]) for i in batch]
@@ -515,30 +516,51 @@ def definition_want(model, items, wins, device, batch_size):
 run_step = CU.run_step
 
 
-def check_step(model, items, wins, device, mode, want, batch_size, encode_png=False):
-    """HostFedStep(crop=True, crop_shrink=True) in ``mode`` per batch of the loop (the k = 1 window through the shrink step as well): source-slot
-    results equal to ``want``, zeros around each image and in the empty slots; ``encode_png``: the streams decode to the same pixels."""
+def check_step(model, items, wins, device, mode, want, batch_size, encode_png=False, encode_jpeg=False, jpeg_quality=95, jpeg_subsampling='420',
+               pairs=None):
+    """HostFedStep(crop=True, crop_shrink=True) in ``mode`` per batch of the loop (the k = 1 window through the shrink step as well; the batches
+    of one bucket through ONE step object, as the loop runs them): source-slot results equal to ``want``, zeros around each image and in the empty
+    slots; ``encode_png``: the streams decode to the same pixels; ``encode_jpeg``: the scans are tests/jpeg_ref.py's scans of ``want``, byte for
+    byte.  ``pairs``: the table the items were written from (the default: PAIRS)."""
     from PIL import Image
+    from tests import jpeg_ref
+    pairs = PAIRS if pairs is None else pairs
     u8 = [P.load_item_u8(*it) for it in items]
     got = [None] * len(items)
-    for (Hp, Wp), _, src_hw, batch in batches_of(wins, batch_size, shrink_k1=True):
-        hs = P.HostFedStep(model, batch_size, Hp, Wp, device, drain=True, mode=mode, crop=True, crop_shrink=True, src_hw=src_hw, encode_png=encode_png)
+    enc = dict(encode_jpeg=True, jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling) if encode_jpeg else {}
+    hs = bucket = None
+    for (Hp, Wp), _, src_hw, batch in batches_of(wins, batch_size, shrink_k1=True, pairs=pairs):
+        if bucket != (Hp, Wp, src_hw):
+            hs = P.HostFedStep(model, batch_size, Hp, Wp, device, drain=True, mode=mode, crop=True, crop_shrink=True, src_hw=src_hw,
+                               encode_png=encode_png, **enc)
+            bucket = (Hp, Wp, src_hw)
         assert hs.mode == mode and hs.crop and hs.crop_shrink and hs.out_hw == src_hw and tuple(hs.u8[0].shape) == (batch_size, *src_hw, 3)
         run_step(hs, [(u8[i][0], u8[i][1], wins[i][:5]) for i in batch])
-        assert np.array_equal(hs.crop_sizes(0)[:len(batch)], [PAIRS[i][0] for i in batch])
+        assert np.array_equal(hs.crop_sizes(0)[:len(batch)], [pairs[i][0] for i in batch]) and not hs.crop_sizes(0)[len(batch):].any()
         if encode_png:
             for j, i in enumerate(batch):
-                got[i] = np.array(Image.open(io.BytesIO(P.png_from_zlib(*PAIRS[i][0], 3, bytes(hs.result_png(0, j))))))
-            assert all(len(hs.result_png(0, j)) == 0 for j in range(len(batch), batch_size))
+                got[i] = np.array(Image.open(io.BytesIO(P.png_from_zlib(*pairs[i][0], 3, bytes(hs.result_png(0, j))))))
+            assert all(len(hs.result_png(0, j)) == 0 for j in range(len(batch), batch_size)) and CU.result_raises(hs)
+            continue
+        if encode_jpeg:
+            for j, i in enumerate(batch):
+                got[i] = bytes(hs.result_jpeg(0, j))
+            assert all(len(hs.result_jpeg(0, j)) == 0 for j in range(len(batch), batch_size)) and CU.result_raises(hs)
             continue
         res = hs.result(0).copy()
         for j, i in enumerate(batch):
-            h, w = PAIRS[i][0]
+            h, w = pairs[i][0]
             got[i] = res[j, :h, :w]
             assert not res[j, h:].any() and not res[j, :, w:].any()
         assert not res[len(batch):].any()
+    if encode_jpeg:                                           # byte for byte the restatement's scan of the definition
+        ss = jpeg_ref.J444 if str(jpeg_subsampling) == '444' else jpeg_ref.J420
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert w.shape == pairs[i][0] + (3,)
+            assert g == jpeg_ref.scan_ref(w, *pairs[i][0], jpeg_quality, ss), (mode, i, 'jpeg', len(g))
+        return got
     for i, (g, w) in enumerate(zip(got, want)):
-        assert g.shape == w.shape == PAIRS[i][0] + (3,)
+        assert g.shape == w.shape == pairs[i][0] + (3,)
         assert np.array_equal(g, w), (mode, i, encode_png, np.argwhere(g != w)[:4].tolist())
         mask = u8[i][1]
         assert np.array_equal(g[mask == 0], u8[i][0][mask == 0]) and (g[mask != 0] != u8[i][0][mask != 0]).any()

@@ -453,11 +453,12 @@ PAIRS = [((40, 56), (10, 20, 8, 12)),     # window (6, 10, 16, 32): the 16 x 32 
 WINDOWS = [(6, 10, 16, 32, 16, 32), (26, 1, 16, 16, 16, 16), (17, 45, 16, 16, 16, 16)]
 
 
-def write_pairs(root, seed=3):
-    """The three PNG pairs; each mask is a box of 255 with one pixel of 1 in its corner (any non-zero pixel is hole) and zeros."""
+def write_pairs(root, seed=3, pairs=None):
+    """The three PNG pairs (or those of ``pairs``); each mask is a box of 255 with one pixel of 1 in its corner (any non-zero pixel is hole) and
+    zeros."""
     from PIL import Image
     os.makedirs(root, exist_ok=True)
-    for i, ((h, w), (by, bx, bh, bw)) in enumerate(PAIRS):
+    for i, ((h, w), (by, bx, bh, bw)) in enumerate(PAIRS if pairs is None else pairs):
         mask = np.zeros((h, w), np.uint8)
         mask[by:by + bh, bx:bx + bw] = 255
         mask[by, bx] = 1
@@ -466,13 +467,13 @@ def write_pairs(root, seed=3):
     return P.list_dataset(root if root.endswith(os.sep) else root + os.sep, '.png')
 
 
-def item_rects(items):
+def item_rects(items, windows=None):
     rects = [P.crop_rect(P.load_item_u8(*it)[1], MARGIN, STEP, PAD_MOD) for it in items]
-    assert rects == WINDOWS, rects
+    assert rects == (WINDOWS if windows is None else windows), rects
     return rects
 
 
-def batches_of(rects, batch_size):
+def batches_of(rects, batch_size, pairs=None):
     """[(bucket (Hp, Wp), source slot (Hs, Ws), [item index lists])] in the order of the loop (plan_rounds: the largest bucket first)."""
     rounds = P.plan_rounds([r[4:] for r in rects], batch_size, 1)
     out = []
@@ -480,7 +481,7 @@ def batches_of(rects, batch_size):
         if not out or out[-1][0] != rd['shape']:
             out.append((rd['shape'], None, []))
         out[-1][2].append(rd['batches'][0])
-    sizes = [hw for hw, _ in PAIRS]
+    sizes = [hw for hw, _ in (PAIRS if pairs is None else pairs)]
     return [(shape, (max(sizes[i][0] for b in bs for i in b), max(sizes[i][1] for b in bs for i in b)), bs) for shape, _, bs in out]
 
 
@@ -494,12 +495,12 @@ def run_step(hs, rows):
     hs.flush(0)
 
 
-def cropped_want(model, items, rects, batch_size, device, mode):
+def cropped_want(model, items, rects, batch_size, device, mode, pairs=None):
     """The definition: per bucket and batch the EXISTING u8 HostFedStep, fed the host-cropped pairs in the same slots of the same batch size,
     its [:ch, :cw] results pasted into the decoded sources by numpy slicing -> one source-size u8 image per item."""
     u8 = [P.load_item_u8(*it) for it in items]
     want = [None] * len(items)
-    for (Hp, Wp), _, batches in batches_of(rects, batch_size):
+    for (Hp, Wp), _, batches in batches_of(rects, batch_size, pairs):
         hs = P.HostFedStep(model, batch_size, Hp, Wp, device, drain=True, mode=mode)
         assert hs.u8_input
         for batch in batches:
@@ -513,32 +514,57 @@ def cropped_want(model, items, rects, batch_size, device, mode):
     return want
 
 
-def check_step(model, items, rects, device, mode, want, batch_size, encode_png=False):
+def result_raises(hs) -> bool:
+    """``result()`` of a step that ends with an encoder: the u8 images are not downloaded."""
+    try:
+        hs.result(0)
+    except L.LamaError:
+        return True
+    return False
+
+
+def check_step(model, items, rects, device, mode, want, batch_size, encode_png=False, encode_jpeg=False, jpeg_quality=95, jpeg_subsampling='420',
+               pairs=None):
     """HostFedStep(crop=True) in ``mode`` per bucket: source-slot results equal to ``want``, zeros around each image and in the empty slots;
-    ``encode_png``: the streams decode to the same pixels."""
+    ``encode_png``: the streams decode to the same pixels; ``encode_jpeg``: the scans are tests/jpeg_ref.py's scans of ``want``, byte for byte.
+    ``pairs``: the table the items were written from (the default: PAIRS)."""
     from PIL import Image
+    from tests import jpeg_ref
+    pairs = PAIRS if pairs is None else pairs
     u8 = [P.load_item_u8(*it) for it in items]
     got = [None] * len(items)
-    for (Hp, Wp), src_hw, batches in batches_of(rects, batch_size):
-        hs = P.HostFedStep(model, batch_size, Hp, Wp, device, drain=True, mode=mode, crop=True, src_hw=src_hw, encode_png=encode_png)
+    enc = dict(encode_jpeg=True, jpeg_quality=jpeg_quality, jpeg_subsampling=jpeg_subsampling) if encode_jpeg else {}
+    for (Hp, Wp), src_hw, batches in batches_of(rects, batch_size, pairs):
+        hs = P.HostFedStep(model, batch_size, Hp, Wp, device, drain=True, mode=mode, crop=True, src_hw=src_hw, encode_png=encode_png, **enc)
         assert hs.mode == mode and hs.crop and hs.out_hw == src_hw and tuple(hs.u8[0].shape) == (batch_size, *src_hw, 3)
         for batch in batches:
             run_step(hs, [(u8[i][0], u8[i][1], rects[i]) for i in batch])
-            assert np.array_equal(hs.crop_sizes(0)[:len(batch)], [PAIRS[i][0] for i in batch])
+            assert np.array_equal(hs.crop_sizes(0)[:len(batch)], [pairs[i][0] for i in batch]) and not hs.crop_sizes(0)[len(batch):].any()
             if encode_png:
                 for j, i in enumerate(batch):
-                    h, w = PAIRS[i][0]
+                    h, w = pairs[i][0]
                     got[i] = np.array(Image.open(io.BytesIO(P.png_from_zlib(h, w, 3, bytes(hs.result_png(0, j))))))
-                assert all(len(hs.result_png(0, j)) == 0 for j in range(len(batch), batch_size))
+                assert all(len(hs.result_png(0, j)) == 0 for j in range(len(batch), batch_size)) and result_raises(hs)
+                continue
+            if encode_jpeg:
+                for j, i in enumerate(batch):
+                    got[i] = bytes(hs.result_jpeg(0, j))
+                assert all(len(hs.result_jpeg(0, j)) == 0 for j in range(len(batch), batch_size)) and result_raises(hs)
                 continue
             res = hs.result(0).copy()
             for j, i in enumerate(batch):
-                h, w = PAIRS[i][0]
+                h, w = pairs[i][0]
                 got[i] = res[j, :h, :w]
                 assert not res[j, h:].any() and not res[j, :, w:].any()
             assert not res[len(batch):].any()
+    if encode_jpeg:                                           # byte for byte the restatement's scan of the definition
+        ss = jpeg_ref.J444 if str(jpeg_subsampling) == '444' else jpeg_ref.J420
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert w.shape == pairs[i][0] + (3,)
+            assert g == jpeg_ref.scan_ref(w, *pairs[i][0], jpeg_quality, ss), (mode, i, 'jpeg', len(g))
+        return got
     for i, (g, w) in enumerate(zip(got, want)):
-        assert g.shape == w.shape == PAIRS[i][0] + (3,)
+        assert g.shape == w.shape == pairs[i][0] + (3,)
         assert np.array_equal(g, w), (mode, i, encode_png)
         mask = u8[i][1]
         assert np.array_equal(g[mask == 0], u8[i][0][mask == 0]) and (g[mask != 0] != u8[i][0][mask != 0]).any()
